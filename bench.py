@@ -4,6 +4,9 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N>1 la
 ``torch.distributed.run`` with one rank per GPU. W untimed warmup steps, then EXACTLY K timed full
 training steps (forward + backward + bucketed all-reduce + fused Adam), bracketed by barrier +
 device synchronize on both sides; the max over ranks is reported. Rank 0 prints ONE JSON line.
+A plain run does nothing else. ``--dump-outputs DIR`` also writes the last timed step's loss and the
+master weights it left as ``DIR/*.npy``; ``--full`` adds the untimed extras (comm/compute overlap of
+one more step, cross-rank self-validation with exit 3 on divergence) to the JSON line.
 
 Data: synthetic full-length sequences of the reference's tensor shapes (offline box, no IMDB);
 weights: random-init bert-base-uncased architecture (no hub). Dropout on, as in training.
@@ -26,6 +29,21 @@ from huggingface_sagemaker_tensorflow_distributed_amd.utils.args import batch_si
 
 METRIC = "sequences/sec (whole node) BERT-base seq128 at 1/2/4/8 MI355X"
 BASELINE_VALUE = None  # the reference publishes no number
+DUMP_PARAMS_MAX = 4 * 2**20  # --dump-outputs: elements of params.npy (16 MB of float32)
+
+
+def dump_outputs(out_dir, loss, store):
+    """What the caller of the last timed ``train_step`` holds: the step's loss and the master weights it left."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    params = store.master.detach()
+    if params.numel() > DUMP_PARAMS_MAX:
+        g = torch.Generator(device="cpu").manual_seed(0)
+        idx = torch.randint(0, params.numel(), (DUMP_PARAMS_MAX,), generator=g).sort().values
+        params = params[idx.to(params.device)]
+    np.save(os.path.join(out_dir, "params.npy"), params.float().cpu().numpy())
 
 
 def main():
@@ -49,7 +67,17 @@ def main():
     ap.add_argument("--hip_graph", type=bool_or_auto, default="auto",
                     help="replay the whole step from a captured HIP graph (N=1); auto = the CLI's rule (launch-bound "
                          "steps of <= 2,048 tokens only: off for the headline's 131,072)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step returned to DIR/<name>.npy "
+                         "(float32): loss.npy, and params.npy = the fp32 master weights it left (all of them, or a "
+                         "fixed seeded sample of DUMP_PARAMS_MAX elements)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the comm/compute overlap of one extra step "
+                         "(N > 1, native RCCL engine) and the cross-rank self-validation (exit 3 when it fails); both "
+                         "go into the JSON line")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus != world_env:
@@ -91,7 +119,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for i in range(a.steps):
-        trainer.train_step([batches[i % n_batches]])
+        loss = trainer.train_step([batches[i % n_batches]])
     sync()
     dt = time.perf_counter() - t0
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -99,32 +127,35 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     dt = float(t.item())
     ms = dt * 1e3 / a.steps
-    # comm/compute overlap of one extra, untimed step (native RCCL engine only): per-bucket HIP events
-    overlap = None
-    buck = trainer.bucketer
-    if buck is not None and buck.set_timing(True):
-        trainer.train_step([batches[0]])
-        overlap = buck.overlap_report()
-        buck.set_timing(False)
-        if overlap is not None:
-            overlap.pop("buckets", None)
     value = a.batch_size * world * a.steps / dt
-    # untimed self-validation (the driver's N > 1 runs): every rank ends the timed steps with bit-identical
-    # parameters, and the gradient path really spans the job (native RCCL engine of `world` ranks, its buckets)
-    div = os.environ.get("HSD_FAULT_DIVERGE_RANK")  # test hook: perturb one rank's weights after the timed steps
-    if div is not None and int(div) == rank:
-        with torch.no_grad():
-            trainer.store.master[0] += 1e-3
-    in_sync = params_in_sync(trainer.store)
-    engine = getattr(trainer.bucketer, "engine", None)
-    rccl_world = int(engine.world) if engine is not None else None
-    validation = {"ranks_in_sync": in_sync, "rccl_world": rccl_world, "native_engine": engine is not None,
-                  "n_buckets": len(trainer.bucketer.buckets) if trainer.bucketer is not None else 0,
-                  "grad_bytes_per_step": trainer.store.grad.numel() * trainer.store.grad.element_size()
-                  if world > 1 else 0}
-    if world > 1:
-        validation["rccl_env"] = rccl_env.effective()
-    ok = in_sync and (engine is None or rccl_world == world)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, trainer.store)
+    overlap, validation, ok = None, None, True
+    if a.full:
+        # comm/compute overlap of one extra, untimed step (native RCCL engine only): per-bucket HIP events
+        buck = trainer.bucketer
+        if buck is not None and buck.set_timing(True):
+            trainer.train_step([batches[0]])
+            overlap = buck.overlap_report()
+            buck.set_timing(False)
+            if overlap is not None:
+                overlap.pop("buckets", None)
+        # untimed self-validation (the driver's N > 1 runs): every rank ends the timed steps with bit-identical
+        # parameters, and the gradient path really spans the job (native RCCL engine of `world` ranks, its buckets)
+        div = os.environ.get("HSD_FAULT_DIVERGE_RANK")  # test hook: perturb one rank's weights after the timed steps
+        if div is not None and int(div) == rank:
+            with torch.no_grad():
+                trainer.store.master[0] += 1e-3
+        in_sync = params_in_sync(trainer.store)
+        engine = getattr(trainer.bucketer, "engine", None)
+        rccl_world = int(engine.world) if engine is not None else None
+        validation = {"ranks_in_sync": in_sync, "rccl_world": rccl_world, "native_engine": engine is not None,
+                      "n_buckets": len(trainer.bucketer.buckets) if trainer.bucketer is not None else 0,
+                      "grad_bytes_per_step": trainer.store.grad.numel() * trainer.store.grad.element_size()
+                      if world > 1 else 0}
+        if world > 1:
+            validation["rccl_env"] = rccl_env.effective()
+        ok = in_sync and (engine is None or rccl_world == world)
     if rank == 0:
         print(json.dumps({
             "metric": METRIC, "value": round(value, 2), "unit": "sequences/sec", "n_gpus": world,
@@ -139,7 +170,7 @@ def main():
                        "grad_wire": trainer.bucketer.compression if trainer.bucketer is not None else None,
                        "comm": ("native-rccl" if getattr(trainer.bucketer, "engine", None) is not None
                                 else ("torch-" + backend.state().backend if world > 1 else "none"))},
-            "validation": validation,
+            **({"validation": validation} if validation is not None else {}),
             **({"comm_overlap": overlap} if overlap is not None else {}),
             **({"batch_plan": parts["batch_plan"].as_dict()} if parts.get("batch_plan") is not None else {}),
         }), flush=True)

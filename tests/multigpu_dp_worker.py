@@ -60,7 +60,7 @@ def main(out):
     overlap = None
     if buck is not None and os.environ.get("HSD_MGPU_OVERLAP") == "1" and buck.set_timing(True):
         # one more step with the engine's per-bucket HIP events on (after the compared state was taken): the
-        # comm / compute overlap report bench.py prints for N > 1
+        # comm / compute overlap report bench.py --full prints for N > 1
         tr.train_step([batch])
         torch.cuda.synchronize()
         overlap = buck.overlap_report()

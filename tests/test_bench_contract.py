@@ -29,7 +29,8 @@ def test_bench_driver_line_cpu(n):
     env = dict(os.environ, OMP_NUM_THREADS="1", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", str(n),
-           "--steps", "2", "--warmup", "1", "--batch_size", "2", "--seq_len", "16", "--model", "hsd-tiny-bert"]
+           "--steps", "2", "--warmup", "1", "--batch_size", "2", "--seq_len", "16", "--model", "hsd-tiny-bert",
+           "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -56,11 +57,48 @@ def test_bench_exits_nonzero_when_ranks_diverge():
                HSD_FAULT_DIVERGE_RANK="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2",
-           "--steps", "1", "--warmup", "1", "--batch_size", "2", "--seq_len", "16", "--model", "hsd-tiny-bert"]
+           "--steps", "1", "--warmup", "1", "--batch_size", "2", "--seq_len", "16", "--model", "hsd-tiny-bert",
+           "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and json.loads(lines[0])["validation"]["ranks_in_sync"] is False
+
+
+def _plain_run(tmp_path, name, steps):
+    env = dict(os.environ, OMP_NUM_THREADS="1", HSD_DEVICE="cpu", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    env.pop("WORLD_SIZE", None)
+    out = tmp_path / name
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                        "--batch_size", "2", "--seq_len", "16", "--model", "hsd-tiny-bert", "--dump-outputs", str(out)],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0]), out
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run prints the headline line without the ``--full`` extras; ``--dump-outputs`` writes the last timed
+    step's loss and master weights as float32, identical from run to run, and ``--steps`` sets how many steps ran."""
+    import numpy as np
+
+    d, out = _plain_run(tmp_path, "a", 2)
+    assert KEYS <= set(d), set(d) ^ KEYS
+    assert "validation" not in d and "comm_overlap" not in d
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["dtype"] == "bf16"
+    assert abs(d["value"] - 2 / (d["ms_per_step"] / 1e3)) / d["value"] < 0.01
+    assert sorted(p.name for p in out.iterdir()) == ["loss.npy", "params.npy"]
+    a = {p.name: np.load(p) for p in out.iterdir()}
+    assert a["loss.npy"].dtype == np.float32 and a["loss.npy"].shape == (1,) and np.isfinite(a["loss.npy"]).all()
+    assert a["params.npy"].dtype == np.float32 and a["params.npy"].ndim == 1 and np.isfinite(a["params.npy"]).all()
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
+    _, out_b = _plain_run(tmp_path, "b", 2)
+    for name, v in a.items():
+        assert np.array_equal(v, np.load(out_b / name)), name
+    # one more timed step is one more optimizer step: the weights move
+    _, out_c = _plain_run(tmp_path, "c", 3)
+    assert not np.array_equal(a["params.npy"], np.load(out_c / "params.npy"))
 
 
 def test_bench_refuses_gpus_world_mismatch():
