@@ -50,7 +50,8 @@ void stream_wait(int64_t dst_ptr, int64_t src_ptr) {
 
 void adam_step(torch::Tensor p, torch::Tensor m, torch::Tensor v, torch::Tensor g, c10::optional<torch::Tensor> out,
                c10::optional<torch::Tensor> decay, double step, double eps, double b1, double b2, double gscale,
-               double lr_wd, c10::optional<torch::Tensor> coef, c10::optional<torch::Tensor> out_lo, bool zero_grad) {
+               double lr_wd, c10::optional<torch::Tensor> coef, c10::optional<torch::Tensor> out_lo, bool zero_grad,
+               c10::optional<torch::Tensor> clip) {
   CHECK_CUDA(p); CHECK_CONTIG(p); CHECK_DTYPE(p, torch::kFloat32);
   TORCH_CHECK(!zero_grad || g.is_contiguous(), "adam zero_grad: contiguous gradient");
   CHECK_DTYPE(m, torch::kFloat32); CHECK_DTYPE(v, torch::kFloat32);
@@ -81,9 +82,49 @@ void adam_step(torch::Tensor p, torch::Tensor m, torch::Tensor v, torch::Tensor 
     TORCH_CHECK(o != nullptr && out_lo->numel() == p.numel() && out_lo->is_contiguous(), "out_lo needs out, same size");
     lo = BF(*out_lo);
   }
+  const float* dclip = nullptr;  // fp32 [1] on the device: the step's global-norm clip coefficient (grad_clip_finalize)
+  if (clip.has_value()) {
+    CHECK_CUDA(*clip); CHECK_DTYPE(*clip, torch::kFloat32);
+    TORCH_CHECK(clip->numel() >= 1, "clip: fp32 [1]");
+    dclip = clip->data_ptr<float>();
+  }
   hsd::launch_adam(p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), g.data_ptr(), gbf, o, dm,
                    p.numel(), (float)step, (float)eps, (float)b1, (float)b2, (float)gscale, (float)lr_wd,
-                   dcoef, cur_stream(), lo, zero_grad);
+                   dcoef, cur_stream(), lo, zero_grad, dclip);
+}
+
+// Sum of squares of the gradient slice `g` (a contiguous, 64-aligned view into the flat gradient buffer): one fp32
+// partial per block into partials[slot_base ...]; returns how many were written (grad_sumsq_blocks).
+int64_t grad_sumsq(torch::Tensor g, torch::Tensor partials, int64_t slot_base) {
+  CHECK_CUDA(g); CHECK_CONTIG(g);
+  CHECK_CUDA(partials); CHECK_CONTIG(partials); CHECK_DTYPE(partials, torch::kFloat32);
+  bool gbf = g.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(gbf || g.scalar_type() == torch::kFloat32, "grad must be fp32 or bf16");
+  TORCH_CHECK(g.numel() > 0 && g.numel() % 64 == 0, "gradient slice must be a non-empty multiple of 64 elements");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0, "gradient slice must start 16-B aligned");
+  const int64_t blocks = hsd::grad_sumsq_blocks(g.numel(), gbf);
+  TORCH_CHECK(slot_base >= 0 && slot_base + blocks <= partials.numel(), "partials: slots [", slot_base, ", ",
+              slot_base + blocks, ") outside a buffer of ", partials.numel());
+  hsd::launch_grad_sumsq(g.data_ptr(), gbf, g.numel(), partials.data_ptr<float>() + slot_base, cur_stream());
+  return blocks;
+}
+
+// partials[0 : nparts] -> out[0] = norm (of the gradient x gscale), out[1] = max_norm / norm if norm > max_norm else 1
+void grad_clip_finalize(torch::Tensor partials, int64_t nparts, double gscale, double max_norm, torch::Tensor out,
+                        c10::optional<torch::Tensor> coef) {
+  CHECK_CUDA(partials); CHECK_CONTIG(partials); CHECK_DTYPE(partials, torch::kFloat32);
+  CHECK_CUDA(out); CHECK_CONTIG(out); CHECK_DTYPE(out, torch::kFloat32);
+  TORCH_CHECK(nparts >= 0 && nparts <= partials.numel(), "nparts outside the partials buffer");
+  TORCH_CHECK(out.numel() >= 2, "out: fp32 [2] (norm, coef)");
+  TORCH_CHECK(max_norm > 0.0, "max_norm must be > 0");
+  const float* dcoef = nullptr;  // fp32 [4] on the device, as adam_step's: grad_scale is read from coef[2]
+  if (coef.has_value()) {
+    CHECK_CUDA(*coef); CHECK_DTYPE(*coef, torch::kFloat32);
+    TORCH_CHECK(coef->numel() >= 4, "coef: fp32 [4]");
+    dcoef = coef->data_ptr<float>();
+  }
+  hsd::launch_grad_clip_finalize(partials.data_ptr<float>(), nparts, (float)gscale, dcoef, (float)max_norm,
+                                 out.data_ptr<float>(), cur_stream());
 }
 
 #define OPT_BF(o) ((o).has_value() ? reinterpret_cast<hsd::bf16_t*>((o)->data_ptr()) : nullptr)
@@ -970,7 +1011,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   hsd::register_comm(m);
   m.def("adam_step", &adam_step, py::arg("p"), py::arg("m"), py::arg("v"), py::arg("g"), py::arg("out"),
         py::arg("decay"), py::arg("step"), py::arg("eps"), py::arg("b1"), py::arg("b2"), py::arg("gscale"),
-        py::arg("lr_wd"), py::arg("coef") = py::none(), py::arg("out_lo") = py::none(), py::arg("zero_grad") = false);
+        py::arg("lr_wd"), py::arg("coef") = py::none(), py::arg("out_lo") = py::none(), py::arg("zero_grad") = false,
+        py::arg("clip") = py::none());
+  m.def("grad_sumsq", &grad_sumsq, py::arg("g"), py::arg("partials"), py::arg("slot_base") = 0);
+  m.def("grad_sumsq_blocks", [](int64_t n, bool bf16) { return (int64_t)hsd::grad_sumsq_blocks(n, bf16); });
+  m.def("grad_clip_finalize", &grad_clip_finalize, py::arg("partials"), py::arg("nparts"), py::arg("gscale"),
+        py::arg("max_norm"), py::arg("out"), py::arg("coef") = py::none());
   m.def("ln_fwd_q8", &ln_fwd_q8);
   m.def("stream_wait", &stream_wait);
   m.def("gemm2_on", &gemm2_on);

@@ -32,19 +32,26 @@ __device__ __forceinline__ f32x4 load_grad(const void* __restrict__ g_, int64_t 
 // U chunks of 4 elements per thread per trip, all U x 4 loads issued before the first use (a one-chunk trip
 // leaves ~4 loads in flight per thread, too few to cover HBM latency at the occupancy a CU holds). Every
 // byte is touched once per step, so loads and stores are non-temporal (no L2 / MALL pollution).
-template <bool kGradBf16, bool kWriteBf16, int U, bool kLo = false>
+// kClip (launched when `clip` is given): an instantiation of its own for clipped steps. As a run-time branch the one
+// extra load cost the unclipped bf16-compute kernel 4 VGPRs and a wave of occupancy (72 -> 76, 7 -> 6 waves/SIMD) and
+// the headline 0.2-0.7 % (profiles/grad_clip_cost.log); this way the unclipped kernels keep the code they had.
+template <bool kGradBf16, bool kWriteBf16, int U, bool kLo = false, bool kClip = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ m,
                                                    float* __restrict__ v, void* __restrict__ g_,
                                                    bf16_t* __restrict__ out, const uint8_t* __restrict__ decay,
                                                    int64_t n4, float step, float eps, float b1, float b2,
                                                    float gscale, float lr_wd, const float* __restrict__ coef,
-                                                   bf16_t* __restrict__ out_lo, int zero_g) {
+                                                   bf16_t* __restrict__ out_lo, int zero_g,
+                                                   const float* __restrict__ clip) {
   if (coef != nullptr) {  // HIP-graph replays: this step's scalars live on the device (train/graph.py)
     step = coef[0];
     eps = coef[1];
     gscale = coef[2];
     lr_wd = coef[3];
   }
+  // global-norm clipping (gradnorm.hip): the step's clip coefficient, computed on the device, folded into the
+  // gradient scale by ONE fp32 multiply (a host replay with float32(gscale) * float32(coef) gives the same bits)
+  if constexpr (kClip) gscale *= clip[0];
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += stride * U) {
     f32x4 g[U], pp[U], mm[U], vv[U];
@@ -96,33 +103,34 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
 
 void launch_adam(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* out_bf16,
                  const uint8_t* decay, int64_t n, float step, float eps, float b1, float b2, float gscale,
-                 float lr_wd, const float* coef, hipStream_t stream, bf16_t* out_lo, bool zero_grad) {
+                 float lr_wd, const float* coef, hipStream_t stream, bf16_t* out_lo, bool zero_grad,
+                 const float* clip) {
   const int zg = zero_grad ? 1 : 0;
   int64_t n4 = n / 4;  // n is a multiple of 1024 (FlatParamStore)
   int threads = 256;
   int64_t blocks = (n4 + threads - 1) / threads;
   if (blocks > 256 * 8) blocks = 256 * 8;  // grid-stride: 8 blocks (32 waves) per CU over 256 CUs
   // two 16-B chunks per thread per trip (1 and 4 measured slower: profiles/bench_adam_r2.json)
-#define HSD_ADAM(GB, WB)                                                                                            \
-  hipLaunchKernelGGL((adam_kernel<GB, WB, 2>), dim3((unsigned)blocks), dim3(threads), 0, stream, p, m, v, g,      \
-                     out_bf16, decay, n4, step, eps, b1, b2, gscale, lr_wd, coef, nullptr, zg)
+#define HSD_ADAM_K(GB, WB, LO, CL)                                                                                  \
+  hipLaunchKernelGGL((adam_kernel<GB, WB, 2, LO, CL>), dim3((unsigned)blocks), dim3(threads), 0, stream, p, m, v, \
+                     g, out_bf16, decay, n4, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zg, clip)
+#define HSD_ADAM(GB, WB, LO)                                                                                        \
+  do {                                                                                                              \
+    if (clip != nullptr) HSD_ADAM_K(GB, WB, LO, true); else HSD_ADAM_K(GB, WB, LO, false);                         \
+  } while (0)
   if (out_lo != nullptr) {
     if (out_bf16 == nullptr) abort();
-    if (grad_bf16)
-      hipLaunchKernelGGL((adam_kernel<true, true, 2, true>), dim3((unsigned)blocks), dim3(threads), 0, stream, p, m, v,
-                         g, out_bf16, decay, n4, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zg);
-    else
-      hipLaunchKernelGGL((adam_kernel<false, true, 2, true>), dim3((unsigned)blocks), dim3(threads), 0, stream, p, m,
-                         v, g, out_bf16, decay, n4, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zg);
+    if (grad_bf16) HSD_ADAM(true, true, true); else HSD_ADAM(false, true, true);
     HSD_CHECK_LAUNCH();
     return;
   }
   if (grad_bf16) {
-    if (out_bf16) HSD_ADAM(true, true); else HSD_ADAM(true, false);
+    if (out_bf16) HSD_ADAM(true, true, false); else HSD_ADAM(true, false, false);
   } else {
-    if (out_bf16) HSD_ADAM(false, true); else HSD_ADAM(false, false);
+    if (out_bf16) HSD_ADAM(false, true, false); else HSD_ADAM(false, false, false);
   }
 #undef HSD_ADAM
+#undef HSD_ADAM_K
   HSD_CHECK_LAUNCH();
 }
 

@@ -12,7 +12,16 @@ struct DropoutParams;
 void launch_adam(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* out_bf16,
                  const uint8_t* decay, int64_t n, float step, float eps, float b1, float b2, float gscale,
                  float lr_wd, const float* coef, hipStream_t stream,
-                 bf16_t* out_lo = nullptr, bool zero_grad = false);
+                 bf16_t* out_lo = nullptr, bool zero_grad = false, const float* clip = nullptr);
+
+// gradnorm.hip: global-norm gradient clipping. grad_sumsq writes grad_sumsq_blocks(n, bf16) fp32 partials (one per
+// block, no atomics) for n gradients (a multiple of 64, 16-B aligned); finalize turns `nparts` partials into
+// out[0] = norm = sqrt(sum) * gscale (gscale from coef[2] when coef is given) and out[1] = max_norm / norm if
+// norm > max_norm else 1.
+int grad_sumsq_blocks(int64_t n, bool grad_bf16);
+void launch_grad_sumsq(const void* g, bool grad_bf16, int64_t n, float* partials, hipStream_t stream);
+void launch_grad_clip_finalize(const float* partials, int64_t nparts, float gscale, const float* coef, float max_norm,
+                               float* out, hipStream_t stream);
 
 }  // namespace hsd
 

@@ -61,8 +61,11 @@ class ThroughputMeter:
             if self.cuda:
                 self._events[-1].synchronize()
             ms = self._elapsed_ms(self._events[self.warmup], self._events[-1]) / (n - 1 - self.warmup)
-            self._append({"step": trainer.global_step, "ms_per_step": ms,
-                          "seq_per_s_rank": self.per_rank_batch * 1e3 / ms, "time": time.time()})
+            rec = {"step": trainer.global_step, "ms_per_step": ms,
+                   "seq_per_s_rank": self.per_rank_batch * 1e3 / ms, "time": time.time()}
+            if getattr(trainer.optimizer, "max_grad_norm", 0.0) > 0.0:
+                rec["grad_norm"] = trainer.optimizer.grad_norm()  # --max_grad_norm: read at log time only
+            self._append(rec)
 
     def on_epoch_end(self, trainer, epoch, logs):
         pass

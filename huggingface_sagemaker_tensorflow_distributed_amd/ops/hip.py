@@ -261,12 +261,36 @@ def _empty(shape, like, dtype=None):
 
 
 # ------------------------------------------------------------------------------------------ optimizer
-def adam_step(p, m, v, g, out, decay, step, eps, b1, b2, gscale, lr_wd, coef=None, out_lo=None, zero_grad=False):
+def adam_step(p, m, v, g, out, decay, step, eps, b1, b2, gscale, lr_wd, coef=None, out_lo=None, zero_grad=False,
+              clip=None):
     """``coef``: optional fp32 [4] device tensor (step, eps, grad_scale, lr*wd) read by the kernel instead of the
     host scalars (captured HIP-graph steps, train/graph.py). ``out_lo``: with ``out``, the kernel writes the updated
     weights' bf16 hi / lo halves (fp32 compute: the split-product GEMMs' operands, ops/hip32.py). ``zero_grad``: the
-    kernel also clears ``g`` after reading it."""
-    _C.adam_step(p, m, v, g, out, decay, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zero_grad)
+    kernel also clears ``g`` after reading it. ``clip``: optional fp32 [1] device tensor, the step's global-norm
+    clip coefficient (:func:`grad_clip_finalize`), multiplied into the gradient scale by the kernel."""
+    if clip is None:
+        _C.adam_step(p, m, v, g, out, decay, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zero_grad)
+    else:
+        _C.adam_step(p, m, v, g, out, decay, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zero_grad, clip)
+
+
+def grad_sumsq_blocks(n: int, bf16: bool = False) -> int:
+    """Partials one :func:`grad_sumsq` launch over ``n`` gradients writes (fixed by ``n``: sizes the workspace)."""
+    return int(_C.grad_sumsq_blocks(int(n), bool(bf16)))
+
+
+def grad_sumsq(g, partials, slot_base: int = 0) -> int:
+    """Sum of squares of the contiguous gradient slice ``g`` (fp32 / bf16, a multiple of 64 elements, 64-aligned in
+    its buffer) as one fp32 partial per block in ``partials[slot_base:]``; returns the number written. No atomics:
+    bit-reproducible."""
+    return int(_C.grad_sumsq(g, partials, int(slot_base)))
+
+
+def grad_clip_finalize(partials, nparts: int, gscale: float, max_norm: float, out, coef=None) -> None:
+    """``out[0] = norm = sqrt(sum(partials[:nparts])) * gscale`` and ``out[1] = max_norm / norm if norm > max_norm
+    else 1`` on the device (fp64 sum, fixed order). ``coef``: the fp32 [4] device scalars of a captured step; the
+    gradient scale is then ``coef[2]``."""
+    _C.grad_clip_finalize(partials, int(nparts), float(gscale), float(max_norm), out, coef)
 
 
 # ------------------------------------------------------------------------------------------ linear

@@ -19,6 +19,15 @@ a side stream the moment its last gradient is queued; data-parallel ranks run it
 right after the slice's bucket all-reduce. The memory-bound update then shares the GPU with the compute-bound
 backward GEMMs instead of following them (the bert-large optimizer pass moves ~10 GB per step). What is left
 at ``step()`` is the join, the slices no gradient reached, and the batched Wᵀ refresh.
+
+Global-norm clipping (``max_grad_norm=C > 0``; ``tf.clip_by_global_norm``, the math of Keras ``global_clipnorm``, no
+epsilon): with ``g`` the gradient averaged over ranks and accumulation micro-steps, ``coef = C / ‖g‖₂`` if ``‖g‖₂ > C``
+else 1, and Adam consumes ``coef · g``. Exact clipping needs the whole norm before any weight moves, so in clip mode
+the overlap hooks run each slice's sum of squares under the backward instead of its update, and ``step()`` finishes
+the norm on the device (no host round trip: a captured whole-step graph replays it) and runs ONE Adam over the whole
+buffer that reads the coefficient from device memory. Data-parallel ranks take the norm over the all-reduced buffer,
+which holds the same values on every rank (also with a bf16 / fp16 wire: every rank casts back the same reduced
+values), so they agree on ``coef`` bit for bit without another collective.
 """
 from __future__ import annotations
 
@@ -37,9 +46,12 @@ class FusedAdam:
     per_slice_fp8 = True
 
     def __init__(self, store: FlatParamStore, lr: float = 1e-3, betas=(0.9, 0.999), eps: Optional[float] = None,
-                 weight_decay: float = 0.0, eps_mode: str = "keras", decoupled: bool = True):
+                 weight_decay: float = 0.0, eps_mode: str = "keras", decoupled: bool = True,
+                 max_grad_norm: float = 0.0):
         if eps_mode not in ("keras", "torch"):
             raise ValueError(eps_mode)
+        if not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"max_grad_norm must be >= 0 (0 = off, inf = report the norm only): {max_grad_norm!r}")
         self.store = store
         self.lr = float(lr)
         self.beta1, self.beta2 = map(float, betas)
@@ -53,6 +65,66 @@ class FusedAdam:
         self._decay_mask = store.decay_block_mask(ALIGN) if weight_decay else None
         self.dcoef: Optional[torch.Tensor] = None  # device-side step scalars (HIP-graph replays), see use_device_coef
         self._capturing = False  # dcoef is handed to the kernel only while a whole-step graph is being captured
+        # global-norm clipping: [norm, coef] of the last step and the per-block partial sums of squares, on the device
+        # at addresses that stay put (a captured graph replays the launches that read and write them). On or off is
+        # fixed here; the value of C may change between eager steps (it travels as a kernel argument)
+        self.max_grad_norm = float(max_grad_norm)
+        self._clip_out: Optional[torch.Tensor] = None
+        self._clip_partials: Optional[torch.Tensor] = None
+        self._clip_bases: List[int] = []  # first partial slot of each overlap slice
+        self._clip_nparts = 0
+        if self.max_grad_norm > 0.0:
+            self._clip_out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=store.master.device)
+            self._plan_clip([])
+
+    # -------------------------------------------------------------------------- global-norm clipping
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """Device scalar: the global norm of the last step's (averaged) gradient; None with clipping off."""
+        return self._clip_out[0] if self._clip_out is not None else None
+
+    @property
+    def last_clip_coef(self) -> Optional[torch.Tensor]:
+        """Device scalar: the factor the last step's gradient was scaled by (1 = not clipped)."""
+        return self._clip_out[1] if self._clip_out is not None else None
+
+    def grad_norm(self) -> float:
+        """The global gradient norm of the last step, as a float. Synchronises with the device: call it only when
+        logging. Needs ``max_grad_norm > 0`` (``inf`` measures the norm and never clips)."""
+        if self._clip_out is None:
+            raise RuntimeError("FusedAdam.grad_norm(): construct with max_grad_norm > 0 (inf = report only)")
+        return float(self._clip_out[0].item())
+
+    def _plan_clip(self, ranges) -> None:
+        """Partial-sum slots of the overlap slices ``ranges`` (the whole buffer as one slice always fits too)."""
+        s = self.store
+        if self._clip_out is None or not s.master.is_cuda:
+            return
+        from ..ops import hip
+
+        bf = s.grad.dtype == torch.bfloat16
+        self._clip_bases, n = [], 0
+        for st, e in ranges:
+            self._clip_bases.append(n)
+            n += hip.grad_sumsq_blocks(e - st, bf)
+        self._clip_nparts = n
+        need = max(n, hip.grad_sumsq_blocks(s.numel, bf))
+        if self._clip_partials is None or self._clip_partials.numel() < need:
+            self._clip_partials = torch.zeros(need, dtype=torch.float32, device=s.master.device)
+
+    def _clipped_step(self, nparts: int, step: float, eps_eff: float, gscale: float, zero_grad: bool) -> None:
+        """Finish the norm from ``nparts`` partials, then ONE Adam over the whole buffer with the device-side clip
+        coefficient, then the end-of-step weight-copy refresh (current stream)."""
+        from ..ops import hip
+
+        s = self.store
+        hip.grad_clip_finalize(self._clip_partials, nparts, gscale, self.max_grad_norm, self._clip_out,
+                               self._kernel_coef())
+        out, out_lo = s.adam_outputs(0, s.numel)
+        hip.adam_step(s.master, self.exp_avg, self.exp_avg_sq, s.grad, out, self._decay_mask, step, eps_eff,
+                      self.beta1, self.beta2, gscale, self.lr * self.weight_decay, self._kernel_coef(), out_lo,
+                      zero_grad=zero_grad, clip=self._clip_out[1:2])
+        s.refresh_transposed()
 
     # --------------------------------------------------------------------------
     def state_tensors(self) -> List[torch.Tensor]:
@@ -123,6 +195,7 @@ class FusedAdam:
         self._ranges = list(ranges)
         self._done = [False] * len(self._ranges)
         self._began = False
+        self._plan_clip(self._ranges)
         # each slice's Wᵀ copies are refreshed right after its update (fp8 weight copies, which need the whole
         # step's amax, are still re-quantised once at the end)
         self._tsub = self.store.transposed_subsets(self._ranges) if self.store.master.is_cuda else None
@@ -156,13 +229,19 @@ class FusedAdam:
 
     @torch.no_grad()
     def step_range(self, b: int) -> None:
-        """Adam on slice ``b`` on the CURRENT stream (the caller orders it after the slice's gradients)."""
+        """Adam on slice ``b`` on the CURRENT stream (the caller orders it after the slice's gradients). With
+        ``max_grad_norm``: the slice's sum of squares instead -- no weight may move before the whole norm is known;
+        the update (and the Wᵀ / fp8 refresh) is one pass at :meth:`step`."""
         if not self._began or self._done[b]:
             return
         from ..ops import hip
 
         st, e = self._ranges[b]
         s = self.store
+        if self._clip_out is not None:
+            hip.grad_sumsq(s.grad[st:e], self._clip_partials, self._clip_bases[b])
+            self._done[b] = True
+            return
         step, eps_eff, gscale = self._coef
         out, out_lo = s.adam_outputs(st, e)
         dm = self._decay_mask[st // ALIGN:(e + ALIGN - 1) // ALIGN] if self._decay_mask is not None else None
@@ -185,7 +264,11 @@ class FusedAdam:
         for b in range(len(self._ranges)):  # slices no gradient reached (unused parameters)
             self.step_range(b)
         self._began = False
-        self._zero = False
+        zero, self._zero = getattr(self, "_zero", False), False
+        if self._clip_out is not None:
+            # every slice's partials were rewritten this step (under the backward, or just above)
+            self._clipped_step(self._clip_nparts, self._coef[0], self._coef[1], self._coef[2], zero)
+            return
         if self._tsub is None:
             self.store.refresh_transposed()
         elif self._f8sub is not None:
@@ -210,6 +293,10 @@ class FusedAdam:
             from ..ops import hip
 
             hip.join_side_streams()  # weight gradients may still be in flight on the wgrad stream
+            if self._clip_out is not None:
+                n = hip.grad_sumsq(s.grad, self._clip_partials, 0)
+                self._clipped_step(n, step, eps_eff, float(grad_scale), zero_grad)
+                return
             out, out_lo = s.adam_outputs(0, s.numel)
             hip.adam_step(s.master, self.exp_avg, self.exp_avg_sq, s.grad, out,
                           self._decay_mask, step, eps_eff, self.beta1, self.beta2, float(grad_scale),
@@ -217,7 +304,15 @@ class FusedAdam:
             s.refresh_transposed()
             return
         # reference path (CPU): identical math on flat buffers
-        g = s.grad.to(torch.float32) * grad_scale
+        g = s.grad.to(torch.float32)
+        if self._clip_out is not None:
+            # the GPU path's formula: norm in fp64, coef and grad_scale * coef rounded to fp32
+            gs32 = torch.tensor(float(grad_scale), dtype=torch.float32)
+            norm = math.sqrt(float(g.double().square().sum()) * float(gs32) ** 2)
+            coef = self.max_grad_norm / norm if norm > self.max_grad_norm else 1.0
+            self._clip_out[0], self._clip_out[1] = norm, coef
+            grad_scale = float(gs32 * self._clip_out[1])
+        g = g * grad_scale
         if self.weight_decay:
             wd = self._decay_mask.repeat_interleave(ALIGN)[: s.numel].to(torch.float32)
             s.master.mul_(1.0 - self.lr * self.weight_decay * wd)

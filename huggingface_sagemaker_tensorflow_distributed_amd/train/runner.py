@@ -129,7 +129,8 @@ def build(args, mode: str):
     base_lr = float(args.learning_rate)
     lr = base_lr * world if mode == "train" else base_lr  # scripts/train.py:112 vs singe_node_train.py:78
     opt = FusedAdam(store, lr=lr, eps=args.adam_epsilon, eps_mode=args.adam_eps_mode,
-                    weight_decay=args.weight_decay if args.optimizer == "adamw" else 0.0)
+                    weight_decay=args.weight_decay if args.optimizer == "adamw" else 0.0,
+                    max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0))
     batch_plan = None
     if args.train_batch_size == "auto":
         # sized on the device before any readiness hook / bucketer exists (the probes are plain fwd + bwd)

@@ -236,7 +236,16 @@ class Trainer:
         return loss, logits
 
     def train_step(self, micro_batches: List[Dict[str, torch.Tensor]], meter: Optional[_Meter] = None) -> torch.Tensor:
-        """One optimizer step over ``len(micro_batches)`` accumulation micro-steps."""
+        """One optimizer step over ``len(micro_batches)`` accumulation micro-steps.
+
+        Gradients after the step: ``store.grad`` is NOT the gradient the step applied. Eager GPU steps leave it all
+        zeros (the fused Adam clears what it read, ``zero_grad_in_optimizer``); captured steps and CPU steps leave the
+        raw accumulated sum, before the ``1 / (world x micro-steps)`` average and before any clipping. With the
+        optimizer overlap the update has moreover been applied slice by slice under the backward, so nothing computed
+        from ``store.grad`` after the step can change it. To observe gradients, ask the optimizer:
+        ``FusedAdam(max_grad_norm=...)`` computes the global norm of the averaged gradient on the device inside the
+        step, ``optimizer.grad_norm()`` reads it (a device sync: call it when logging), and ``--max_grad_norm inf``
+        reports the norm without ever clipping."""
         self.model.train()
         if self._seed is not None and self._graph_replay and self._full_graph and len(micro_batches) == 1:
             return self._graph_step(micro_batches[0], meter)
@@ -408,9 +417,12 @@ class Trainer:
                     wd.step_end(self.global_step - 1, self.device)
                 if verbose and self.rank == 0 and self.log_every and (step + 1) % self.log_every == 0:
                     r = meter.result(global_=False)
-                    logger.info("epoch %d step %d/%d - loss: %.4f - sparse_categorical_accuracy: %.4f - %.1f ms/step",
+                    # --max_grad_norm: the last step's global gradient norm (a device read, at log time only)
+                    gn = (" - grad_norm=%.4g" % self.optimizer.grad_norm()
+                          if getattr(self.optimizer, "max_grad_norm", 0.0) > 0.0 else "")
+                    logger.info("epoch %d step %d/%d - loss: %.4f - sparse_categorical_accuracy: %.4f - %.1f ms/step%s",
                                 epoch + 1, step + 1, nsteps, r["loss"], r["sparse_categorical_accuracy"],
-                                (time.time() - t0) * 1e3 / (step + 1))
+                                (time.time() - t0) * 1e3 / (step + 1), gn)
                 for cb in callbacks:
                     cb.on_batch_end(self, step)
             for _ in it:  # drain the prefetch thread

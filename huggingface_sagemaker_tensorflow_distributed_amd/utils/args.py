@@ -93,6 +93,10 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
     g.add_argument("--adam_eps_mode", choices=["keras", "torch"], default="keras")
     g.add_argument("--adam_epsilon", type=float, default=None)
     g.add_argument("--gradient_accumulation_steps", type=int, default=1)
+    g.add_argument("--max_grad_norm", type=float, default=0.0,
+                   help="clip the global gradient norm (over all parameters, after the rank / accumulation average) to "
+                        "this value inside the fused optimizer step (tf.clip_by_global_norm / Keras global_clipnorm "
+                        "math); 0 (default) = off, as the reference; inf = measure and log the norm, never clip")
     g.add_argument("--lr_schedule", choices=["constant", "linear"], default="constant",
                    help="constant = Keras Adam(learning_rate) (reference); linear = warmup then linear decay to 0")
     g.add_argument("--lr_warmup_steps", type=int, default=0, help="linear warmup steps of the learning rate")
