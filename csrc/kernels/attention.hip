@@ -225,6 +225,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t* __restrict_
     *reinterpret_cast<u32x4*>(Kall + toff(row, ch * 8)) = kv;
   }
   const float kb2 = mask_bias2(mask, b, S, key);
+  // a sequence with every key masked: p below is 1 where 1/S is meant, folded into the output scales (common.h)
+  const float pw = all_masked_scale(lse2[(size_t)bh * S], S);
+  scale *= pw;
   f32x16 dk0 = {}, dk1 = {}, dv0 = {}, dv1 = {};
   const bool single = S <= 128;
   const int nqb = (S + 31) / 32;
@@ -343,11 +346,11 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t* __restrict_
       w.x = pack_bf2(dk1[4 * i] * scale, dk1[4 * i + 1] * scale);
       w.y = pack_bf2(dk1[4 * i + 2] * scale, dk1[4 * i + 3] * scale);
       *reinterpret_cast<u32x2*>(dk + 32 + d) = w;
-      w.x = pack_bf2(dv0[4 * i], dv0[4 * i + 1]);
-      w.y = pack_bf2(dv0[4 * i + 2], dv0[4 * i + 3]);
+      w.x = pack_bf2(dv0[4 * i] * pw, dv0[4 * i + 1] * pw);
+      w.y = pack_bf2(dv0[4 * i + 2] * pw, dv0[4 * i + 3] * pw);
       *reinterpret_cast<u32x2*>(dvp + d) = w;
-      w.x = pack_bf2(dv1[4 * i], dv1[4 * i + 1]);
-      w.y = pack_bf2(dv1[4 * i + 2], dv1[4 * i + 3]);
+      w.x = pack_bf2(dv1[4 * i] * pw, dv1[4 * i + 1] * pw);
+      w.y = pack_bf2(dv1[4 * i + 2] * pw, dv1[4 * i + 3] * pw);
       *reinterpret_cast<u32x2*>(dvp + 32 + d) = w;
     }
   }

@@ -345,9 +345,11 @@ __global__ __launch_bounds__(256, 3) void attn128_bwd_kernel(const bf16_t* __res
     bf16_t* stg = dSt + wave * 32 * D;
     bf16_t* rowbase = dqkv + ((int64_t)b * S + wave * 32) * ld + hh * D;
     float* bs_w = dbias ? bsum + wave * D : nullptr;
-    store_rows(stg, dv0, dv1, 1.0f, rowbase + 2 * H, ld, lane, dbias ? bs_w + 2 * 4 * D : nullptr);
-    store_rows(stg, dk0, dk1, scale, rowbase + H, ld, lane, dbias ? bs_w + 4 * D : nullptr);
-    store_rows(stg, dq0, dq1, scale, rowbase, ld, lane, bs_w);
+    // a sequence with every key masked: the probabilities above were 1 where 1/S is meant (common.h)
+    const float pw = all_masked_scale(lse_s[0], S);
+    store_rows(stg, dv0, dv1, pw, rowbase + 2 * H, ld, lane, dbias ? bs_w + 2 * 4 * D : nullptr);
+    store_rows(stg, dk0, dk1, scale * pw, rowbase + H, ld, lane, dbias ? bs_w + 4 * D : nullptr);
+    store_rows(stg, dq0, dq1, scale * pw, rowbase, ld, lane, bs_w);
   }
   if (dbias) {
     // qkv bias gradient: column sums of this (batch, head)'s dQ | dK | dV, one atomic per column

@@ -338,8 +338,10 @@ __global__ __launch_bounds__(256, 2) void attn32m_bwd_kv_kernel(const bf16_t* __
     }
   }
   float* rowbase = dqkv + ((int64_t)b * S + k0) * ld + hh * D;
-  store_rows32(dv0, dv1, 1.0f, rowbase + 2 * H, ld, lane);
-  store_rows32(dk0, dk1, scale, rowbase + H, ld, lane);
+  // a sequence with every key masked: the probabilities above were 1 where 1/S is meant (common.h)
+  const float pw = all_masked_scale(lse_s[0], S);
+  store_rows32(dv0, dv1, pw, rowbase + 2 * H, ld, lane);
+  store_rows32(dk0, dk1, scale * pw, rowbase + H, ld, lane);
 }
 
 // ------------------------------------------------------------------------------------------------ backward dQ
@@ -455,7 +457,8 @@ __global__ __launch_bounds__(256, 2) void attn32m_bwd_q_kernel(const bf16_t* __r
       }
     }
   }
-  store_rows32(dq0, dq1, scale, dqkv + ((int64_t)b * S + q0) * ld + hh * D, ld, lane);
+  // (a sequence with every key masked: the probabilities above were 1 where 1/S is meant, common.h)
+  store_rows32(dq0, dq1, scale * all_masked_scale(lse_q, S), dqkv + ((int64_t)b * S + q0) * ld + hh * D, ld, lane);
 }
 
 // fp32 x [n] -> hi = bf16(x), lo = bf16(x - hi)

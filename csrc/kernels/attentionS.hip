@@ -397,6 +397,8 @@ __global__ __launch_bounds__(256, 2) void attnS_bwd_kv_kernel(const bf16_t* __re
 #pragma unroll 1
   for (int t = 0, stg = 0; t < nt; ++t, stg = stg == NSTG - 1 ? 0 : stg + 1) tile(stg, t);
   __syncthreads();  // Q images no longer read: reuse as staging
+  // a sequence with every key masked: the probabilities above were 1 where 1/S is meant (common.h)
+  const float pw = all_masked_scale(lse_s[0], S);
   bf16_t* stg_w = Qb + wave * 32 * D;
   const int64_t roff = ((int64_t)b * S + k0) * ld + hh * D;
   bf16_t* rowbase = dqkv + roff;
@@ -404,9 +406,9 @@ __global__ __launch_bounds__(256, 2) void attnS_bwd_kv_kernel(const bf16_t* __re
   uint8_t* q8b = q8o.q != nullptr ? q8o.q + roff : nullptr;
   float qs = 0.f, qm = 0.f;
   if (q8b != nullptr) qs = fmt_scale(qfmt, *q8o.amax_in);
-  store_rows(stg_w, dv0, dv1, 1.0f, rowbase + 2 * H, ld, lane, dbias ? bsum + (4 + wave) * D : nullptr,
+  store_rows(stg_w, dv0, dv1, pw, rowbase + 2 * H, ld, lane, dbias ? bsum + (4 + wave) * D : nullptr,
              q8b ? q8b + 2 * H : nullptr, qfmt, qs, &qm, q8o.only != 0);
-  store_rows(stg_w, dk0, dk1, scale, rowbase + H, ld, lane, dbias ? bsum + wave * D : nullptr,
+  store_rows(stg_w, dk0, dk1, scale * pw, rowbase + H, ld, lane, dbias ? bsum + wave * D : nullptr,
              q8b ? q8b + H : nullptr, qfmt, qs, &qm, q8o.only != 0);
   if (q8b != nullptr) wave_amax_track(qm, q8o.amax_track);
   if (dbias) {
@@ -553,7 +555,9 @@ __global__ __launch_bounds__(256, 2) void attnS_bwd_q_kernel(const bf16_t* __res
     qs = fmt_scale(qfmt, *q8o.amax_in);
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *q8o.sinv = 1.0f / qs;
   }
-  store_rows(Kb + wave * 32 * D, dq0, dq1, scale, dqkv + qoff, ld, lane, dbias ? bsum + wave * D : nullptr,
+  // (a sequence with every key masked: the probabilities above were 1 where 1/S is meant, common.h)
+  store_rows(Kb + wave * 32 * D, dq0, dq1, scale * all_masked_scale(lse_q, S), dqkv + qoff, ld, lane,
+             dbias ? bsum + wave * D : nullptr,
              q8o.q != nullptr ? q8o.q + qoff : nullptr, qfmt, qs, &qm, q8o.only != 0);
   if (q8o.q != nullptr) wave_amax_track(qm, q8o.amax_track);
   if (dbias) {

@@ -122,6 +122,15 @@ __device__ __forceinline__ float max_xor32(float v) {
   return fmaxf(__uint_as_float(p[0]), __uint_as_float(p[1]));
 }
 
+// ---- attention backward: a sequence whose keys are ALL masked ------------------------------------
+// Every attention kernel clamps the additive key bias (log2 domain) at -1e30. A sequence with every key at the clamp
+// has all its scores absorbed (x = -1e30 exactly), so the forward gives the uniform softmax 1/S, as the reference
+// does (ops/reference.py: s + finfo.min == finfo.min), and saves lse2 = -1e30 + log2(S) == -1e30f: the log2(S) term
+// is lost. The backward's exp2(x - lse2) is then exactly 1 for every (query, key) where 1/S is meant. dQ, dK and dV
+// are linear in the probabilities, so the backward kernels multiply their outputs' scale by this factor instead:
+// 1/S for such a sequence (told by the saved lse2 of any of its rows), 1 otherwise.
+__device__ __forceinline__ float all_masked_scale(float lse2, int S) { return lse2 <= -1e30f ? 1.0f / (float)S : 1.0f; }
+
 // ---- wave64 reductions ---------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -590,6 +590,8 @@ __global__ __launch_bounds__(64) void attn32_dq_kernel(const float* __restrict__
     }
   }
   if (!valid) return;
+  // a sequence with every key masked: the probabilities above were 1 where 1/S is meant (common.h)
+  scale *= all_masked_scale(ls, S);
   float* op = dqkv + ((int64_t)b * S + q) * ld + h * AD;
 #pragma unroll
   for (int d = 0; d < AD; d += 4)
@@ -689,7 +691,8 @@ __global__ __launch_bounds__(64) void attn32_dkv_kernel(const float* __restrict_
   }
   if (!valid) return;
   // DK: Qs held q · sl2 = q · log2(e)/√d; dk = (1/√d) Σ ds q = Σ ds (q·sl2) / log2(e)
-  const float f = DV ? 1.0f : scale / sl2;
+  // (a sequence with every key masked: the probabilities above were 1 where 1/S is meant, common.h)
+  const float f = (DV ? 1.0f : scale / sl2) * all_masked_scale(lse[(int64_t)bh * S], S);
   float* op = dqkv + ((int64_t)b * S + k) * ld + (DV ? 2 * H : H) + h * AD;
 #pragma unroll
   for (int d = 0; d < AD; d += 4)

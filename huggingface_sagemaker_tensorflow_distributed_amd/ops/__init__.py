@@ -112,7 +112,8 @@ def attn_block(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, batch,
                p_hidden, seed_hidden, q8_next=None):
     """Self-attention sub-block: ``LN(dropout(attn(h Wqkvᵀ + b) Woᵀ + bo) + h)``. ``q8_next``: the weight of the
     GEMM that consumes the output (HIP fp8 path: the LayerNorm writes its fp8 input copy)."""
-    if _hip(h) and h.dtype == torch.bfloat16 and qkv_w.shape[0] == 3 * heads * 64:
+    if _hip(h) and h.dtype == torch.bfloat16 and qkv_w.shape[0] == 3 * heads * 64 and seq % 2 == 0:
+        # (an odd sequence length: the three ops below, with the reference attention -- ops/hip.py attention_ok)
         return _hipmod().attn_block(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, batch, seq, heads,
                                     p_attn, seed_attn, p_hidden, seed_hidden, q8_next)
     if _hip32(h) and _hip32mod().attn_block_ok(h, qkv_w, seq, heads):

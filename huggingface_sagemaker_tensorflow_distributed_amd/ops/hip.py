@@ -573,8 +573,14 @@ def _attn_ws(B, S, heads, device):
     return (torch.zeros if zero else torch.empty)(n, dtype=torch.float32, device=device)
 
 
+def attention_ok(qkv, seq, heads) -> bool:
+    """The attention kernels take head dim 64 and an even sequence length (their dropout hash covers column pairs,
+    csrc/bindings.cpp attn_fwd); the rest runs the reference op, as on the fp32 path (ops/hip32.py attention_ok)."""
+    return qkv.shape[-1] == 3 * heads * 64 and seq % 2 == 0
+
+
 def attention(qkv, mask_bias, batch, seq, heads, p, seed):
-    if qkv.shape[-1] != 3 * heads * 64:
+    if not attention_ok(qkv, seq, heads):
         from .reference import attention as ref
 
         return ref(qkv, mask_bias, batch, seq, heads, p, seed, p > 0)
@@ -1044,7 +1050,12 @@ class _AttnBlock(torch.autograd.Function):
 def attn_block(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, B, S, heads, p_a, seed_a, p_h, seed_h,
                q8_next=None):
     """``q8_next``: the weight of the GEMM that consumes this block's output (the FFN's W1): its fp8 input copy is
-    written by this block's LayerNorm."""
+    written by this block's LayerNorm. A sequence length the attention kernels do not take (:func:`attention_ok`: odd
+    S) runs the block as its three ops, with the reference attention between the HIP linear layers."""
+    if S % 2:
+        qkv = linear(h.reshape(-1, h.shape[-1]), qkv_w, qkv_b)
+        actx = attention(qkv, mask_bias, B, S, heads, p_a, seed_a)
+        return dense_residual_ln(actx, out_w, out_b, h, ln_w, ln_b, eps, p_h, seed_h)
     return _AttnBlock.apply(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, B, S, heads, p_a, seed_a,
                             p_h, seed_h, q8_next)
 
