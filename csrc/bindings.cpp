@@ -457,6 +457,61 @@ void fp8_quant_many(torch::Tensor amax_desc, int64_t amax_blocks, torch::Tensor 
                              amax.data_ptr<float>(), sinv.data_ptr<float>(), (int)fmt, cur_stream());
 }
 
+// The epilogue arguments of a bf16-output GEMM (gemm2, gemm2_on, gemm8) against what epilogue `epi` reads and writes
+// (gemm_plan.h Epi2 predicates); returns the optional fp32 outputs' pointers.
+struct GemmEpiOut {
+  float* dbias = nullptr;
+  float* rd = nullptr;
+};
+static GemmEpiOut check_gemm_epilogue_args(const char* who, int64_t epi, int64_t M, int64_t N, const torch::Tensor& C,
+                                           const c10::optional<torch::Tensor>& bias,
+                                           const c10::optional<torch::Tensor>& aux,
+                                           const c10::optional<torch::Tensor>& C2,
+                                           const c10::optional<torch::Tensor>& dbias,
+                                           const c10::optional<torch::Tensor>& rd, int64_t rd_seq) {
+  if (hsd::epi_bias((int)epi)) {
+    TORCH_CHECK(bias.has_value() && bias->numel() == N && bias->scalar_type() == torch::kBFloat16 &&
+                bias->is_contiguous(), who, " bias");
+  }
+  if (hsd::epi_aux((int)epi)) {
+    TORCH_CHECK(aux.has_value() && aux->dim() == 2 && aux->size(0) == M && aux->size(1) == N &&
+                aux->stride(1) == 1 && aux->stride(0) % 8 == 0 && aux->scalar_type() == torch::kBFloat16, who, " aux");
+  }
+  if (hsd::epi_two_out((int)epi)) {
+    TORCH_CHECK(C2.has_value() && C2->sizes() == C.sizes() && C2->strides() == C.strides() &&
+                C2->scalar_type() == torch::kBFloat16, who, " C2");
+  }
+  GemmEpiOut out;
+  if (dbias.has_value()) {
+    TORCH_CHECK(hsd::epi_fused_dbias((int)epi) && N % 256 == 0, who,
+                " fused dbias: DGELU / MUL epilogue with N % 256 == 0");
+    check_f32(*dbias, "dbias");
+    TORCH_CHECK(dbias->numel() == N, "dbias size");
+    out.dbias = dbias->data_ptr<float>();
+  }
+  if (epi == hsd::E2_STORE_RDOT) {
+    // delta rows of the attention backward: [M / rd_seq][N / 64][rd_seq] fp32
+    TORCH_CHECK(rd.has_value() && rd_seq > 0 && M % rd_seq == 0, who, " row dots: rd and the sequence length");
+    check_f32(*rd, "rd");
+    TORCH_CHECK(rd->numel() == M * (N / 64), who, " row dots: rd size");
+    out.rd = rd->data_ptr<float>();
+  }
+  return out;
+}
+
+// A plan's fp32 workspace: the caller's (checked against the plan's size), or one from the current stream's pool
+static float* gemm_plan_workspace(const hsd::GemmPlan& pl, const c10::optional<torch::Tensor>& given,
+                                  torch::Tensor& owned, const torch::TensorOptions& like, const char* who) {
+  if (given.has_value()) {
+    TORCH_CHECK(given->is_cuda() && given->scalar_type() == torch::kFloat32 && given->is_contiguous() &&
+                given->numel() >= pl.ws_numel, who, ": slab workspace too small");
+    return given->data_ptr<float>();
+  }
+  if (pl.ws_numel == 0) return nullptr;
+  owned = torch::empty({pl.ws_numel}, like.dtype(torch::kFloat32));  // K-split slabs (stream-ordered pool)
+  return owned.data_ptr<float>();
+}
+
 // C = epilogue(sa·sb · A8 · B8ᵀ): A8 [M][K], B8 [N][K] uint8 (fp8 bits), same epilogue codes as gemm2 (bf16 out)
 // q8 (optional): uint8 [M][N] fp8 copy of the bf16 output (C2 for two-output epilogues, else C) in format q8fmt,
 // delayed scaling from q8_amax[0]; q8_sinv[0] = 1/scale; q8_track[0] accumulates the output's amax
@@ -484,42 +539,19 @@ void gemm8(torch::Tensor A, int64_t fa, torch::Tensor sa, torch::Tensor B, int64
   const int64_t M = A.size(0), K = A.size(1), N = B.size(0);
   TORCH_CHECK(B.size(1) == K, "gemm8 K mismatch");
   TORCH_CHECK(C.size(0) == M && C.size(1) == N && C.scalar_type() == torch::kBFloat16, "gemm8 C");
-  TORCH_CHECK(hsd::gemm8_supported((int)epi, (int)M, (int)N, (int)K), "gemm8: unsupported shape/epilogue");
-  TORCH_CHECK(A.stride(0) % 16 == 0 && B.stride(0) % 16 == 0 && C.stride(0) % 8 == 0, "gemm8 leading dims alignment");
   TORCH_CHECK(fa == 0 || fa == 1, "gemm8 fa");
   TORCH_CHECK(fb == 0, "gemm8: weights (B) are e4m3");
+  const GemmEpiOut eo = check_gemm_epilogue_args("gemm8", epi, M, N, C, bias, aux, C2, dbias, rd, rd_seq);
+  const hsd::GemmPlan pl = hsd::plan::plan_gemm8((int)epi, (int)M, (int)N, (int)K, (int)fa, dbias.has_value(),
+                                                 q8.has_value(), hsd::gemm_num_cus());
+  TORCH_CHECK(pl.supported(), "gemm8: unsupported shape/epilogue");
+  TORCH_CHECK(A.stride(0) % 16 == 0 && B.stride(0) % 16 == 0 && C.stride(0) % 8 == 0, "gemm8 leading dims alignment");
   check_f32(sa, "sa"); check_f32(sb, "sb");
-  if (epi == 1 || epi == 2 || epi == 3 || epi == 8) {
-    TORCH_CHECK(bias.has_value() && bias->numel() == N && bias->scalar_type() == torch::kBFloat16 &&
-                bias->is_contiguous(), "gemm8 bias");
-  }
-  if (epi == 3 || epi == 4 || epi == 5 || epi == 9 || epi == 10) {
-    TORCH_CHECK(aux.has_value() && aux->dim() == 2 && aux->size(0) == M && aux->size(1) == N &&
-                aux->stride(1) == 1 && aux->stride(0) % 8 == 0 && aux->scalar_type() == torch::kBFloat16, "gemm8 aux");
-  }
-  if (epi == 2 || epi == 8) {
-    TORCH_CHECK(C2.has_value() && C2->sizes() == C.sizes() && C2->strides() == C.strides() &&
-                C2->scalar_type() == torch::kBFloat16, "gemm8 C2");
-  }
-  float* dbp = nullptr;
-  if (dbias.has_value()) {
-    TORCH_CHECK((epi == 5 || epi == 9) && N % 256 == 0, "gemm8 fused dbias: DGELU / MUL epilogue with N % 256 == 0");
-    check_f32(*dbias, "dbias");
-    TORCH_CHECK(dbias->numel() == N, "dbias size");
-    dbp = dbias->data_ptr<float>();
-  }
-  float* rdp = nullptr;
-  if (epi == 10) {
-    TORCH_CHECK(rd.has_value() && rd_seq > 0 && M % rd_seq == 0, "gemm8 row dots: rd and the sequence length");
-    check_f32(*rd, "rd");
-    TORCH_CHECK(rd->numel() == M * (N / 64), "gemm8 row dots: rd size");
-    rdp = rd->data_ptr<float>();
-  }
   hsd::launch_gemm8((int)epi, A.data_ptr<uint8_t>(), A.stride(0), (int)fa, sa.data_ptr<float>(), B.data_ptr<uint8_t>(),
                     B.stride(0), (int)fb, sb.data_ptr<float>(), (int)M, (int)N, (int)K, BF(C), C.stride(0),
                     bias.has_value() ? CBF(*bias) : nullptr, aux.has_value() ? CBF(*aux) : nullptr,
-                    aux.has_value() ? aux->stride(0) : 0, C2.has_value() ? BF(*C2) : nullptr, p, (uint64_t)seed, dbp,
-                    cur_stream(), q8p, q8a, q8s, q8t, (int)q8fmt, rdp, (int)rd_seq, q8_only ? 1 : 0);
+                    aux.has_value() ? aux->stride(0) : 0, C2.has_value() ? BF(*C2) : nullptr, p, (uint64_t)seed,
+                    eo.dbias, cur_stream(), q8p, q8a, q8s, q8t, (int)q8fmt, eo.rd, (int)rd_seq, q8_only ? 1 : 0, &pl);
 }
 
 // C[M][N] fp32 += sdy·sx · dY8ᵀ · X8 (fp8 TT weight gradient): dY8 uint8 [T][M] (format fdy), X8 uint8 [T][N] (e4m3),
@@ -533,12 +565,13 @@ void gemm8_wgrad(int64_t stream_ptr, torch::Tensor dy, int64_t fdy, torch::Tenso
   const int64_t T = dy.size(0), M = dy.size(1), N = x.size(1);
   TORCH_CHECK(x.size(0) == T, "gemm8_wgrad: token count mismatch");
   TORCH_CHECK(C.size(0) == M && C.size(1) == N && C.scalar_type() == torch::kFloat32, "gemm8_wgrad: C fp32 [M][N]");
-  TORCH_CHECK(hsd::gemm8_wgrad_supported((int)M, (int)N, (int)T), "gemm8_wgrad: unsupported shape");
-  TORCH_CHECK(dy.stride(0) % 16 == 0 && x.stride(0) % 16 == 0 && C.stride(0) % 4 == 0, "gemm8_wgrad: leading dims");
   TORCH_CHECK(fdy == 0 || fdy == 1, "gemm8_wgrad: fdy");
+  const hsd::GemmPlan pl = hsd::plan::plan_gemm8_wgrad((int)M, (int)N, (int)T, (int)splits, (int)fdy);
+  TORCH_CHECK(pl.supported(), "gemm8_wgrad: unsupported shape");
+  TORCH_CHECK(dy.stride(0) % 16 == 0 && x.stride(0) % 16 == 0 && C.stride(0) % 4 == 0, "gemm8_wgrad: leading dims");
   TORCH_CHECK(fx == 0, "gemm8_wgrad: activations (X8) are e4m3");
   check_f32(sdy, "sdy"); check_f32(sx, "sx"); check_f32(ws, "ws");
-  TORCH_CHECK(ws.numel() >= hsd::gemm8_wgrad_ws_numel((int)M, (int)N, (int)T, (int)splits), "gemm8_wgrad: workspace");
+  TORCH_CHECK(ws.numel() >= pl.ws_numel, "gemm8_wgrad: workspace");
   hipStream_t st = stream_ptr ? reinterpret_cast<hipStream_t>(stream_ptr) : cur_stream();
   hsd::launch_gemm8_wgrad(dy.data_ptr<uint8_t>(), dy.stride(0), (int)fdy, sdy.data_ptr<float>(), x.data_ptr<uint8_t>(),
                           x.stride(0), (int)fx, sx.data_ptr<float>(), (int)M, (int)N, (int)T, C.data_ptr<float>(),
@@ -571,60 +604,24 @@ void gemm2(torch::Tensor A, torch::Tensor B, torch::Tensor C, int64_t la, int64_
   const int64_t KB = lb == 0 ? B.size(1) : B.size(0);
   TORCH_CHECK(K == KB, "gemm2 K mismatch");
   TORCH_CHECK(C.size(0) == M && C.size(1) == N, "gemm2 C shape");
-  TORCH_CHECK(hsd::gemm2_supported((int)la, (int)lb, (int)epi, (int)M, (int)N, (int)K), "gemm2: unsupported shape/epilogue");
+  const bool f32out = epi == hsd::E2_F32_ATOMIC || epi == hsd::E2_F32_SLAB;
+  TORCH_CHECK(f32out || la == 0 || splits <= 1, "gemm2: split-K bf16 output is NT only");
+  const GemmEpiOut eo = check_gemm_epilogue_args("gemm2", epi, M, N, C, bias, aux, C2, dbias, rd, rd_seq);
+  // splits <= 0 = automatic; NT bf16 output: 1 = one pass, > 1 = split-K slabs + epilogue pass
+  const hsd::GemmPlan pl = hsd::plan::plan_gemm2((int)la, (int)lb, (int)epi, (int)M, (int)N, (int)K, (int)splits,
+                                                 dbias.has_value(), hsd::gemm_num_cus(), C.stride(0) % 4 == 0);
+  TORCH_CHECK(pl.supported(), "gemm2: unsupported shape/epilogue");
   TORCH_CHECK(A.stride(0) % 8 == 0 && B.stride(0) % 8 == 0 && C.stride(0) % 8 == 0, "gemm2 leading dims alignment");
-  const bool f32out = epi == 6 || epi == 7;
   TORCH_CHECK(C.scalar_type() == (f32out ? torch::kFloat32 : torch::kBFloat16), "gemm2 C dtype");
-  if (epi == 1 || epi == 2 || epi == 3 || epi == 8) {
-    TORCH_CHECK(bias.has_value() && bias->numel() == N && bias->scalar_type() == torch::kBFloat16 &&
-                bias->is_contiguous(), "gemm2 bias");
-  }
-  if (epi == 3 || epi == 4 || epi == 5 || epi == 9 || epi == 10) {
-    TORCH_CHECK(aux.has_value() && aux->dim() == 2 && aux->size(0) == M && aux->size(1) == N &&
-                aux->stride(1) == 1 && aux->stride(0) % 8 == 0 && aux->scalar_type() == torch::kBFloat16, "gemm2 aux");
-  }
-  if (epi == 2 || epi == 8) {
-    TORCH_CHECK(C2.has_value() && C2->sizes() == C.sizes() && C2->strides() == C.strides() &&
-                C2->scalar_type() == torch::kBFloat16, "gemm2 C2");
-  }
-  float* wsp = nullptr;
-  int sp = (int)splits;
-  if (f32out && sp <= 0) sp = hsd::gemm2_wgrad_splits((int)M, (int)N, (int)K);
-  if (epi == 7) {
-    TORCH_CHECK(C.is_contiguous() || C.stride(0) % 4 == 0, "gemm2 slab C");
-    TORCH_CHECK(ws.has_value() && ws->scalar_type() == torch::kFloat32 && ws->is_contiguous() &&
-                ws->numel() >= (int64_t)sp * M * N, "gemm2 slab workspace too small");
-    wsp = ws->data_ptr<float>();
-  }
+  // TT slabs: the caller's workspace (the side stream's); NT split-K: one from the current stream's pool
+  TORCH_CHECK(la == 0 || pl.ws_numel == 0 || ws.has_value(), "gemm2 slab workspace missing");
   torch::Tensor nt_ws;
-  if (!f32out) {
-    // NT bf16 output: splits <= 0 = automatic (gemm2_nt_splits), 1 = one pass, > 1 = split-K slabs + epilogue pass
-    if (sp <= 0) sp = la == 0 ? hsd::gemm2_nt_splits((int)M, (int)N, (int)K) : 1;
-    TORCH_CHECK(la == 0 || sp == 1, "gemm2: split-K bf16 output is NT only");
-    if (sp > 1) {
-      nt_ws = torch::empty({(int64_t)sp * M * N}, A.options().dtype(torch::kFloat32));
-      wsp = nt_ws.data_ptr<float>();
-    }
-  }
-  float* dbp = nullptr;
-  if (dbias.has_value()) {
-    TORCH_CHECK((epi == 5 || epi == 9) && N % 256 == 0, "gemm2 fused dbias: DGELU / MUL epilogue with N % 256 == 0");
-    check_f32(*dbias, "dbias");
-    TORCH_CHECK(dbias->numel() == N, "dbias size");
-    dbp = dbias->data_ptr<float>();
-  }
-  float* rdp = nullptr;
-  if (epi == 10) {
-    // delta rows of the attention backward: [M / rd_seq][N / 64][rd_seq] fp32
-    TORCH_CHECK(rd.has_value() && rd_seq > 0 && M % rd_seq == 0, "gemm2 row dots: rd and the sequence length");
-    check_f32(*rd, "rd");
-    TORCH_CHECK(rd->numel() == M * (N / 64), "gemm2 row dots: rd size");
-    rdp = rd->data_ptr<float>();
-  }
+  float* wsp = gemm_plan_workspace(pl, la == 1 ? ws : c10::nullopt, nt_ws, A.options(), "gemm2");
   hsd::launch_gemm2((int)la, (int)lb, (int)epi, CBF(A), A.stride(0), CBF(B), B.stride(0), (int)M, (int)N, (int)K,
                     C.data_ptr(), C.stride(0), bias.has_value() ? CBF(*bias) : nullptr,
                     aux.has_value() ? CBF(*aux) : nullptr, aux.has_value() ? aux->stride(0) : 0,
-                    C2.has_value() ? BF(*C2) : nullptr, p, (uint64_t)seed, sp, wsp, dbp, cur_stream(), rdp, (int)rd_seq);
+                    C2.has_value() ? BF(*C2) : nullptr, p, (uint64_t)seed, (int)splits, wsp, eo.dbias, cur_stream(),
+                    eo.rd, (int)rd_seq, &pl);
 }
 
 // ---- fp32 step (fp32.hip, ops/hip32.py) ---------------------------------------------------------------------------
@@ -635,14 +632,15 @@ void gemm2_f32nt(torch::Tensor A, torch::Tensor B, torch::Tensor C, int64_t lb) 
   const int64_t M = A.size(0), K = A.size(1);
   const int64_t N = lb == 0 ? B.size(0) : B.size(1), KB = lb == 0 ? B.size(1) : B.size(0);
   TORCH_CHECK(K == KB && C.size(0) == M && C.size(1) == N, "gemm2_f32nt shapes");
-  TORCH_CHECK(hsd::gemm2_supported(0, (int)lb, 7, (int)M, (int)N, (int)K), "gemm2_f32nt: unsupported shape");
+  const hsd::GemmPlan pl = hsd::plan::plan_gemm2(0, (int)lb, hsd::E2_F32_SLAB, (int)M, (int)N, (int)K, 0, false,
+                                                 hsd::gemm_num_cus());
+  TORCH_CHECK(pl.supported(), "gemm2_f32nt: unsupported shape");
   TORCH_CHECK(C.is_contiguous(), "gemm2_f32nt: contiguous C");
-  const int sp = hsd::gemm2_f32nt_splits((int)M, (int)N, (int)K);
   torch::Tensor ws;
-  if (sp > 1) ws = torch::empty({(int64_t)sp * M * N}, C.options());  // K-split slabs (stream-ordered pool)
-  hsd::launch_gemm2(0, (int)lb, 7, CBF(A), A.stride(0), CBF(B), B.stride(0), (int)M, (int)N, (int)K, C.data_ptr(),
-                    C.stride(0), nullptr, nullptr, 0, nullptr, 0.0, 0, sp, sp > 1 ? ws.data_ptr<float>() : nullptr,
-                    nullptr, cur_stream());
+  float* wsp = gemm_plan_workspace(pl, c10::nullopt, ws, C.options(), "gemm2_f32nt");
+  hsd::launch_gemm2(0, (int)lb, hsd::E2_F32_SLAB, CBF(A), A.stride(0), CBF(B), B.stride(0), (int)M, (int)N, (int)K,
+                    C.data_ptr(), C.stride(0), nullptr, nullptr, 0, nullptr, 0.0, 0, 0, wsp, nullptr, cur_stream(),
+                    nullptr, 0, &pl);
 }
 
 // Segmented-K split-product GEMM (gemm2.hip launch_gemm2_seg): C = Σ_s A[s] · B[s] over three K segments of the bf16
@@ -667,14 +665,14 @@ void gemm2_seg(std::vector<torch::Tensor> A, std::vector<torch::Tensor> B, torch
   TORCH_CHECK(Kseg == KB && C.size(0) == M && C.size(1) == N, "gemm2_seg shapes");
   TORCH_CHECK(hsd::gemm2_seg_supported((int)la, (int)lb, (int)M, (int)N, (int)Kseg), "gemm2_seg: unsupported shape");
   TORCH_CHECK(A[0].stride(0) % 8 == 0 && B[0].stride(0) % 8 == 0, "gemm2_seg leading dims alignment");
-  const int64_t wsn = hsd::gemm2_seg_ws_numel((int)la, (int)lb, (int)M, (int)N, (int)Kseg);
   torch::Tensor ws;
-  if (wsn > 0) ws = torch::empty({wsn}, C.options());  // K-split slabs (stream-ordered pool)
+  float* wsp = gemm_plan_workspace(hsd::plan::plan_gemm2_seg((int)la, (int)lb, (int)M, (int)N, (int)Kseg, accumulate,
+                                                             hsd::gemm_num_cus()),
+                                   c10::nullopt, ws, C.options(), "gemm2_seg");
   const hsd::bf16_t* a[3] = {CBF(A[0]), CBF(A[1]), CBF(A[2])};
   const hsd::bf16_t* b[3] = {CBF(B[0]), CBF(B[1]), CBF(B[2])};
   hsd::launch_gemm2_seg((int)la, (int)lb, a, A[0].stride(0), b, B[0].stride(0), (int)M, (int)N, (int)Kseg,
-                        C.data_ptr<float>(), C.stride(0), wsn > 0 ? ws.data_ptr<float>() : nullptr, cur_stream(),
-                        accumulate);
+                        C.data_ptr<float>(), C.stride(0), wsp, cur_stream(), accumulate);
 }
 
 bool gemm2_seg_supported(int64_t la, int64_t lb, int64_t M, int64_t N, int64_t Kseg) {
@@ -1000,6 +998,45 @@ void gemm2_set_diag(c10::optional<at::Tensor> buf) {
   hsd::gemm2_set_diag(buf.has_value() ? buf->data_ptr() : nullptr);
 }
 
+// The launch plan of a GEMM entry point as plain data (no device is touched; `cus` stands for the CU count):
+// entry "gemm2" (K = the contraction; TT: tokens), "gemm2_seg" (K = Kseg; `accumulate`), "gemm8" (`fa`, `q8`),
+// "gemm8_wgrad" (K = tokens; `fa` = the gradient's format). launches: the kernels the launcher enqueues, in order.
+py::dict gemm_plan(const std::string& entry, int64_t la, int64_t lb, int64_t epi, int64_t M, int64_t N, int64_t K,
+                   int64_t splits, bool dbias, bool accumulate, bool q8, int64_t fa, int64_t cus) {
+  namespace P = hsd::plan;
+  hsd::GemmPlan pl;
+  if (entry == "gemm2") pl = P::plan_gemm2((int)la, (int)lb, (int)epi, (int)M, (int)N, (int)K, (int)splits, dbias, (int)cus);
+  else if (entry == "gemm2_seg") pl = P::plan_gemm2_seg((int)la, (int)lb, (int)M, (int)N, (int)K, accumulate, (int)cus);
+  else if (entry == "gemm8") pl = P::plan_gemm8((int)epi, (int)M, (int)N, (int)K, (int)fa, dbias, q8, (int)cus);
+  else if (entry == "gemm8_wgrad") pl = P::plan_gemm8_wgrad((int)M, (int)N, (int)K, (int)splits, (int)fa);
+  else TORCH_CHECK(false, "gemm_plan: entry is gemm2, gemm2_seg, gemm8 or gemm8_wgrad");
+  py::list launches;
+  for (const P::PlannedLaunch& l : P::plan_launches(pl)) {
+    py::dict d;
+    d["kernel"] = l.kernel;
+    d["targs"] = l.targs;
+    d["grid"] = l.grid;
+    d["wg"] = l.wg;
+    launches.append(d);
+  }
+  py::dict out;
+  out["supported"] = pl.supported();
+  out["launches"] = launches;
+  out["ws_numel"] = pl.ws_numel;
+  out["splits"] = pl.splits;
+  out["kps"] = pl.kps;
+  out["landing"] = pl.landing;
+  return out;
+}
+
+// a TT weight gradient dW[N][K] over T tokens: (supported, K-splits to request, fp32 workspace elements)
+std::tuple<bool, int64_t, int64_t> gemm2_wgrad_plan(int64_t N, int64_t K, int64_t T) {
+  const int sp = hsd::gemm2_wgrad_splits((int)N, (int)K, (int)T);
+  const hsd::GemmPlan pl = hsd::plan::plan_gemm2(1, 1, hsd::E2_F32_SLAB, (int)N, (int)K, (int)T, sp, false,
+                                                 hsd::gemm_num_cus());
+  return {pl.supported(), sp, pl.ws_numel};
+}
+
 bool gemm2_supported(int64_t la, int64_t lb, int64_t epi, int64_t M, int64_t N, int64_t K) {
   return hsd::gemm2_supported((int)la, (int)lb, (int)epi, (int)M, (int)N, (int)K);
 }
@@ -1112,6 +1149,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return hsd::gemm8_wgrad_ws_numel((int)M, (int)N, (int)T, (int)splits);
   });
   m.def("gemm2_nt_splits", &gemm2_nt_splits);
+  m.def("gemm_plan", &gemm_plan, py::arg("entry"), py::arg("la"), py::arg("lb"), py::arg("epi"), py::arg("M"),
+        py::arg("N"), py::arg("K"), py::arg("splits") = 0, py::arg("dbias") = false, py::arg("accumulate") = false,
+        py::arg("q8") = false, py::arg("fa") = 0, py::arg("cus") = 256);
+  m.def("gemm2_wgrad_plan", &gemm2_wgrad_plan);
   m.def("gemm2_supported", &gemm2_supported);
   m.def("gemm2_set_diag", &gemm2_set_diag);
   m.def("attn128_set_diag", &attn128_set_diag);

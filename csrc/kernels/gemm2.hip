@@ -35,7 +35,7 @@
 #endif
 #include <stdlib.h>
 
-#include <cmath>
+#include <type_traits>
 
 namespace hsd {
 
@@ -1253,50 +1253,9 @@ __global__ __launch_bounds__(256 * KW, (NSTG <= 2 && KW == 1) ? 2 : 1) void gemm
 
 }  // namespace g2
 
-// Main-loop schedule (interleaved rounds in one process, random operands, T = 131072 tokens): the staggered 4-phase
-// form (SYNC 4) is the fastest on both layouts. NT (forward / dgrad): +5-10 % over one-barrier-per-K-tile SYNC 1 on
-// every BERT shape (tools/gemm_probe.py, profiles/gemm_probe_r1_sync.json). TT (weight gradients), once its LDS-DMA
-// stopped draining every K-tile (dma_lds_asm): 1,018-1,134 TFLOP/s vs 920-1,065 for SYNC 7 and 979-1,074 for SYNC 0
-// on the four bert-base weights (tools/tt_probe.py, profiles/tt_probe_r3_sync_splits.json). HSD_G2_SYNC overrides
-// for A/B runs; the bf16 epilogue stores are non-temporal (st16nt).
-static int g2_sync_mode(int la, int K) {
-  const int e = HSD_KNOB("HSD_G2_SYNC", kKnobUnset);
-  (void)la;
-  return e != kKnobUnset ? e : 4;
-}
 
-template <int LA, int LB, int EPI, int BN, bool SEG = false>
-static void g2_launch(const G2Params& p0, int splits, hipStream_t st) {
-  G2Params p = p0;
-  const int tiles_m = (p.M + g2::BM - 1) / g2::BM;
-  p.tiles_n = (p.N + BN - 1) / BN;
-  if (splits < 1) splits = 1;
-  int kps = (p.K + splits - 1) / splits;
-  kps = (kps + g2::BK - 1) / g2::BK * g2::BK;
-  splits = (p.K + kps - 1) / kps;
-  p.kps = kps;
-  p.ntiles = tiles_m * p.tiles_n;
-  dim3 grid(p.ntiles * splits);
-  if constexpr (SEG) {
-    hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 4, true>), grid, dim3(512), 0, st, p);
-    HSD_CHECK_LAUNCH();
-    return;
-  }
-  const int mode = g2_sync_mode(LA, p.K);
-  if (mode == 1) hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 1>), grid, dim3(512), 0, st, p);
-  else if (mode == 2) hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 2>), grid, dim3(512), 0, st, p);
-  else if (mode == 4) hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 4>), grid, dim3(512), 0, st, p);
-  else if (mode == 5) hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 5>), grid, dim3(512), 0, st, p);
-  else if (mode == 6) hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 6>), grid, dim3(512), 0, st, p);
-  else if (mode == 7) hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 7>), grid, dim3(512), 0, st, p);
-  else hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 0>), grid, dim3(512), 0, st, p);
-  HSD_CHECK_LAUNCH();
-}
-
-// Persistent NT kernel (gemm2pk_kernel): for grids of more than one round of workgroups (a one-round grid has no tile
-// seam to hide). Measured on the bert-base B=1024 NT GEMMs (tools/env_ab_gemm.py, profiles/persist_ab_r3.log): 1-6 %
-// faster on every one, bit-identical outputs; the headline step 80.8 -> 79.3 ms. HSD_G2_PERSIST=0 turns it off.
-static int g2_num_cus() {
+// ---- host side: the launchers execute a GemmPlan (gemm_plan.h holds the policy and its measurements) ------------------
+int gemm_num_cus() {
   static int n = 0;
   if (n == 0) {
     int dev = 0;
@@ -1332,378 +1291,196 @@ static int* g2_tq_slot(hipStream_t st) {
   return base[dev] + (size_t)(next++ % kSlots) * kTqInts;
 }
 
-static bool g2_persist(int tiles) {
-  if (!HSD_KNOB("HSD_G2_PERSIST", 1)) return false;
-  return tiles > (g2_num_cus() & ~7);
-}
-
-template <int EPI, int BN>
-static void g2pk_launch(const G2Params& p0, hipStream_t st) {
-  G2Params p = p0;
-  const int tiles_m = (p.M + g2::BM - 1) / g2::BM;
-  p.tiles_n = (p.N + BN - 1) / BN;
-  p.ntiles = tiles_m * p.tiles_n;
-  p.kps = p.K;
-  if (p.K % g2::BK) abort();
-  const int grid = std::min(p.ntiles, g2_num_cus() & ~7);
-  p.tq = g2_tq_slot(st);
-  hipLaunchKernelGGL((g2::gemm2pk_kernel<EPI, BN>), dim3(grid), dim3(512), 0, st, p);
-  HSD_CHECK_LAUNCH();
-}
-
-template <int EPI, int BN, int FA>
-static void g8pk_launch(const G2Params& p0, const float* sa, const float* sb, hipStream_t st) {
-  G2Params p = p0;
-  const int tiles_m = (p.M + g2::BM - 1) / g2::BM;
-  p.tiles_n = (p.N + BN - 1) / BN;
-  p.ntiles = tiles_m * p.tiles_n;
-  p.kps = p.K;
-  const int grid = p.ntiles > (g2_num_cus() & ~7) ? (g2_num_cus() & ~7) : p.ntiles;
-  p.tq = g2_tq_slot(st);
-  if (p.q8 != nullptr) {
-    // fp8 output copies: the FFN epilogues whose outputs feed the next fp8 GEMM (GELU -> FFN2 forward, GELU'
-    // product -> FFN1 dgrad)
-    if constexpr (EPI == E2_BIAS_GELU_D || EPI == E2_BIAS_GELU || EPI == E2_MUL || EPI == E2_DGELU)
-      hipLaunchKernelGGL((g2::gemm8pk_kernel<EPI, BN, FA, 0, true>), dim3(grid), dim3(512), 0, st, p, sa, sb);
-    else
-      abort();
-  } else {
-    hipLaunchKernelGGL((g2::gemm8pk_kernel<EPI, BN, FA, 0>), dim3(grid), dim3(512), 0, st, p, sa, sb);
-  }
-  HSD_CHECK_LAUNCH();
-}
-
-// fp8 NT GEMM on the persistent kernel (gemm8.hip's launch_gemm8 routes here): A8 [M][K], B8 [N][K] bytes, K % 128 == 0,
-// even leading dimensions; fa: A format (0 e4m3, 1 e5m2), B e4m3.
-void launch_gemm8pk(int epi, int bn, const G2Params& p0, int fa, const float* sa, const float* sb, hipStream_t st) {
-  G2Params p = p0;
-  p.nt_store = 1;  // non-temporal epilogue stores (profiles/store_policy_r3.log)
-  p.K /= 2;
-  p.lda /= 2;
-  p.ldb /= 2;
-#define G8PK(E)                                                                   \
-  case E:                                                                         \
-    if (bn == 256) {                                                              \
-      if (fa == 0) g8pk_launch<E, 256, 0>(p, sa, sb, st);                         \
-      else g8pk_launch<E, 256, 1>(p, sa, sb, st);                                 \
-    } else {                                                                      \
-      if (fa == 0) g8pk_launch<E, 192, 0>(p, sa, sb, st);                         \
-      else g8pk_launch<E, 192, 1>(p, sa, sb, st);                                 \
-    }                                                                             \
-    return;
+// f(std::integral_constant<int, E>) for the bf16-output epilogue `epi`
+template <class F>
+static void for_bf16_epi(int epi, F&& f) {
   switch (epi) {
-    G8PK(E2_STORE)
-    G8PK(E2_BIAS)
-    G8PK(E2_BIAS_GELU)
-    G8PK(E2_BIAS_DROP_RES)
-    G8PK(E2_RES)
-    G8PK(E2_DGELU)
-    G8PK(E2_BIAS_GELU_D)
-    G8PK(E2_MUL)
-    case E2_STORE_RDOT:  // 64-column wave tiles (one head per 8-lane group): BN 256
-      if (fa == 0) g8pk_launch<E2_STORE_RDOT, 256, 0>(p, sa, sb, st);
-      else g8pk_launch<E2_STORE_RDOT, 256, 1>(p, sa, sb, st);
-      return;
+#define HSD_EPI_CASE(E) \
+  case E:               \
+    f(std::integral_constant<int, E>{}); \
+    return;
+    HSD_BF16_EPIS(HSD_EPI_CASE)
+#undef HSD_EPI_CASE
     default: abort();
   }
-#undef G8PK
 }
 
-// Tile width for a bf16-output NT GEMM: minimise (rounds of 256 CUs) x (per-tile cost ∝ BN + c).
-int gemm2_pick_bn(int M, int N) {
-  const int tm = (M + 255) / 256;
-  int best = 0;
-  double best_cost = 1e30;
-  for (int bn : {256, 192}) {
-    if (N % bn) continue;
-    const int blocks = tm * (N / bn);
-    const int rounds = (blocks + 255) / 256;
-    const double cost = rounds * (bn + 64.0);
-    if (cost < best_cost) { best_cost = cost; best = bn; }
+template <int LA, int LB, int EPI, int BN, bool SEG = false>
+static void g2_launch(const G2Params& p, const GemmPlan& pl, hipStream_t st) {
+  const dim3 grid(pl.grid), wg(pl.wg);
+  if constexpr (SEG) {
+    hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 4, true>), grid, wg, 0, st, p);
+    return;
   }
-  return best;
-}
-
-// K-splits for a bf16-output NT GEMM. A 256 x 256 tile grid that leaves more than half of the 256 CUs idle
-// (the reference's own per-rank batch: bert-large, B = 8, S = 512 -> M = 4096: 64 tiles on the H-wide GEMMs)
-// is split over K into fp32 slabs plus one reduce-and-epilogue pass, keeping >= 8 K-tiles per split.
-// HSD_G2_SPLITK=0 disables, =n forces n.
-constexpr int SBN_HOST = 128;
-bool gemm2s_use(int M, int N, int K);
-
-int gemm2_nt_splits(int M, int N, int K) {
-  const int e = HSD_KNOB("HSD_G2_SPLITK", kKnobUnset);
-  const int kt = K / 64;
-  if (e != kKnobUnset) return std::max(1, std::min(e, kt));
-  if (gemm2s_use(M, N, K)) {
-    // 128 x 128 tiles: split only grids that leave more than half of the CUs idle (serving batches: B = 1 has 6-24
-    // tiles, each a latency-bound chain of 12-48 K-steps), >= 2 K-tiles per split
-    const int tiles = ((M + 127) / 128) * (N / 128);
-    if (tiles * 2 > 256) return 1;
-    int s = 256 / tiles;
-    while (s > 1 && kt / s < 2) --s;
-    return s;
+  switch (pl.sync) {
+    case 1: hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 1>), grid, wg, 0, st, p); break;
+    case 2: hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 2>), grid, wg, 0, st, p); break;
+    case 4: hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 4>), grid, wg, 0, st, p); break;
+    case 5: hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 5>), grid, wg, 0, st, p); break;
+    case 6: hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 6>), grid, wg, 0, st, p); break;
+    case 7: hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 7>), grid, wg, 0, st, p); break;
+    default: hipLaunchKernelGGL((g2::gemm2_kernel<LA, LB, EPI, BN, 0>), grid, wg, 0, st, p); break;
   }
-  const int tiles = ((M + 255) / 256) * ((N + 255) / 256);
-  if (tiles * 2 > 256) return 1;
-  int s = 256 / tiles;
-  while (s > 1 && kt / s < 8) --s;
-  return s;
-}
-
-// gemm2s (128 x 128 tiles) for NT grids that 256 x 256 tiles leave mostly idle. HSD_G2_SMALL=0 disables,
-// =1 forces it for every shape it supports.
-bool gemm2s_use(int M, int N, int K) {
-  if (N % SBN_HOST != 0 || K % 64 != 0) return false;
-  const int e = HSD_KNOB("HSD_G2_SMALL", kKnobUnset);
-  if (e != kKnobUnset) return e != 0;
-  // long K (>= 16,384: the MLM head's dgrad over the ~50k-word table): the 256 x 256 kernel with K-splits filling the
-  // CUs beats 128 x 128 tiles at one split -- 4,928 x 1,024 x 50,432: 446 us at 3 splits vs 770 us
-  // (tools/mlm_dgrad_probe.py, profiles/mlm_dgrad_probe_r4.jsonl)
-  if (K >= 16384) return false;
-  const int tiles = ((M + 255) / 256) * ((N + 255) / 256);
-  return tiles * 2 <= 256;
-}
-
-// Weight-gradient plan: 256 x 256 tiles (gemm2, split-K slabs) or 128 x 128 tiles (gemm2s TT), and the K-split
-// count, by a cost model fitted to tools/wgrad_ab.py on MI355X (24 BERT shapes x T = 4096 / 8192 / 16384; it
-// picks the faster path on all 24, profiles/wgrad_ab_r2.json): us = rounds x (a·K-tiles per split + b) + c·MB of
-// slab / C traffic, rounds = ceil(workgroups / 256) (one workgroup per CU on both). HSD_G2_SMALL_TT=0 / 1 forces
-// the tile size (the split count is still chosen by the model); >= 2 K-tiles per split.
-struct WgradPlan {
-  bool small;
-  int splits;
-};
-
-static double wgrad_cost(int M, int N, int K, int s, bool small) {
-  const int tile = small ? 128 : 256;
-  const double tiles = (double)((M + tile - 1) / tile) * ((N + tile - 1) / tile);
-  const int kt_all = K / 64;
-  const int kt = (kt_all + s - 1) / s;
-  const int real = (kt_all + kt - 1) / kt;
-  const double rounds = std::ceil(tiles * real / 256.0);
-  const double mb = ((real > 1 ? 8.0 * real : 0.0) + 8.0) * M * N / 1e6;
-  return small ? rounds * (0.658 * kt + 5.02) + 0.176 * mb : rounds * (1.637 * kt + 15.9) + 0.0847 * mb;
-}
-
-static WgradPlan wgrad_plan(int M, int N, int K) {
-  const int force = HSD_KNOB("HSD_G2_SMALL_TT", -1);
-  const bool can_small = N % SBN_HOST == 0 && M % 8 == 0 && K % 64 == 0 && force != 0;
-  const bool can_big = N % 256 == 0 && force != 1;
-  // small steps (<= 8,192 tokens), whose weight gradients run on the side stream under the backward: the fewest K-splits
-  // of the 128 x 128 kernel that still give 384 workgroups, so a weight gradient takes no more CUs and slab traffic
-  // than it needs beside the critical path (the latency cost model below minimises its own time instead). Measured
-  // (profiles/wgrad_min_grid_ab_r4.log): bert-large S=512 B=8 504-505 -> 524-526 seq/s, bert-base B=64 +1.8 % at a
-  // 192-workgroup target; re-swept in round 6 with the optimizer slices behind the weight-gradient forks
-  // (profiles/r6/bl8_knob_sweep_r6.log, profiles/r6/wgrad_min_grid_small_steps_r6.log): 384 is +1.2-1.4 % at
-  // bert-large B = 8 (552.6-554.2 vs 546.4-547.7) and ahead at bert-base B = 32 too; 256, 512 and 768 are 2 % slower.
-  // Both are 4,096-token steps: below that (the graph-replayed small batches) the measured 192 stays.
-  // HSD_WGRAD_MIN_GRID sets the workgroup target (0 = the cost model at every size).
-  const int grid_knob = HSD_KNOB("HSD_WGRAD_MIN_GRID", kKnobUnset);
-  const int min_grid = grid_knob != kKnobUnset ? grid_knob : (K <= 8192 ? (K >= 4096 ? 384 : 192) : 0);
-  if (min_grid > 0 && can_small) {
-    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    int sp = 1;
-    while (tiles * sp < min_grid && sp < 32 && (K / 64) / (sp + 1) >= 2) ++sp;
-    return WgradPlan{true, sp};
-  }
-  const int min_kt = 2;
-  const int kt_all = K / 64;
-  WgradPlan best{can_small && !can_big, 1};
-  double best_cost = 1e30;
-  for (int small = 0; small < 2; ++small) {
-    if (small ? !can_small : !can_big) continue;
-    for (int sp = 1; sp <= 32 && (sp == 1 || kt_all / sp >= min_kt); ++sp) {
-      const double c = wgrad_cost(M, N, K, sp, small);
-      if (c < best_cost) { best_cost = c; best = WgradPlan{small != 0, sp}; }
-    }
-  }
-  return best;
-}
-
-bool gemm2st_use(int M, int N, int K) { return wgrad_plan(M, N, K).small; }
-
-// LDS stages of gemm2s: 2 -> two workgroups per CU, 3 -> one with a deeper DMA prefetch. A grid that fits one
-// workgroup per CU takes 3 stages, a larger one 2 (tools/nt_ab.py, profiles/nt_ab_r2.jsonl: at T = 8192 the 384-tile
-// bert-base GEMMs run 19-49 us at 2 stages vs 26-68 us at 3; at <= 256 tiles 3 stages are equal or up to 5 % faster).
-// HSD_G2S_STAGES (2-4) overrides.
-static int g2s_stages(int grid) {
-  const int e = HSD_KNOB("HSD_G2S_STAGES", kKnobUnset);
-  const int v = e != kKnobUnset ? e : (grid <= 256 ? 3 : 2);
-  return v < 2 ? 2 : (v > 4 ? 4 : v);
-}
-
-// gemm2s workgroup for grids of one workgroup per CU (3 stages): 8 waves with the in-workgroup K-split (2 waves per
-// SIMD, default) or 4 (one per SIMD). Measured end to end (profiles/g2s_kw2_ab_r4.log, interleaved x2): bert-large
-// S = 512 B = 8 488 -> 500-502 seq/s, bert-base B = 32 5,581-5,666 -> 5,723-5,734. HSD_G2S_KW = 1 / 2 overrides.
-static int g2s_kw(int grid) {
-  const int e = HSD_KNOB("HSD_G2S_KW", kKnobUnset);
-  if (e != kKnobUnset) return e == 2 ? 2 : 1;
-  (void)grid;
-  return 2;
 }
 
 template <int LA, int LB, int EPI, bool SEG = false>
-static void g2s_launch(const G2Params& q, int grid, hipStream_t st) {
-  const int ns = g2s_stages(grid);
+static void g2s_launch(const G2Params& p, const GemmPlan& pl, hipStream_t st) {
+  const dim3 grid(pl.grid), wg(pl.wg);
   if constexpr (SEG) {
-    if (ns == 2) hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 2, 1, true>), dim3(grid), dim3(256), 0, st, q);
-    else hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 3, 2, true>), dim3(grid), dim3(512), 0, st, q);
-    HSD_CHECK_LAUNCH();
+    if (pl.nstg == 2) hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 2, 1, true>), grid, wg, 0, st, p);
+    else hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 3, 2, true>), grid, wg, 0, st, p);
     return;
   }
-  if (ns == 2) hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 2>), dim3(grid), dim3(256), 0, st, q);
-  else if (ns == 3 && g2s_kw(grid) == 2)
-    hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 3, 2>), dim3(grid), dim3(512), 0, st, q);
-  else if (ns == 3) hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 3>), dim3(grid), dim3(256), 0, st, q);
-  else hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 4>), dim3(grid), dim3(256), 0, st, q);
+  if (pl.nstg == 2) hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 2>), grid, wg, 0, st, p);
+  else if (pl.nstg == 3 && pl.kw == 2) hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 3, 2>), grid, wg, 0, st, p);
+  else if (pl.nstg == 3) hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 3>), grid, wg, 0, st, p);
+  else hipLaunchKernelGGL((g2::gemm2s_kernel<LA, LB, EPI, 4>), grid, wg, 0, st, p);
+}
+
+// the fp32-output kernels of a family F<LA, LB, SEG>: the layouts (0,0), (0,1), (1,1)
+#define HSD_F32_LAYOUTS(LAUNCH, EPI_, ...)                                   \
+  do {                                                                       \
+    if (pl.la == 0 && pl.lb == 0) LAUNCH<0, 0, EPI_, __VA_ARGS__>(p, pl, st); \
+    else if (pl.la == 0 && pl.lb == 1) LAUNCH<0, 1, EPI_, __VA_ARGS__>(p, pl, st); \
+    else if (pl.la == 1 && pl.lb == 1) LAUNCH<1, 1, EPI_, __VA_ARGS__>(p, pl, st); \
+    else abort();                                                            \
+  } while (0)
+
+template <int EPI, int BN, int FA>
+static void g8pk_launch(const G2Params& p, const GemmPlan& pl, const float* sa, const float* sb, hipStream_t st) {
+  const dim3 grid(pl.grid), wg(pl.wg);
+  if (pl.q8) {
+    if constexpr (epi_q8_copy(EPI)) hipLaunchKernelGGL((g2::gemm8pk_kernel<EPI, BN, FA, 0, true>), grid, wg, 0, st, p, sa, sb);
+    else abort();
+  } else {
+    hipLaunchKernelGGL((g2::gemm8pk_kernel<EPI, BN, FA, 0>), grid, wg, 0, st, p, sa, sb);
+  }
+}
+
+// the plan's main kernel; E2_STORE_RDOT exists at BN 256 only
+static void launch_main(const GemmPlan& pl, const G2Params& p, hipStream_t st, const float* sa, const float* sb) {
+  switch (pl.kernel) {
+    case GK_G2:
+      if (pl.seg) HSD_F32_LAYOUTS(g2_launch, E2_F32_SLAB, 256, true);
+      else if (pl.epi == E2_F32_SLAB) HSD_F32_LAYOUTS(g2_launch, E2_F32_SLAB, 256);
+      else if (pl.epi == E2_F32_ATOMIC) g2_launch<1, 1, E2_F32_ATOMIC, 256>(p, pl, st);
+      else
+        for_bf16_epi(pl.epi, [&](auto e) {
+          constexpr int E = decltype(e)::value;
+          if (pl.lb == 1) g2_launch<0, 1, E, 256>(p, pl, st);
+          else if (pl.bn == 256) g2_launch<0, 0, E, 256>(p, pl, st);
+          else if constexpr (E != E2_STORE_RDOT) g2_launch<0, 0, E, 192>(p, pl, st);
+          else abort();
+        });
+      break;
+    case GK_G2S:
+      if (pl.seg) HSD_F32_LAYOUTS(g2s_launch, E2_F32_SLAB, true);
+      else if (pl.epi == E2_F32_SLAB) HSD_F32_LAYOUTS(g2s_launch, E2_F32_SLAB, false);
+      else
+        for_bf16_epi(pl.epi, [&](auto e) {
+          constexpr int E = decltype(e)::value;
+          if (pl.lb == 1) g2s_launch<0, 1, E>(p, pl, st);
+          else g2s_launch<0, 0, E>(p, pl, st);
+        });
+      break;
+    case GK_G2PK:
+      for_bf16_epi(pl.epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        const dim3 grid(pl.grid), wg(pl.wg);
+        if (pl.bn == 256) hipLaunchKernelGGL((g2::gemm2pk_kernel<E, 256>), grid, wg, 0, st, p);
+        else if constexpr (E != E2_STORE_RDOT) hipLaunchKernelGGL((g2::gemm2pk_kernel<E, 192>), grid, wg, 0, st, p);
+        else abort();
+      });
+      break;
+    case GK_G8PK:
+      for_bf16_epi(pl.epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if (pl.bn == 256) {
+          if (pl.fa == 0) g8pk_launch<E, 256, 0>(p, pl, sa, sb, st);
+          else g8pk_launch<E, 256, 1>(p, pl, sa, sb, st);
+        } else if constexpr (E != E2_STORE_RDOT) {
+          if (pl.fa == 0) g8pk_launch<E, 192, 0>(p, pl, sa, sb, st);
+          else g8pk_launch<E, 192, 1>(p, pl, sa, sb, st);
+        } else {
+          abort();
+        }
+      });
+      break;
+    case GK_G8TT:
+      if (pl.fa == 0) hipLaunchKernelGGL((g2::gemm8tt_kernel<0, 0>), dim3(pl.grid), dim3(pl.wg), 0, st, p, sa, sb);
+      else hipLaunchKernelGGL((g2::gemm8tt_kernel<1, 0>), dim3(pl.grid), dim3(pl.wg), 0, st, p, sa, sb);
+      break;
+    default: abort();
+  }
+  HSD_CHECK_LAUNCH();
+}
+#undef HSD_F32_LAYOUTS
+
+// C (fp32, ldc) = / += Σ of `slabs` [M][N] slabs in ws
+static void run_slab_reduce(const float* ws, float* C, int64_t ldc, int M, int N, int slabs, bool assign,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(g2::slab_reduce_kernel, dim3(plan::slab_reduce_blocks(M, N)), dim3(256), 0, st, ws, C, ldc, M, N,
+                     slabs, assign ? 1 : 0);
   HSD_CHECK_LAUNCH();
 }
 
-bool gemm2_supported(int la, int lb, int epi, int M, int N, int K) {
-  if (K % 64 || M < 1 || N % 8) return false;
-  if (epi == E2_STORE_RDOT && (la != 0 || N % 256)) return false;
-  if (la == 0 && epi == E2_F32_SLAB) return N % 256 == 0;  // fp32-output NT, one pass (launch_gemm2)
-  if (la == 0 && lb == 0) return epi_bf16_out(epi) && gemm2_pick_bn(M, N) != 0;
-  if (la == 0 && lb == 1) return epi_bf16_out(epi) && (N % 256 == 0 || gemm2s_use(M, N, K));
-  if (la == 1 && lb == 1)
-    return (epi == E2_F32_ATOMIC || epi == E2_F32_SLAB) && M % 8 == 0 &&
-           (N % 256 == 0 || (epi == E2_F32_SLAB && gemm2st_use(M, N, K)));
-  return false;
-}
-
-// K-splits of the fp32-output NT GEMM (the fp32 step's split-product forward / dgrad): a 256 x 256 grid of at most
-// half the CUs (bert-large B = 8: M = 4,096 tokens, N = 1,024 -> 64 workgroups on 256 CUs) is split over K until it
-// fills the chip, keeping >= 8 K-tiles per split. HSD_F32NT_SPLITS: 1 = off, n = force n.
-int gemm2_f32nt_splits(int M, int N, int K) {
-  const int force = HSD_KNOB("HSD_F32NT_SPLITS", 0);
-  if (force > 0) return std::max(1, std::min(force, K / 64));
-  const int tiles = ((M + 255) / 256) * ((N + 255) / 256);
-  const int cus = g2_num_cus();
-  if (2 * tiles > cus) return 1;
-  return std::max(1, std::min(cus / tiles, K / (64 * 8)));
-}
-
-// K-splits of the TT wgrad (wgrad_plan)
-int gemm2_wgrad_splits(int M, int N, int K) {
-  return wgrad_plan(M, N, K).splits;
-}
-
-// NT-shaped GEMM (bf16 out, fused epilogues): B k-contiguous (LB = 0: B[N][K], e.g. the stored Wᵀ for dgrad) or
-// k-strided (LB = 1: B[K][N], the dgrad reading W[N_out][K_in] directly, no Wᵀ copy). 128 x 128 tiles for grids the
-// 256 x 256 kernel leaves mostly idle, split-K slabs + one reduce-and-epilogue pass for the smallest grids.
-template <int LB>
-static void launch_nt(const G2Params& p, int epi, int M, int N, int K, int splits, float* ws, float* dbias,
-                      hipStream_t st) {
-  if (splits <= 1 && gemm2s_use(M, N, K)) {
-    G2Params q = p;
-    q.tiles_n = N / g2::SBN;
-    q.ntiles = ((M + g2::SBM - 1) / g2::SBM) * q.tiles_n;
-    q.kps = K;
-#define G2_SMALL(E)                   \
-  case E:                             \
-    g2s_launch<0, LB, E>(q, q.ntiles, st); \
-    break;
-    switch (epi) {
-      G2_SMALL(E2_STORE)
-      G2_SMALL(E2_BIAS)
-      G2_SMALL(E2_BIAS_GELU)
-      G2_SMALL(E2_BIAS_DROP_RES)
-      G2_SMALL(E2_RES)
-      G2_SMALL(E2_DGELU)
-      G2_SMALL(E2_BIAS_GELU_D)
-      G2_SMALL(E2_MUL)
-      G2_SMALL(E2_STORE_RDOT)
-      default: abort();
-    }
-#undef G2_SMALL
-    return;
+// Executes a plan. p: the operands and the output as the caller sees it (C, ldc); the plan's tile counts, K-split and
+// landing are filled in here. ws: the fp32 workspace of pl.ws_numel elements when the plan lands through slabs.
+void run_gemm_plan(const GemmPlan& pl, const G2Params& p0, float* ws, hipStream_t st, const float* sa,
+                   const float* sb) {
+  if (!pl.supported() || (pl.slabs() && ws == nullptr)) abort();
+  G2Params p = p0;
+  p.kps = pl.kps;
+  p.tiles_n = pl.tiles_n;
+  p.ntiles = pl.ntiles;
+  p.accum_direct = pl.accum_flag ? 1 : 0;
+  if (pl.slabs()) {
+    p.C = ws;
+    p.dbias = nullptr;  // the epilogue pass sums the bias-gradient columns
   }
-  if (splits > 1) {
-    if (ws == nullptr || !epi_bf16_out(epi)) abort();
-    G2Params q = p;
-    q.C = ws;
-    q.dbias = nullptr;
-    int kps = (K + splits - 1) / splits;
-    kps = (kps + 63) / 64 * 64;
-    const int real = (K + kps - 1) / kps;
-    if (gemm2s_use(M, N, K)) {
-      q.tiles_n = N / g2::SBN;
-      q.ntiles = ((M + g2::SBM - 1) / g2::SBM) * q.tiles_n;
-      q.kps = kps;
-      g2s_launch<0, LB, E2_F32_SLAB>(q, q.ntiles * real, st);
-    } else {
-      g2_launch<0, LB, E2_F32_SLAB, 256>(q, splits, st);
-    }
-    const int gx = (N + 63) / 64;
-    const int gy_want = std::max(1, 2048 / gx);
-    int rpb = (M + gy_want - 1) / gy_want;
-    rpb = (rpb + 31) / 32 * 32;
-    const dim3 grid(gx, (M + rpb - 1) / rpb);
-#define G2_SK(E)                                                                                          \
-  case E:                                                                                                 \
-    hipLaunchKernelGGL(g2::splitk_epi_kernel<E>, grid, dim3(256), 0, st, (const float*)ws, real, rpb, p); \
-    break;
-    switch (epi) {
-      G2_SK(E2_STORE)
-      G2_SK(E2_BIAS)
-      G2_SK(E2_BIAS_GELU)
-      G2_SK(E2_BIAS_DROP_RES)
-      G2_SK(E2_RES)
-      G2_SK(E2_DGELU)
-      G2_SK(E2_BIAS_GELU_D)
-      G2_SK(E2_MUL)
-      G2_SK(E2_STORE_RDOT)
-      default: abort();
-    }
-#undef G2_SK
+  if (pl.kernel == GK_G2PK || pl.kernel == GK_G8PK) p.tq = g2_tq_slot(st);  // one ring slot per persistent launch
+  launch_main(pl, p, st, sa, sb);
+  if (pl.landing == GL_SLABS_ASSIGN || pl.landing == GL_SLABS_ADD) {
+    run_slab_reduce(ws, reinterpret_cast<float*>(p0.C), p0.ldc, p0.M, p0.N, pl.splits, pl.landing == GL_SLABS_ASSIGN,
+                    st);
+  } else if (pl.landing == GL_SLABS_EPI) {
+    int rpb;
+    const plan::GridDim g = plan::splitk_epi_grid(p0.M, p0.N, &rpb);
+    for_bf16_epi(pl.out_epi, [&](auto e) {
+      hipLaunchKernelGGL(g2::splitk_epi_kernel<decltype(e)::value>, dim3(g.x, g.y), dim3(256), 0, st,
+                         (const float*)ws, pl.splits, rpb, p0);
+    });
     HSD_CHECK_LAUNCH();
-    return;
-  }
-  {
-    int bn = LB == 1 || epi == E2_STORE_RDOT ? 256 : gemm2_pick_bn(M, N);  // k-strided B images are 256 wide
-    if (dbias != nullptr) {
-      if ((epi != E2_DGELU && epi != E2_MUL) || N % 256) abort();  // fused column sums: 8 columns per lane (BN 256)
-      bn = 256;
-    }
-    const bool pk = LB == 0 && g2_persist((M + 255) / 256 * (N / bn));
-#define G2_NT(E)                                                     \
-  case E:                                                            \
-    if (pk) {                                                        \
-      if (bn == 256) g2pk_launch<E, 256>(p, st);                     \
-      else g2pk_launch<E, 192>(p, st);                               \
-    } else if (bn == 256 || LB == 1) {                               \
-      g2_launch<0, LB, E, 256>(p, 1, st);                            \
-    } else {                                                         \
-      g2_launch<0, LB, E, LB == 1 ? 256 : 192>(p, 1, st);            \
-    }                                                                \
-    return;
-    switch (epi) {
-      G2_NT(E2_STORE)
-      G2_NT(E2_BIAS)
-      G2_NT(E2_BIAS_GELU)
-      G2_NT(E2_BIAS_DROP_RES)
-      G2_NT(E2_RES)
-      G2_NT(E2_DGELU)
-      G2_NT(E2_BIAS_GELU_D)
-      G2_NT(E2_MUL)
-      case E2_STORE_RDOT:  // 64-column wave tiles only (one head per 8-lane group): BN 256
-        if (pk) g2pk_launch<E2_STORE_RDOT, 256>(p, st);
-        else g2_launch<0, LB, E2_STORE_RDOT, 256>(p, 1, st);
-        return;
-      default: abort();
-    }
-#undef G2_NT
   }
 }
 
+// ---- thin reads of the plan (bindings, tools) -------------------------------------------------------------------------
+bool gemm2_supported(int la, int lb, int epi, int M, int N, int K) {
+  return plan::plan_gemm2(la, lb, epi, M, N, K, 0, false, gemm_num_cus()).supported();
+}
+bool gemm2_seg_supported(int la, int lb, int M, int N, int Kseg) {
+  return plan::plan_gemm2_seg(la, lb, M, N, Kseg, false, gemm_num_cus()).supported();
+}
+int64_t gemm2_seg_ws_numel(int la, int lb, int M, int N, int Kseg) {
+  return plan::plan_gemm2_seg(la, lb, M, N, Kseg, false, gemm_num_cus()).ws_numel;
+}
+int gemm2_wgrad_splits(int M, int N, int K) { return plan::wgrad_plan(M, N, K).splits; }
+int gemm2_nt_splits(int M, int N, int K) { return plan::gemm2_nt_splits(M, N, K); }
+int gemm2_f32nt_splits(int M, int N, int K) { return plan::gemm2_f32nt_splits(M, N, K, gemm_num_cus()); }
+bool gemm8_wgrad_supported(int M, int N, int T) { return plan::plan_gemm8_wgrad(M, N, T, 1, 0).supported(); }
+int gemm8_wgrad_splits(int M, int N, int T) { return plan::gemm8_wgrad_splits(M, N, T); }
+int64_t gemm8_wgrad_ws_numel(int M, int N, int T, int splits) {
+  return plan::plan_gemm8_wgrad(M, N, T, splits, 0).ws_numel;
+}
+
+// ---- entry points: fill G2Params, plan once (or take the caller's plan), run ------------------------------------------
 static unsigned long long* g_diag = nullptr;
 void gemm2_set_diag(void* p) { g_diag = (unsigned long long*)p; }
 
 void launch_gemm2(int la, int lb, int epi, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N,
                   int K, void* C, int64_t ldc, const bf16_t* bias, const bf16_t* aux, int64_t ldaux, bf16_t* C2,
                   double p_drop, uint64_t seed, int splits, float* ws, float* dbias, hipStream_t st, float* rd,
-                  int rd_seq) {
+                  int rd_seq, const GemmPlan* planned) {
   G2Params p{};
   p.dbias = dbias;
   p.rd = rd;
@@ -1714,108 +1491,17 @@ void launch_gemm2(int la, int lb, int epi, const bf16_t* A, int64_t lda, const b
   p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.M = M; p.N = N; p.K = K; p.C = C; p.ldc = ldc;
   p.bias = bias; p.aux = aux; p.ldaux = ldaux; p.C2 = C2;
   p.dp = make_dropout(p_drop, seed);
-  if (la == 0 && epi == E2_F32_SLAB) {
-    // fp32 output [M][N] (ldc == N): the split-product GEMMs of the fp32 step (fp32.hip, ops/hip32.py). splits > 1
-    // (gemm2_f32nt_splits: grids that would leave most CUs idle): K-split fp32 slabs in ws, then C = Σ slabs
-    if (ldc != N || (splits > 1 && ws == nullptr)) abort();
-    G2Params q = p;
-    if (splits > 1) q.C = ws;
-    if (lb == 0) g2_launch<0, 0, E2_F32_SLAB, 256>(q, splits, st);
-    else g2_launch<0, 1, E2_F32_SLAB, 256>(q, splits, st);
-    if (splits > 1) {
-      int kps = (K + splits - 1) / splits;
-      kps = (kps + 63) / 64 * 64;
-      const int real = (K + kps - 1) / kps;
-      const int64_t n4 = (int64_t)M * N / 4;
-      const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
-      hipLaunchKernelGGL(g2::slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, ws, reinterpret_cast<float*>(C), ldc,
-                         M, N, real, 1);
-      HSD_CHECK_LAUNCH();
-    }
-    return;
-  }
-  if (la == 0 && lb == 0) {
-    launch_nt<0>(p, epi, M, N, K, splits, ws, dbias, st);
-  } else if (la == 1 && lb == 1) {
-    if (splits <= 0) splits = gemm2_wgrad_splits(M, N, K);
-    if (epi == E2_F32_SLAB && gemm2st_use(M, N, K) && (splits == 1 || ws != nullptr)) {
-      G2Params q = p;
-      q.tiles_n = N / g2::SBN;
-      q.ntiles = ((M + g2::SBM - 1) / g2::SBM) * q.tiles_n;
-      int kps = (K + splits - 1) / splits;
-      kps = (kps + 63) / 64 * 64;
-      const int real = (K + kps - 1) / kps;
-      q.kps = kps;
-      if (real > 1) q.C = ws;
-      g2s_launch<1, 1, E2_F32_SLAB>(q, q.ntiles * real, st);
-      if (real > 1) {
-        const int64_t n4 = (int64_t)M * N / 4;
-        int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
-        hipLaunchKernelGGL(g2::slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, ws, reinterpret_cast<float*>(C),
-                           ldc, M, N, real, 0);
-        HSD_CHECK_LAUNCH();
-      }
-    } else if (epi == E2_F32_SLAB && splits > 1 && ws != nullptr) {
-      G2Params q = p;
-      q.C = ws;
-      g2_launch<1, 1, E2_F32_SLAB, 256>(q, splits, st);
-      int kps = (K + splits - 1) / splits;
-      kps = (kps + 63) / 64 * 64;
-      const int real = (K + kps - 1) / kps;
-      const int64_t n4 = (int64_t)M * N / 4;
-      int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
-      hipLaunchKernelGGL(g2::slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, ws, reinterpret_cast<float*>(C), ldc,
-                         M, N, real, 0);
-      HSD_CHECK_LAUNCH();
-    } else if (epi == E2_F32_SLAB && splits <= 1 && ldc % 4 == 0 && !HSD_KNOB("HSD_G2_TT_ATOMIC", 0)) {
-      // one K-split: every output element has one owner -> C += acc in place instead of fp32 atomics (the tied MLM
-      // decoder weight gradient: Vp x H = 51.6 M atomics per roberta-large step; HSD_G2_TT_ATOMIC=1 = the old path)
-      G2Params q = p;
-      q.accum_direct = 1;
-      g2_launch<1, 1, E2_F32_SLAB, 256>(q, 1, st);
-    } else {
-      g2_launch<1, 1, E2_F32_ATOMIC, 256>(p, splits, st);
-    }
-  } else if (la == 0 && lb == 1) {
-    launch_nt<1>(p, epi, M, N, K, splits, ws, dbias, st);
-  } else {
-    abort();
-  }
+  if (la == 0 && epi == E2_F32_SLAB && ldc != N) abort();  // fp32 NT output: [M][N]
+  const GemmPlan pl = planned != nullptr ? *planned
+                                         : plan::plan_gemm2(la, lb, epi, M, N, K, la == 0 && splits <= 0 ? 1 : splits,
+                                                            dbias != nullptr, gemm_num_cus(), ldc % 4 == 0);
+  run_gemm_plan(pl, p, ws, st);
 }
 
-// ---- segmented-K fp32-output GEMMs (the fp32 step's split products) ------------------------------------------------
-// C[M][N] (fp32) = Σ_{s<3} A_s · B_s over segments of Kseg (G2Params seg): la = 0, lb = 0 / 1: the NT forward / dgrad
-// (C written, or C += with `accumulate`: the fp32 blocks' residual gradient + dgrad in place; split-K slabs + one reduce
-// for small grids, gemm2_f32nt_splits), la = lb = 1: the TT weight gradient (C += ..., wgrad_plan's tile size and
-// K-splits). Kseg % 64 == 0.
-// the fp32 forward / dgrad on 128 x 128 tiles (gemm2s, one K-split) for grids that 256 x 256 tiles leave mostly idle
-// (gemm2s_use) and K < 6,144, instead of 256 x 256 tiles split over K into slabs plus a reduce pass. bert-large T = 4,096
-// (tools/seg_vs_cat.py, profiles/r6/seg_vs_cat_r6e.log): N 1,024 at K 3 x 1,024: 32.4 / 34.8 us (fwd / dgrad) vs 44.4 /
-// 45.2 on slabs; at K 3 x 3,072 and 3 x 4,096 the slabs win (81.6 vs 91.2, 96.6 vs 111.8, 99.3 vs 124.5 us).
-// HSD_SEG_NT_SMALL=0: always the slabs.
-static bool seg_nt_small(int M, int N, int K) {
-  return HSD_KNOB("HSD_SEG_NT_SMALL", 1) && K < 6144 && gemm2s_use(M, N, K);
-}
-
-bool gemm2_seg_supported(int la, int lb, int M, int N, int Kseg) {
-  if (Kseg % 64 || Kseg <= 0) return false;
-  if (la == 0) return (lb == 0 || lb == 1) && gemm2_supported(0, lb, E2_F32_SLAB, M, N, 3 * Kseg);
-  return la == 1 && lb == 1 && gemm2_supported(1, 1, E2_F32_SLAB, M, N, 3 * Kseg);
-}
-
-int64_t gemm2_seg_ws_numel(int la, int lb, int M, int N, int Kseg) {
-  const int K = 3 * Kseg;
-  if (la == 0 && seg_nt_small(M, N, K)) return 0;
-  int sp = la == 0 ? gemm2_f32nt_splits(M, N, K) : wgrad_plan(M, N, K).splits;
-  if (sp <= 1) return 0;
-  int kps = (K + sp - 1) / sp;
-  kps = (kps + 63) / 64 * 64;
-  return (int64_t)((K + kps - 1) / kps) * M * N;
-}
-
+// C[M][N] (fp32) = Σ_{s<3} A_s · B_s over segments of Kseg (G2Params seg; plan_gemm2_seg). Kseg % 64 == 0.
 void launch_gemm2_seg(int la, int lb, const bf16_t* const A[3], int64_t lda, const bf16_t* const B[3], int64_t ldb,
                       int M, int N, int Kseg, float* C, int64_t ldc, float* ws, hipStream_t st, bool accumulate) {
-  if (!gemm2_seg_supported(la, lb, M, N, Kseg) || ldc % 4) abort();
+  if (ldc % 4 || (la == 0 && ldc != N)) abort();
   G2Params p{};
   p.nt_store = 1;
   p.A = A[0]; p.lda = lda; p.B = B[0]; p.ldb = ldb; p.M = M; p.N = N; p.K = 3 * Kseg; p.C = C; p.ldc = ldc;
@@ -1824,113 +1510,20 @@ void launch_gemm2_seg(int la, int lb, const bf16_t* const A[3], int64_t lda, con
     p.segA[s] = A[s];
     p.segB[s] = B[s];
   }
-  const int K = 3 * Kseg;
-  auto reduce = [&](int real, int assign) {
-    const int64_t n4 = (int64_t)M * N / 4;
-    const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
-    hipLaunchKernelGGL(g2::slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, ws, C, ldc, M, N, real, assign);
-    HSD_CHECK_LAUNCH();
-  };
-  auto real_of = [&](int sp) {
-    int kps = (K + sp - 1) / sp;
-    kps = (kps + 63) / 64 * 64;
-    return (K + kps - 1) / kps;
-  };
-  if (la == 0) {
-    if (ldc != N) abort();
-    if (seg_nt_small(M, N, K)) {
-      // 128 x 128 tiles, one K-split: the grid fills the CUs without slabs or a reduce pass; each output element has
-      // one owner (written, or C += acc with `accumulate`)
-      G2Params q = p;
-      q.tiles_n = N / g2::SBN;
-      q.ntiles = ((M + g2::SBM - 1) / g2::SBM) * q.tiles_n;
-      q.kps = K;
-      q.accum_direct = accumulate ? 1 : 0;
-      if (lb == 0) g2s_launch<0, 0, E2_F32_SLAB, true>(q, q.ntiles, st);
-      else g2s_launch<0, 1, E2_F32_SLAB, true>(q, q.ntiles, st);
-      return;
-    }
-    const int sp = gemm2_f32nt_splits(M, N, K);
-    if (sp > 1 && ws == nullptr) abort();
-    G2Params q = p;
-    if (sp > 1) q.C = ws;
-    else q.accum_direct = accumulate ? 1 : 0;  // one split: each element has one owner (C += acc in place)
-    if (lb == 0) g2_launch<0, 0, E2_F32_SLAB, 256, true>(q, sp, st);
-    else g2_launch<0, 1, E2_F32_SLAB, 256, true>(q, sp, st);
-    if (sp > 1) reduce(real_of(sp), accumulate ? 0 : 1);
-    return;
-  }
-  const WgradPlan plan = wgrad_plan(M, N, K);
-  const int real = real_of(plan.splits);
-  if (real > 1 && ws == nullptr) abort();
-  G2Params q = p;
-  if (plan.small) {
-    q.tiles_n = N / g2::SBN;
-    q.ntiles = ((M + g2::SBM - 1) / g2::SBM) * q.tiles_n;
-    int kps = (K + plan.splits - 1) / plan.splits;
-    q.kps = (kps + 63) / 64 * 64;
-    if (real > 1) q.C = ws;  // one split: the kernel accumulates into C (unique owner per element)
-    g2s_launch<1, 1, E2_F32_SLAB, true>(q, q.ntiles * real, st);
-  } else if (real > 1) {
-    q.C = ws;
-    g2_launch<1, 1, E2_F32_SLAB, 256, true>(q, plan.splits, st);
-  } else {
-    q.accum_direct = 1;
-    g2_launch<1, 1, E2_F32_SLAB, 256, true>(q, 1, st);
-  }
-  if (real > 1) reduce(real, 0);
+  run_gemm_plan(plan::plan_gemm2_seg(la, lb, M, N, Kseg, accumulate, gemm_num_cus()), p, ws, st);
 }
 
 // ---- fp8 TT weight gradient (g2::gemm8tt_kernel) ----------------------------------------------------------------------
-bool gemm8_wgrad_supported(int M, int N, int T) { return M % 256 == 0 && N % 256 == 0 && T % 128 == 0 && T >= 128; }
-
-// K-splits: wgrad_plan's cost model for the 256-tile kernel with one fp8 K-tile (128 tokens: the bytes and MFMA cycles
-// of one bf16 K-tile of 64) per bf16 K-tile
-int gemm8_wgrad_splits(int M, int N, int T) {
-  const int kt_all = T / 128;
-  int best = 1;
-  double best_cost = 1e30;
-  for (int sp = 1; sp <= 32 && (sp == 1 || kt_all / sp >= 2); ++sp) {
-    const double c = wgrad_cost(M, N, T / 2, sp, false);
-    if (c < best_cost) { best_cost = c; best = sp; }
-  }
-  return best;
-}
-
-// token splits actually launched for `splits` requested (each a multiple of 128 tokens); the workspace holds that
-// many [M][N] fp32 slabs
-static int g8tt_kps(int T, int splits) {
-  int kps = (T + splits - 1) / splits;
-  return (kps + 127) / 128 * 128;
-}
-int64_t gemm8_wgrad_ws_numel(int M, int N, int T, int splits) {
-  if (splits <= 0) splits = gemm8_wgrad_splits(M, N, T);
-  const int kps = g8tt_kps(T, splits);
-  return (int64_t)((T + kps - 1) / kps) * M * N;
-}
-
 // C[M][N] (fp32, ldc) += sdy·sx · dY8ᵀ · X8: dY8 [T][M] (ldd bytes, format fdy), X8 [T][N] (ldx bytes, e4m3)
 void launch_gemm8_wgrad(const uint8_t* dy, int64_t ldd, int fdy, const float* sdy, const uint8_t* x, int64_t ldx,
                         int fx, const float* sx, int M, int N, int T, float* C, int64_t ldc, int splits, float* ws,
                         hipStream_t st) {
-  if (!gemm8_wgrad_supported(M, N, T) || fx != 0 || (fdy != 0 && fdy != 1) || ws == nullptr) abort();
-  if (splits <= 0) splits = gemm8_wgrad_splits(M, N, T);
+  if (fx != 0) abort();
   G2Params p{};
   p.A = reinterpret_cast<const bf16_t*>(dy); p.lda = ldd;
   p.B = reinterpret_cast<const bf16_t*>(x); p.ldb = ldx;
-  p.M = M; p.N = N; p.K = T; p.C = ws; p.ldc = N;
-  p.kps = g8tt_kps(T, splits);
-  const int real = (T + p.kps - 1) / p.kps;
-  p.tiles_n = N / 256;
-  p.ntiles = (M / 256) * p.tiles_n;
-  const dim3 grid(p.ntiles * real);
-  if (fdy == 0) hipLaunchKernelGGL((g2::gemm8tt_kernel<0, 0>), grid, dim3(512), 0, st, p, sdy, sx);
-  else hipLaunchKernelGGL((g2::gemm8tt_kernel<1, 0>), grid, dim3(512), 0, st, p, sdy, sx);
-  HSD_CHECK_LAUNCH();
-  const int64_t n4 = (int64_t)M * N / 4;
-  const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 2048);
-  hipLaunchKernelGGL(g2::slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, ws, C, ldc, M, N, real, 0);
-  HSD_CHECK_LAUNCH();
+  p.M = M; p.N = N; p.K = T; p.C = C; p.ldc = ldc;
+  run_gemm_plan(plan::plan_gemm8_wgrad(M, N, T, splits, fdy), p, ws, st, sdy, sx);
 }
 
 }  // namespace hsd

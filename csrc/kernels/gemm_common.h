@@ -4,26 +4,9 @@
 #pragma once
 #include "common.h"
 #include "fp8_common.h"
+#include "gemm_plan.h"  // enum Epi2 and its predicates, GemmPlan
 
 namespace hsd {
-
-// E2_BIAS_GELU_D: C = gelu'(y), C2 = gelu(y) (y = acc + bias) — the FFN1 forward keeps the GELU DERIVATIVE
-// for backward, so the FFN2 dgrad epilogue is a plain product (E2_MUL: C = bf16(acc) * aux) instead of
-// re-evaluating erf/exp per element.
-// E2_STORE_RDOT: C = bf16(acc), plus the attention backward's delta rows rd[(b·heads + h)·S + s] = Σ_{64 columns of head h}
-// C·aux over row m = b·S + s (aux = the attention output O, heads = N / 64): the out-projection dgrad writes dO AND the
-// row dots the streaming attention backward would otherwise recompute in a separate pass (re-reading dO and O)
-enum Epi2 : int { E2_STORE = 0, E2_BIAS = 1, E2_BIAS_GELU = 2, E2_BIAS_DROP_RES = 3, E2_RES = 4, E2_DGELU = 5,
-                  E2_F32_ATOMIC = 6, E2_F32_SLAB = 7, E2_BIAS_GELU_D = 8, E2_MUL = 9, E2_STORE_RDOT = 10 };
-
-__host__ __device__ constexpr bool epi_bias(int e) { return e == E2_BIAS || e == E2_BIAS_GELU || e == E2_BIAS_DROP_RES || e == E2_BIAS_GELU_D; }
-__host__ __device__ constexpr bool epi_aux(int e) {
-  return e == E2_BIAS_DROP_RES || e == E2_RES || e == E2_DGELU || e == E2_MUL || e == E2_STORE_RDOT;
-}
-__host__ __device__ constexpr bool epi_two_out(int e) { return e == E2_BIAS_GELU || e == E2_BIAS_GELU_D; }
-__host__ __device__ constexpr bool epi_bf16_out(int e) {
-  return e <= E2_DGELU || e == E2_BIAS_GELU_D || e == E2_MUL || e == E2_STORE_RDOT;
-}
 
 struct G2Params {
   const bf16_t* A;
@@ -69,6 +52,13 @@ struct G2Params {
   const bf16_t* segA[3];
   const bf16_t* segB[3];
 };
+
+// gemm2.hip: the shared launcher. Runs `pl` on the operands and the output in `p` (tile counts, K-split and landing
+// come from the plan); ws: pl.ws_numel fp32 elements when the plan lands through slabs; sa / sb: the fp8 kernels'
+// device dequant scalars.
+int gemm_num_cus();
+void run_gemm_plan(const GemmPlan& pl, const G2Params& p, float* ws, hipStream_t st, const float* sa = nullptr,
+                   const float* sb = nullptr);
 
 // wave-uniform copy of a kernel-argument pointer (readfirstlane'd halves: SGPRs, as wave_rsrc below)
 __device__ __forceinline__ const bf16_t* uniform_ptr(const bf16_t* ptr) {

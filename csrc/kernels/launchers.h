@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gemm_plan.h"
+
 namespace hsd {
 typedef uint16_t bf16_t;
 struct DropoutParams;
@@ -105,8 +107,6 @@ namespace hsd {
 void launch_gemm(int la, int lb, int epi, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N,
                  int K, void* C, int64_t ldc, const bf16_t* bias, const bf16_t* aux, int64_t ldaux, bf16_t* C2,
                  double p_drop, uint64_t seed, int splits, hipStream_t st);
-// gemm2.hip — 256-row-tile 8-phase MFMA GEMM: (0,0) NT bf16 out with epilogues 0..5; (1,1) TT fp32 out
-// (epi 6 = atomics, 7 = split-K slabs in `ws` [splits][M][N] + reduce into C)
 // device step seed for dropout (common.h g_dropout_dev_seed); nullptr = off
 void set_dropout_dev_seed(const uint32_t* p);
 // HSD_* knobs are cached per generation (common.h HSD_KNOB); this re-reads them at their next use
@@ -150,34 +150,42 @@ void launch_cls32_bwd(const float* pre, const float* t_in, const float* W2, cons
 // contention emulation: `blocks` workgroups holding one whole CU each (160 KiB LDS) for `usec` us
 void launch_cu_hog(int blocks, double usec, hipStream_t st);
 
-// fp8 (gemm8.hip / fp8.hip)
+// fp8.hip
+void launch_fp8_quant(const bf16_t* x, int64_t n, float* amax, uint8_t* q, float* sinv, int fmt, bool compute_amax,
+                      float* amax_track, hipStream_t st);
+void launch_fp8_quant_many(const int64_t* amax_desc, int n_amax, int amax_blocks, const int64_t* quant_desc,
+                           int n_quant, int quant_blocks_total, float* amax, float* sinv, int fmt, hipStream_t st);
+int fp8_elems_per_block();
+void attn_set_force_generic(bool on);  // tests: every S on the tiled generic attention kernels
+void attn128_set_diag(void* p);  // diagnostic phase stamps of the S=128 attention backward ([B*heads][8] u64)
+
+// ---- MFMA GEMMs (gemm2.hip, gemm8.hip). The launch policy is gemm_plan.h: the *_supported / *_splits / *_ws_numel
+// functions are thin reads of a plan; a launcher given `planned` runs that plan instead of planning again. -----------
+int gemm_num_cus();  // CUs of the current device (256 without one)
+void gemm2_set_diag(void* p);  // diagnostic timestamps of the persistent NT kernel ([grid][64][4] u64), nullptr = off
+// gemm2.hip — 256-row-tile 8-phase MFMA GEMM: (0,0) / (0,1) NT bf16 out with the bf16 epilogues; (0,x) epi 7: fp32 NT
+// out; (1,1) TT fp32 out (epi 6 = atomics, 7 = in place, or split-K slabs in `ws` + reduce into C)
+void launch_gemm2(int la, int lb, int epi, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N,
+                  int K, void* C, int64_t ldc, const bf16_t* bias, const bf16_t* aux, int64_t ldaux, bf16_t* C2,
+                  double p_drop, uint64_t seed, int splits, float* ws, float* dbias, hipStream_t st,
+                  float* rd = nullptr, int rd_seq = 0, const GemmPlan* planned = nullptr);
+bool gemm2_supported(int la, int lb, int epi, int M, int N, int K);
+int gemm2_wgrad_splits(int M, int N, int K);
+int gemm2_nt_splits(int M, int N, int K);
+int gemm2_f32nt_splits(int M, int N, int K);
+// segmented-K fp32-output GEMMs over bf16 hi / lo operand halves (the fp32 step's split products)
+bool gemm2_seg_supported(int la, int lb, int M, int N, int Kseg);
+int64_t gemm2_seg_ws_numel(int la, int lb, int M, int N, int Kseg);
+void launch_gemm2_seg(int la, int lb, const bf16_t* const A[3], int64_t lda, const bf16_t* const B[3], int64_t ldb,
+                      int M, int N, int Kseg, float* C, int64_t ldc, float* ws, hipStream_t st, bool accumulate = false);
+// fp8 NT (gemm8.hip; gemm2.hip gemm8pk_kernel)
 bool gemm8_supported(int epi, int M, int N, int K);
 void launch_gemm8(int epi, const uint8_t* A, int64_t lda, int fa, const float* sa, const uint8_t* B, int64_t ldb,
                   int fb, const float* sb, int M, int N, int K, bf16_t* C, int64_t ldc, const bf16_t* bias,
                   const bf16_t* aux, int64_t ldaux, bf16_t* C2, double p_drop, uint64_t seed, float* dbias,
                   hipStream_t st, uint8_t* q8 = nullptr, const float* q8_amax = nullptr, float* q8_sinv = nullptr,
                   float* q8_track = nullptr, int q8_fmt = 0, float* rd = nullptr, int rd_seq = 0,
-                  int q8_only = 0);
-void launch_fp8_quant(const bf16_t* x, int64_t n, float* amax, uint8_t* q, float* sinv, int fmt, bool compute_amax,
-                      float* amax_track, hipStream_t st);
-void launch_fp8_quant_many(const int64_t* amax_desc, int n_amax, int amax_blocks, const int64_t* quant_desc,
-                           int n_quant, int quant_blocks_total, float* amax, float* sinv, int fmt, hipStream_t st);
-int fp8_elems_per_block();
-void attn_set_force_generic(bool on);
-// gemm2.hip: segmented-K fp32-output GEMMs over bf16 hi / lo operand halves (the fp32 step's split products)
-bool gemm2_seg_supported(int la, int lb, int M, int N, int Kseg);
-int64_t gemm2_seg_ws_numel(int la, int lb, int M, int N, int Kseg);
-void launch_gemm2_seg(int la, int lb, const bf16_t* const A[3], int64_t lda, const bf16_t* const B[3], int64_t ldb,
-                      int M, int N, int Kseg, float* C, int64_t ldc, float* ws, hipStream_t st, bool accumulate = false);  // tests: every S on the tiled generic attention kernels
-void attn128_set_diag(void* p);  // diagnostic phase stamps of the S=128 attention backward ([B*heads][8] u64)
-void gemm2_set_diag(void* p);  // diagnostic timestamps of the persistent NT kernel ([grid][64][4] u64), nullptr = off
-void launch_gemm2(int la, int lb, int epi, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N,
-                  int K, void* C, int64_t ldc, const bf16_t* bias, const bf16_t* aux, int64_t ldaux, bf16_t* C2,
-                  double p_drop, uint64_t seed, int splits, float* ws, float* dbias, hipStream_t st,
-                  float* rd = nullptr, int rd_seq = 0);
-bool gemm2_supported(int la, int lb, int epi, int M, int N, int K);
-int gemm2_wgrad_splits(int M, int N, int K);
-int gemm2_f32nt_splits(int M, int N, int K);
+                  int q8_only = 0, const GemmPlan* planned = nullptr);
 // fp8 TT weight gradient (gemm2.hip gemm8tt_kernel + slab_reduce): C[M][N] (fp32) += sdy·sx · dY8ᵀ · X8
 bool gemm8_wgrad_supported(int M, int N, int T);
 int gemm8_wgrad_splits(int M, int N, int T);
@@ -185,5 +193,4 @@ int64_t gemm8_wgrad_ws_numel(int M, int N, int T, int splits);
 void launch_gemm8_wgrad(const uint8_t* dy, int64_t ldd, int fdy, const float* sdy, const uint8_t* x, int64_t ldx,
                         int fx, const float* sx, int M, int N, int T, float* C, int64_t ldc, int splits, float* ws,
                         hipStream_t st);
-int gemm2_nt_splits(int M, int N, int K);
 }  // namespace hsd

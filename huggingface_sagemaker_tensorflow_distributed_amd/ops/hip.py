@@ -205,13 +205,13 @@ def _launch_wgrad(s, g: "_Grad", dy, x, dyq, xq):
     if g.buf is g.mg and _wgrad8_ok(dyq, xq, N, K, T):
         _wgrad8(g.buf, dyq, xq, N, K, T, s)
         return None
-    if g.buf is g.mg and _C.gemm2_supported(1, 1, 7, N, K, T):
+    ok, sp, ws = _C.gemm2_wgrad_plan(N, K, T) if g.buf is g.mg else (False, 0, 0)
+    if ok:
         # the common case without any Python stream plumbing: TT GEMM (+ split-K reduce) launched on the side stream
-        sp = _C.gemm2_splits(N, K, T)
         # (fp32 atomics per K-split instead of slabs + one reduce pass: headline -5.7 %, bert-large B = 64 -13.5 %,
         # profiles/r6/wgrad_atomic_rejected_r6.log)
-        _C.gemm2_on(s.cuda_stream, dy, x, g.buf, 1, 1, 7, None, None, None, 0.0, 0, sp,
-                    _workspace(sp * N * K, dy.device, s), None)
+        _C.gemm2_on(s.cuda_stream, dy, x, g.buf, 1, 1, EPI_F32_SLAB, None, None, None, 0.0, 0, sp,
+                    _workspace(ws, dy.device, s), None)
         return None
     with torch.cuda.stream(s):
         gemm_wgrad_(g, dy, x, dyq, xq)
@@ -301,10 +301,7 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b):
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        if x2.dtype == torch.bfloat16 and _nt_ok(x2.shape[0], w.shape[0], x2.shape[1], EPI_BIAS):
-            y = gemm_fwd(x2, w, EPI_BIAS, bias=b)
-        else:
-            y = torch.addmm(b, x2, w.t())
+        y, _ = _dense_fwd(x2, w, b)
         ctx.save_for_backward(x2, w, b)
         ctx.xshape = x.shape
         return y.view(*x.shape[:-1], w.shape[0])
@@ -313,17 +310,9 @@ class _Linear(torch.autograd.Function):
     def backward(ctx, dy):
         x2, w, b = ctx.saved_tensors
         dy2 = dy.reshape(-1, w.shape[0]).contiguous()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if dy2.dtype == torch.bfloat16 and _nt_ok(dy2.shape[0], w.shape[1], dy2.shape[1], EPI_STORE):
-                dx = gemm_dgrad(dy2, w).view(ctx.xshape)
-            else:
-                dx = torch.mm(dy2, w).view(ctx.xshape)
+        dx = _dense_dgrad(dy2, w).view(ctx.xshape) if ctx.needs_input_grad[0] else None
         gw, gb = _Grad(w), _Grad(b)
-        if dy2.dtype == torch.bfloat16 and _C.gemm2_supported(1, 1, 7, w.shape[0], w.shape[1], dy2.shape[0]):
-            gemm_wgrad_(gw, dy2, x2)
-        else:
-            _wgrad_(gw, dy2, x2)
+        _dense_wgrad_(gw, dy2, x2)
         if dy2.shape[1] % 8 == 0:
             _C.colsum(dy2, gb.buf)
         else:
@@ -342,13 +331,7 @@ class _LinearGelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b):
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        if x2.dtype == torch.bfloat16 and _nt_ok(x2.shape[0], w.shape[0], x2.shape[1], EPI_BIAS_GELU):
-            g = torch.empty((x2.shape[0], w.shape[0]), dtype=x2.dtype, device=x2.device)
-            y = gemm_fwd(x2, w, EPI_BIAS_GELU, bias=b, out2=g)
-        else:
-            y = torch.addmm(b, x2, w.t())
-            g = torch.empty_like(y)
-            _C.gelu_fwd(y, g)
+        y, g = _dense_fwd(x2, w, b, EPI_BIAS_GELU)
         ctx.save_for_backward(x2, w, b, y)
         ctx.xshape = x.shape
         return g.view(*x.shape[:-1], w.shape[0])
@@ -360,16 +343,8 @@ class _LinearGelu(torch.autograd.Function):
         gw, gb = _Grad(w), _Grad(b)
         da = torch.empty_like(y)
         _C.gelu_bwd_colsum(dg2, y, da, gb.buf)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if da.dtype == torch.bfloat16 and _nt_ok(da.shape[0], w.shape[1], da.shape[1], EPI_STORE):
-                dx = gemm_dgrad(da, w).view(ctx.xshape)
-            else:
-                dx = torch.mm(da, w).view(ctx.xshape)
-        if da.dtype == torch.bfloat16 and _C.gemm2_supported(1, 1, 7, w.shape[0], w.shape[1], da.shape[0]):
-            gemm_wgrad_(gw, da, x2)
-        else:
-            _wgrad_(gw, da, x2)
+        dx = _dense_dgrad(da, w).view(ctx.xshape) if ctx.needs_input_grad[0] else None
+        _dense_wgrad_(gw, da, x2)
         return dx, gw.done(), gb.done()
 
 
@@ -382,10 +357,7 @@ class _DenseResidualLN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, res, ln_w, ln_b, eps, p, seed):
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        if x2.dtype == torch.bfloat16 and _nt_ok(x2.shape[0], w.shape[0], x2.shape[1], EPI_BIAS):
-            y = gemm_fwd(x2, w, EPI_BIAS, bias=b)
-        else:
-            y = torch.addmm(b, x2, w.t())
+        y, _ = _dense_fwd(x2, w, b)
         rows, H = y.shape
         z = torch.empty_like(y)
         out = torch.empty_like(y)
@@ -409,16 +381,8 @@ class _DenseResidualLN(torch.autograd.Function):
             _C.ln_bwd(dout2, z, mean, rstd, ln_w, None, dy, None, gg.buf, gbe.buf, gb.buf, 0.0, 0)
             dz = dy
         gln_w, gln_b = gg.done(), gbe.done()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if _nt_ok(dy.shape[0], w.shape[1], dy.shape[1], EPI_STORE):
-                dx = gemm_dgrad(dy, w).view(ctx.xshape)
-            else:
-                dx = torch.mm(dy, w).view(ctx.xshape)
-        if _C.gemm2_supported(1, 1, 7, w.shape[0], w.shape[1], dy.shape[0]):
-            gemm_wgrad_(gw, dy, x2)
-        else:
-            _wgrad_(gw, dy, x2)
+        dx = _dense_dgrad(dy, w, bf16_only=False).view(ctx.xshape) if ctx.needs_input_grad[0] else None
+        _dense_wgrad_(gw, dy, x2, bf16_only=False)
         return dx, gw.done(), gb.done(), dz.view(dout.shape), gln_w, gln_b, None, None, None
 
 
@@ -633,6 +597,44 @@ def _workspace(numel: int, device, stream=None) -> torch.Tensor:
 
 def _nt_ok(M, N, K, epi):
     return _C.gemm2_supported(0, 0, epi, M, N, K)
+
+
+def _tt_ok(N, K, T):
+    """gemm2 takes the weight gradient dW[N][K] over T tokens."""
+    return _C.gemm2_supported(1, 1, EPI_F32_SLAB, N, K, T)
+
+
+# The dense layers outside the fused encoder blocks (task heads, LN tails): gemm2 when the shape tiles, else the library
+# GEMM (e.g. the 2-way classifier). ``bf16_only``: the library GEMM for any other dtype too.
+def _dense_fwd(x2, w, b, epi=EPI_BIAS, bf16_only=True):
+    """``(y, g)``: y = x2 wᵀ + b, and with EPI_BIAS_GELU also g = gelu(y) (else None)."""
+    gelu = epi == EPI_BIAS_GELU
+    if (x2.dtype == torch.bfloat16 or not bf16_only) and _nt_ok(x2.shape[0], w.shape[0], x2.shape[1], epi):
+        g = torch.empty((x2.shape[0], w.shape[0]), dtype=x2.dtype, device=x2.device) if gelu else None
+        return gemm_fwd(x2, w, epi, bias=b, out2=g), g
+    y = torch.addmm(b, x2, w.t())
+    g = None
+    if gelu:
+        g = torch.empty_like(y)
+        _C.gelu_fwd(y, g)
+    return y, g
+
+
+def _dense_dgrad(dy2, w, bf16_only=True):
+    """dx = dy2 · w"""
+    if (dy2.dtype == torch.bfloat16 or not bf16_only) and _nt_ok(dy2.shape[0], w.shape[1], dy2.shape[1], EPI_STORE):
+        return gemm_dgrad(dy2, w)
+    return torch.mm(dy2, w)
+
+
+def _dense_wgrad_(g: "_Grad", dy2, x2, bf16_only=True, small_rows=False):
+    """g += dy2ᵀ · x2. ``small_rows``: under 64 rows that gemm2 does not take go to the small-T kernel."""
+    if (dy2.dtype == torch.bfloat16 or not bf16_only) and _tt_ok(dy2.shape[1], x2.shape[1], dy2.shape[0]):
+        gemm_wgrad_(g, dy2, x2)
+    elif small_rows and dy2.shape[0] < 64:
+        _C.small_wgrad(dy2, x2, g.buf.view(dy2.shape[1], x2.shape[1]))
+    else:
+        _wgrad_(g, dy2, x2)
 
 
 # ---- fp8 GEMM path (SURVEY.md §2.10 K19; gemm8.hip / fp8.hip) -------------------------------------------
@@ -910,10 +912,10 @@ def gemm_wgrad_(g: "_Grad", dy, x, dyq=None, xq=None):
     N, K, T = dy.shape[1], x.shape[1], dy.shape[0]
     if _wgrad8_ok(dyq, xq, N, K, T):
         _wgrad8(g.buf, dyq, xq, N, K, T)
-    elif _C.gemm2_supported(1, 1, 7, N, K, T):
-        sp = _C.gemm2_splits(N, K, T)
-        ws = _workspace(sp * N * K, dy.device)
-        _C.gemm2(dy, x, g.buf, 1, 1, 7, None, None, None, 0.0, 0, sp, ws, None)
+        return
+    ok, sp, ws = _C.gemm2_wgrad_plan(N, K, T)
+    if ok:
+        _C.gemm2(dy, x, g.buf, 1, 1, EPI_F32_SLAB, None, None, None, 0.0, 0, sp, _workspace(ws, dy.device), None)
     else:
         splits = _wgrad_splits(N, K, T)
         _C.gemm(dy, x, g.buf, 1, 1, EPI_F32_ATOMIC, None, None, None, 0.0, 0, splits)
@@ -1173,7 +1175,7 @@ class _ClsHead(torch.autograd.Function):
         x = h.reshape(B, S * H)[:, :H]  # the [CLS] rows, read in place (row stride S*H)
         if p_in > 0:
             x = dropout(x.contiguous(), p_in, seed_in)
-        pre = gemm_fwd(x, w1, EPI_BIAS, bias=b1) if _nt_ok(B, H, H, EPI_BIAS) else torch.addmm(b1, x, w1.t())
+        pre, _ = _dense_fwd(x, w1, b1, bf16_only=False)
         t = torch.empty_like(pre)
         logits = torch.empty((B, C), dtype=h.dtype, device=h.device)
         nblk = _C.cls_head_blocks(B)
@@ -1200,12 +1202,7 @@ class _ClsHead(torch.autograd.Function):
         r_w2, r_b2 = g_w2.done(), g_b2.done()
         _C.colsum(dpre, g_b1.buf)
         r_b1 = g_b1.done()
-        if _C.gemm2_supported(1, 1, 7, H, H, B):
-            gemm_wgrad_(g_w1, dpre, x)
-        elif B < 64:
-            _C.small_wgrad(dpre, x, g_w1.buf.view(H, H))
-        else:
-            _wgrad_(g_w1, dpre, x)
+        _dense_wgrad_(g_w1, dpre, x, bf16_only=False, small_rows=True)
         r_w1 = g_w1.done()
         dh = None
         if ctx.needs_input_grad[0]:
@@ -1213,7 +1210,7 @@ class _ClsHead(torch.autograd.Function):
             _C.memset0(dh)
             dst = dh.reshape(B, S * H)[:, :H]  # the [CLS] rows of dh (row stride S*H)
             if p_in > 0:
-                dx = gemm_dgrad(dpre, w1) if _nt_ok(B, H, H, EPI_STORE) else torch.mm(dpre, w1)
+                dx = _dense_dgrad(dpre, w1, bf16_only=False)
                 _C.dropout(dx, dx, p_in, _s64(seed_in))
                 dst.copy_(dx)
             elif _C.gemm2_supported(0, 1, EPI_STORE, B, H, H):

@@ -140,7 +140,7 @@ def _seg_ok(la: int, lb: int, M: int, N: int, Kseg: int) -> bool:
 
 
 def _nt_ok(M: int, N: int, K: int) -> bool:
-    return N % 256 == 0 and (3 * K) % 64 == 0 and K % 4 == 0 and _C.gemm2_supported(0, 0, 7, M, N, 3 * K)
+    return N % 256 == 0 and (3 * K) % 64 == 0 and K % 4 == 0 and _C.gemm2_supported(0, 0, hip.EPI_F32_SLAB, M, N, 3 * K)
 
 
 def mm_nt(x: torch.Tensor, w: torch.Tensor, xs=None) -> torch.Tensor:
@@ -176,7 +176,7 @@ def mm_dgrad(dy: torch.Tensor, w: torch.Tensor, dys: Optional[torch.Tensor] = No
         return dx
     if acc is not None:
         return acc.add_(mm_dgrad(dy, w, dys))
-    if not (K % 256 == 0 and (3 * N) % 64 == 0 and N % 4 == 0 and _C.gemm2_supported(0, 1, 7, M, K, 3 * N)):
+    if not (K % 256 == 0 and (3 * N) % 64 == 0 and N % 4 == 0 and _C.gemm2_supported(0, 1, hip.EPI_F32_SLAB, M, K, 3 * N)):
         return dy @ w
     dx = torch.empty((M, K), dtype=torch.float32, device=dy.device)
     _C.gemm2_f32nt(dys if dys is not None else _split(dy, PAT_A), _split(w, PAT_B, rows=True), dx, 1)
@@ -195,14 +195,13 @@ def wgrad_(g: _Grad, dy: torch.Tensor, x: torch.Tensor, dys=None, xs=None) -> No
         _C.gemm2_seg([dh, dh, dl], [xh, xl, xh], g.buf, 1, 1)
         return
     Tp = -(-T // 64) * 64
-    if not (N % 8 == 0 and K % 256 == 0 and N % 4 == 0 and K % 4 == 0 and _C.gemm2_supported(1, 1, 7, N, K, 3 * Tp)):
+    if not (N % 8 == 0 and K % 256 == 0 and N % 4 == 0 and K % 4 == 0 and hip._tt_ok(N, K, 3 * Tp)):
         g.buf.add_(dy.t() @ x)
         return
     a = dys if dys is not None else _split(dy, PAT_A, rows=True, pad_rows=64)
     b = _split(x, PAT_B, rows=True, pad_rows=64)
-    sp = _C.gemm2_splits(N, K, 3 * Tp)
-    ws = hip._workspace(sp * N * K, dy.device)
-    _C.gemm2(a, b, g.buf, 1, 1, 7, None, None, None, 0.0, 0, sp, ws, None)
+    _, sp, ws = _C.gemm2_wgrad_plan(N, K, 3 * Tp)
+    _C.gemm2(a, b, g.buf, 1, 1, hip.EPI_F32_SLAB, None, None, None, 0.0, 0, sp, hip._workspace(ws, dy.device), None)
 
 
 def _colsum_(g: _Grad, x: torch.Tensor) -> None:
