@@ -258,8 +258,28 @@ void embed_bwd(torch::Tensor dout, torch::Tensor ids, torch::Tensor pos_ids, c10
                bool pos_is_arange, double p, int64_t seed) {
   check_bf16(dout, "dout");
   check_f32(gword, "gword"); check_f32(gpos, "gpos"); check_f32(ggamma, "ggamma"); check_f32(gbeta, "gbeta");
+  TORCH_CHECK(ids.scalar_type() == torch::kInt64 && pos_ids.scalar_type() == torch::kInt64, "ids must be int64");
+  TORCH_CHECK(ids.is_contiguous() && pos_ids.is_contiguous(), "ids contiguous");
+  check_bf16(word, "word"); check_bf16(pos, "pos"); check_bf16(gamma, "gamma");
+  check_f32(mean, "mean"); check_f32(rstd, "rstd");
+  TORCH_CHECK(word.dim() == 2 && pos.dim() == 2 && pos.size(1) == word.size(1), "embed_bwd tables");
   const int H = (int)word.size(1);
-  TORCH_CHECK(ids.numel() == B * S && dout.numel() == B * S * H, "embed_bwd shapes");
+  // as embed_fwd: the kernels read 4-column groups and the launcher has no instantiation above 1024
+  TORCH_CHECK(H % 4 == 0 && H <= 1024, "embed_bwd: H must be a multiple of 4 and <= 1024");
+  TORCH_CHECK(B > 0 && S > 0 && ids.numel() == B * S && pos_ids.numel() == B * S && dout.numel() == B * S * H,
+              "embed_bwd shapes");
+  TORCH_CHECK(mean.numel() == B * S && rstd.numel() == B * S, "embed_bwd: mean / rstd hold one value per token");
+  TORCH_CHECK(gamma.numel() == H && ggamma.numel() == H && gbeta.numel() == H, "embed_bwd: gamma / ggamma / gbeta width");
+  TORCH_CHECK(type.has_value() == type_ids.has_value(), "type table and ids go together");
+  if (type.has_value()) {
+    check_bf16(*type, "type");
+    TORCH_CHECK(type_ids->scalar_type() == torch::kInt64 && type_ids->is_contiguous() && type_ids->numel() == B * S,
+                "type ids");
+    TORCH_CHECK(type->dim() == 2 && type->size(1) == H, "type table width");
+    if (gtype.has_value()) { check_f32(*gtype, "gtype"); TORCH_CHECK(gtype->numel() == type->numel(), "gtype shape"); }
+  } else {
+    TORCH_CHECK(!gtype.has_value(), "gtype without a type table");
+  }
   TORCH_CHECK(gword.numel() == word.numel() && gpos.numel() == pos.numel(), "grad table shapes");
   hsd::launch_embed_bwd(CBF(dout), ids.data_ptr<int64_t>(), pos_ids.data_ptr<int64_t>(), OPT_I64(type_ids),
                         CBF(word), CBF(pos), type.has_value() ? CBF(*type) : nullptr, CBF(gamma),

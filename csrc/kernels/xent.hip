@@ -62,6 +62,8 @@ __global__ __launch_bounds__(256) void xent_kernel(const void* __restrict__ logi
 #pragma unroll
     for (int k = 1; k < VEC; ++k) cm = fmaxf(cm, v[k]);
     const float nm = fmaxf(m, cm);
+    // nothing but -inf so far (a masked-out prefix): s stays 0; -inf - -inf below would turn it into NaN for good
+    if (nm == -INFINITY) return;
     s = s * __expf(m - nm);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
@@ -86,6 +88,7 @@ __global__ __launch_bounds__(256) void xent_kernel(const void* __restrict__ logi
   for (int j = Vv + lane; j < V; j += 64) {
     const float v = ld1<kBF16>(logits, base + j);
     const float nm = fmaxf(m, v);
+    if (nm == -INFINITY) continue;  // as in consume()
     s = s * __expf(m - nm) + __expf(v - nm);
     m = nm;
     if (v > best || (v == best && j < besti)) { best = v; besti = j; }
