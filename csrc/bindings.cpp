@@ -127,6 +127,110 @@ void grad_clip_finalize(torch::Tensor partials, int64_t nparts, double gscale, d
                                  out.data_ptr<float>(), cur_stream());
 }
 
+// ---- fused LAMB (kernels/lamb.hip, optim/lamb.py) ------------------------------------------------------------------
+// The tile and segment tables of a flat buffer of `numel` elements, built and checked ONCE on the host from the
+// segments' 64-aligned spans and uploaded to the device, where they stay put (captured graphs replay launches that
+// read them). Every tile lies inside [0, numel) by construction; lamb_step then only has to compare buffer sizes.
+struct LambPlan {
+  int64_t numel = 0, tile = 0;
+  std::vector<int64_t> first_tile;  // [nsegs + 1]
+  torch::Tensor tiles, segs;        // device int64 [ntiles, 3], [nsegs, 3]
+  std::vector<int64_t> host_tiles;
+
+  LambPlan(std::vector<int64_t> offsets, std::vector<int64_t> spans, std::vector<int64_t> adapt, int64_t numel_,
+           torch::Tensor like) {
+    CHECK_CUDA(like);
+    TORCH_CHECK(offsets.size() == spans.size() && offsets.size() == adapt.size() && !offsets.empty(),
+                "LambPlan: offsets, spans, adapt of one non-zero length");
+    TORCH_CHECK(numel_ > 0 && numel_ < (int64_t(1) << 40), "LambPlan: numel");
+    numel = numel_;
+    tile = hsd::lamb_tile();
+    std::vector<int64_t> hs;
+    int64_t end = 0;
+    first_tile.push_back(0);
+    for (size_t s = 0; s < offsets.size(); ++s) {
+      const int64_t off = offsets[s], span = spans[s];
+      TORCH_CHECK(off % 64 == 0 && span > 0 && span % 64 == 0, "LambPlan: segment ", s, " [", off, ", +", span,
+                  ") is not a non-empty 64-aligned span");
+      TORCH_CHECK(off >= end && span <= numel && off <= numel - span, "LambPlan: segment ", s, " [", off, ", ",
+                  off + span, ") overlaps its predecessor or lies outside a buffer of ", numel);
+      end = off + span;
+      const int64_t t0 = (int64_t)host_tiles.size() / 3;
+      for (int64_t a = 0; a < span; a += tile) {
+        host_tiles.push_back(off + a);
+        host_tiles.push_back(std::min(tile, span - a));
+        host_tiles.push_back((int64_t)s);
+      }
+      const int64_t t1 = (int64_t)host_tiles.size() / 3;
+      hs.push_back(t0);
+      hs.push_back(t1 - t0);
+      hs.push_back(adapt[s] ? 1 : 0);
+      first_tile.push_back(t1);
+    }
+    auto opt = torch::TensorOptions().dtype(torch::kInt64);
+    tiles = torch::from_blob(host_tiles.data(), {first_tile.back(), 3}, opt).clone().to(like.device());
+    segs = torch::from_blob(hs.data(), {(int64_t)offsets.size(), 3}, opt).clone().to(like.device());
+  }
+  int64_t nsegs() const { return (int64_t)first_tile.size() - 1; }
+  int64_t ntiles() const { return first_tile.back(); }
+};
+
+// LAMB on segments [seg0, seg0 + nsegs) of the WHOLE flat buffers p, m, v, g (and out / out_lo), each of plan.numel
+// elements: partials [>= 2 x tiles] and ratio [>= 3 x segments] are indexed by global tile / segment id, so a slice
+// writes only its own slots. Out-of-range arguments raise before anything is launched.
+void lamb_step(const LambPlan& plan, int64_t seg0, int64_t nsegs, torch::Tensor p, torch::Tensor m, torch::Tensor v,
+               torch::Tensor g, c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> out_lo,
+               torch::Tensor partials, torch::Tensor ratio, double lr, double ibc1, double ibc2, double eps, double b1,
+               double b2, double gscale, double wd, c10::optional<torch::Tensor> coef,
+               c10::optional<torch::Tensor> clip, bool zero_grad) {
+  auto flat = [&](const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.device() == plan.tiles.device(), name,
+                ": contiguous tensor on the plan's GPU");
+    TORCH_CHECK(t.numel() == plan.numel, name, ": ", t.numel(), " elements, the plan's buffer has ", plan.numel);
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must start 16-B aligned");
+  };
+  flat(p, "p"); flat(m, "m"); flat(v, "v"); flat(g, "g");
+  CHECK_DTYPE(p, torch::kFloat32); CHECK_DTYPE(m, torch::kFloat32); CHECK_DTYPE(v, torch::kFloat32);
+  const bool gbf = g.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(gbf || g.scalar_type() == torch::kFloat32, "grad must be fp32 or bf16");
+  TORCH_CHECK(seg0 >= 0 && nsegs >= 0 && seg0 <= plan.nsegs() && nsegs <= plan.nsegs() - seg0, "segments [", seg0,
+              ", ", seg0 + nsegs, ") outside the plan's ", plan.nsegs());
+  hsd::bf16_t* o = nullptr;
+  if (out.has_value()) {
+    flat(*out, "out"); CHECK_DTYPE(*out, torch::kBFloat16);
+    o = BF(*out);
+  }
+  hsd::bf16_t* lo = nullptr;
+  if (out_lo.has_value()) {
+    TORCH_CHECK(o != nullptr, "out_lo needs out");
+    flat(*out_lo, "out_lo"); CHECK_DTYPE(*out_lo, torch::kBFloat16);
+    lo = BF(*out_lo);
+  }
+  CHECK_CUDA(partials); CHECK_CONTIG(partials); CHECK_DTYPE(partials, torch::kFloat32);
+  CHECK_CUDA(ratio); CHECK_CONTIG(ratio); CHECK_DTYPE(ratio, torch::kFloat32);
+  TORCH_CHECK(partials.numel() >= 2 * plan.ntiles(), "partials: ", partials.numel(), " slots, 2 x ", plan.ntiles(),
+              " tiles needed");
+  TORCH_CHECK(ratio.numel() >= 3 * plan.nsegs(), "ratio: ", ratio.numel(), " slots, 3 x ", plan.nsegs(),
+              " segments needed");
+  const float* dcoef = nullptr;  // fp32 [8] on the device: (lr, 1/(1-b1^t), 1/(1-b2^t), eps, grad_scale, wd, -, -)
+  if (coef.has_value()) {
+    CHECK_CUDA(*coef); CHECK_CONTIG(*coef); CHECK_DTYPE(*coef, torch::kFloat32);
+    TORCH_CHECK(coef->numel() >= 8, "coef: fp32 [8]");
+    dcoef = coef->data_ptr<float>();
+  }
+  const float* dclip = nullptr;  // fp32 [1] on the device: the step's global-norm clip coefficient
+  if (clip.has_value()) {
+    CHECK_CUDA(*clip); CHECK_DTYPE(*clip, torch::kFloat32);
+    TORCH_CHECK(clip->numel() >= 1, "clip: fp32 [1]");
+    dclip = clip->data_ptr<float>();
+  }
+  const int64_t t0 = plan.first_tile[seg0], t1 = plan.first_tile[seg0 + nsegs];
+  hsd::launch_lamb(p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), g.data_ptr(), gbf, o, lo,
+                   plan.tiles.data_ptr<int64_t>(), plan.segs.data_ptr<int64_t>(), t0, t1 - t0, seg0, nsegs,
+                   partials.data_ptr<float>(), ratio.data_ptr<float>(), (float)lr, (float)ibc1, (float)ibc2, (float)eps,
+                   (float)b1, (float)b2, (float)gscale, (float)wd, dcoef, dclip, zero_grad, cur_stream());
+}
+
 #define OPT_BF(o) ((o).has_value() ? reinterpret_cast<hsd::bf16_t*>((o)->data_ptr()) : nullptr)
 #define OPT_F(o) ((o).has_value() ? (o)->data_ptr<float>() : nullptr)
 #define OPT_I64(o) ((o).has_value() ? (o)->data_ptr<int64_t>() : nullptr)
@@ -1074,6 +1178,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_sumsq_blocks", [](int64_t n, bool bf16) { return (int64_t)hsd::grad_sumsq_blocks(n, bf16); });
   m.def("grad_clip_finalize", &grad_clip_finalize, py::arg("partials"), py::arg("nparts"), py::arg("gscale"),
         py::arg("max_norm"), py::arg("out"), py::arg("coef") = py::none());
+  py::class_<LambPlan>(m, "LambPlan")
+      .def(py::init<std::vector<int64_t>, std::vector<int64_t>, std::vector<int64_t>, int64_t, torch::Tensor>(),
+           py::arg("offsets"), py::arg("spans"), py::arg("adapt"), py::arg("numel"), py::arg("like"))
+      .def_readonly("numel", &LambPlan::numel)
+      .def_readonly("tile", &LambPlan::tile)
+      .def_readonly("first_tile", &LambPlan::first_tile)
+      .def_readonly("tiles", &LambPlan::tiles)
+      .def_readonly("segs", &LambPlan::segs)
+      .def_property_readonly("nsegs", &LambPlan::nsegs)
+      .def_property_readonly("ntiles", &LambPlan::ntiles);
+  m.def("lamb_tile", []() { return (int64_t)hsd::lamb_tile(); });
+  m.def("lamb_step", &lamb_step, py::arg("plan"), py::arg("seg0"), py::arg("nsegs"), py::arg("p"), py::arg("m"),
+        py::arg("v"), py::arg("g"), py::arg("out"), py::arg("out_lo"), py::arg("partials"), py::arg("ratio"),
+        py::arg("lr"), py::arg("ibc1"), py::arg("ibc2"), py::arg("eps"), py::arg("b1"), py::arg("b2"),
+        py::arg("gscale"), py::arg("wd"), py::arg("coef") = py::none(), py::arg("clip") = py::none(),
+        py::arg("zero_grad") = false);
   m.def("ln_fwd_q8", &ln_fwd_q8);
   m.def("stream_wait", &stream_wait);
   m.def("gemm2_on", &gemm2_on);

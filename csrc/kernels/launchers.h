@@ -25,6 +25,18 @@ void launch_grad_sumsq(const void* g, bool grad_bf16, int64_t n, float* partials
 void launch_grad_clip_finalize(const float* partials, int64_t nparts, float gscale, const float* coef, float max_norm,
                                float* out, hipStream_t stream);
 
+// lamb.hip: fused LAMB (TF Addons' math) on segments [seg0, seg0 + nsegs) of the flat store = tiles
+// [tile0, tile0 + ntiles) of the host-built tables tiles [*, 3] = (start, length, segment) and segs [*, 3] = (first
+// tile, tiles, adapt / decay flag); a tile is at most lamb_tile() elements and never straddles two segments. Three
+// launches: moments + per-tile (Σw², Σu²) into partials[2 tile ...], per-segment (r, Σw², Σu²) into ratio[3 seg ...],
+// then the weight update (with the bf16 copy, or the hi / lo halves). coef: fp32 [8] on the device (lr, 1/(1-b1ᵗ),
+// 1/(1-b2ᵗ), eps, grad_scale, wd, -, -) overriding the scalars; clip: fp32 [1] multiplied into grad_scale.
+int lamb_tile();
+void launch_lamb(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* out_bf16, bf16_t* out_lo,
+                 const int64_t* tiles, const int64_t* segs, int64_t tile0, int64_t ntiles, int64_t seg0, int64_t nsegs,
+                 float* partials, float* ratio, float lr, float ibc1, float ibc2, float eps, float b1, float b2,
+                 float gscale, float wd, const float* coef, const float* clip, bool zero_grad, hipStream_t stream);
+
 }  // namespace hsd
 
 namespace hsd {

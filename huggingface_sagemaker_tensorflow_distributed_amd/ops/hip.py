@@ -293,6 +293,30 @@ def grad_clip_finalize(partials, nparts: int, gscale: float, max_norm: float, ou
     _C.grad_clip_finalize(partials, int(nparts), float(gscale), float(max_norm), out, coef)
 
 
+def lamb_tile() -> int:
+    """Elements per tile of the fused LAMB: a segment's 64-aligned span is cut into tiles of this size."""
+    return int(_C.lamb_tile())
+
+
+def lamb_plan(offsets, spans, adapt, numel: int, like):
+    """The tile / segment tables of the fused LAMB for a flat buffer of ``numel`` elements, checked on the host and
+    uploaded to ``like``'s device: segment ``i`` is the 64-aligned span ``[offsets[i], offsets[i] + spans[i])``;
+    ``adapt[i]`` = it takes weight decay and the trust ratio. Raises ``RuntimeError`` for a span outside the buffer."""
+    return _C.LambPlan([int(o) for o in offsets], [int(s) for s in spans], [int(bool(a)) for a in adapt], int(numel),
+                       like)
+
+
+def lamb_step(plan, seg0, nsegs, p, m, v, g, out, out_lo, partials, ratio, lr, ibc1, ibc2, eps, b1, b2, gscale, wd,
+              coef=None, clip=None, zero_grad=False):
+    """Fused LAMB on segments ``[seg0, seg0 + nsegs)`` of the whole flat buffers (three launches on the current
+    stream, nothing returns to the host). ``partials``: fp32 ``[2 x plan.ntiles]`` (Σw², Σu² per tile); ``ratio``: fp32
+    ``[3 x plan.nsegs]`` (r, Σw², Σu² per segment). ``ibc1`` / ``ibc2`` = ``1 / (1 - βᵗ)``. ``coef``: optional fp32 [8]
+    device tensor ``(lr, ibc1, ibc2, eps, grad_scale, wd, -, -)`` read instead of the host scalars (captured steps);
+    ``clip`` / ``out`` / ``out_lo`` / ``zero_grad`` as :func:`adam_step`."""
+    _C.lamb_step(plan, int(seg0), int(nsegs), p, m, v, g, out, out_lo, partials, ratio, float(lr), float(ibc1),
+                 float(ibc2), float(eps), float(b1), float(b2), float(gscale), float(wd), coef, clip, bool(zero_grad))
+
+
 # ------------------------------------------------------------------------------------------ linear
 class _Linear(torch.autograd.Function):
     """y = x Wᵀ + b for the task heads (pooler / classifier / MLM dense): gemm2 when the shape tiles,

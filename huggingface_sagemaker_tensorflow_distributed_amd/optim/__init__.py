@@ -1,3 +1,4 @@
 from .adam import FusedAdam
+from .lamb import FusedLamb
 
-__all__ = ["FusedAdam"]
+__all__ = ["FusedAdam", "FusedLamb"]

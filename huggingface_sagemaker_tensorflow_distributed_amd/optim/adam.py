@@ -44,6 +44,7 @@ from ..parallel.flat_params import ALIGN, FlatParamStore
 class FusedAdam:
     # overlapped steps re-quantise each slice's fp8 weights right after its update (False: one pass at the end; A/B)
     per_slice_fp8 = True
+    kind = "adam"  # what load_state_dict accepts (a state without a "kind" is Adam's)
 
     def __init__(self, store: FlatParamStore, lr: float = 1e-3, betas=(0.9, 0.999), eps: Optional[float] = None,
                  weight_decay: float = 0.0, eps_mode: str = "keras", decoupled: bool = True,
@@ -136,6 +137,11 @@ class FusedAdam:
                 "weight_decay": self.weight_decay}
 
     def load_state_dict(self, sd: dict) -> None:
+        # states of other optimizers over the same buffers (optim/lamb.py) carry their "kind"; Adam's own carry none
+        kind = sd.get("kind")
+        if kind is not None and kind != self.kind:
+            raise ValueError(f"optimizer state of kind {kind!r} cannot be loaded into {type(self).__name__} "
+                             f"(kind {self.kind!r}): resume with the --optimizer the checkpoint was written with")
         self.step_count = int(sd["step"])
         self.exp_avg.copy_(sd["exp_avg"].to(self.exp_avg.device))
         self.exp_avg_sq.copy_(sd["exp_avg_sq"].to(self.exp_avg_sq.device))

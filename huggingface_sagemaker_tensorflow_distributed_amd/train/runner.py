@@ -24,7 +24,7 @@ import torch
 from .. import data as hdata
 from .. import ops
 from ..models import from_pretrained, save_pretrained
-from ..optim import FusedAdam
+from ..optim import FusedAdam, FusedLamb
 from ..parallel.ddp import resolve_compression
 from ..parallel.flat_params import keep_transposed_weights
 from ..parallel import FlatParamStore, GradBucketer, ShardSampler, backend, broadcast_parameters
@@ -128,9 +128,16 @@ def build(args, mode: str):
                            transposed=keep_transposed_weights(rank_tokens))
     base_lr = float(args.learning_rate)
     lr = base_lr * world if mode == "train" else base_lr  # scripts/train.py:112 vs singe_node_train.py:78
-    opt = FusedAdam(store, lr=lr, eps=args.adam_epsilon, eps_mode=args.adam_eps_mode,
-                    weight_decay=args.weight_decay if args.optimizer == "adamw" else 0.0,
-                    max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0))
+    if args.optimizer == "lamb":
+        # the learning rate keeps the Horovod x world rule above; LAMB always uses its bias-corrected form
+        if args.adam_eps_mode != "keras":
+            logger.info("--adam_eps_mode %s does not apply to --optimizer lamb (ignored)", args.adam_eps_mode)
+        opt = FusedLamb(store, lr=lr, eps=args.adam_epsilon, weight_decay=args.weight_decay,
+                        max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0))
+    else:
+        opt = FusedAdam(store, lr=lr, eps=args.adam_epsilon, eps_mode=args.adam_eps_mode,
+                        weight_decay=args.weight_decay if args.optimizer == "adamw" else 0.0,
+                        max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0))
     batch_plan = None
     if args.train_batch_size == "auto":
         # sized on the device before any readiness hook / bucketer exists (the probes are plain fwd + bwd)

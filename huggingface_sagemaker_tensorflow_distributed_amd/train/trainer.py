@@ -420,6 +420,9 @@ class Trainer:
                     # --max_grad_norm: the last step's global gradient norm (a device read, at log time only)
                     gn = (" - grad_norm=%.4g" % self.optimizer.grad_norm()
                           if getattr(self.optimizer, "max_grad_norm", 0.0) > 0.0 else "")
+                    # --optimizer lamb: the last step's trust ratios over the adapted parameters (a device read too)
+                    if hasattr(self.optimizer, "trust_ratio_summary"):
+                        gn += " - trust_ratio=%.3g/%.3g/%.3g" % self.optimizer.trust_ratio_summary()
                     logger.info("epoch %d step %d/%d - loss: %.4f - sparse_categorical_accuracy: %.4f - %.1f ms/step%s",
                                 epoch + 1, step + 1, nsteps, r["loss"], r["sparse_categorical_accuracy"],
                                 (time.time() - t0) * 1e3 / (step + 1), gn)

@@ -88,7 +88,10 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
                         "for bf16 / fp8 runs on GPUs at N >= 2 (the casts cost less than the transfer time they save "
                         "over xGMI, parallel/ddp.py resolve_compression), fp32 for --dtype fp32; none = fp32 always "
                         "(the reference's Horovod all-reduce)")
-    g.add_argument("--optimizer", choices=["adam", "adamw"], default="adam")
+    g.add_argument("--optimizer", choices=["adam", "adamw", "lamb"], default="adam",
+                   help="adam (reference) | adamw (decoupled --weight_decay) | lamb (TF Addons' LAMB for large batches: "
+                        "per-parameter trust ratio ||w|| / ||u||, biases and LayerNorm excluded from decay and "
+                        "adaptation, --adam_epsilon defaults to 1e-6, --weight_decay applies as given)")
     g.add_argument("--weight_decay", type=float, default=0.0)
     g.add_argument("--adam_eps_mode", choices=["keras", "torch"], default="keras")
     g.add_argument("--adam_epsilon", type=float, default=None)
