@@ -465,6 +465,52 @@ void attn_bwd(torch::Tensor qkv, c10::optional<torch::Tensor> mask, torch::Tenso
                        keep_mask_ptr(kmask, B, S, heads), delta_ready);
 }
 
+// padding-free attention over packed sequences (attention_varlen.hip): qkv [T, 3H], cu_seqlens int32 [B+1] on the
+// device, lse2 [heads, T]; rows from cu_seqlens[B] on are dead and come back as zeros
+static const int* check_varlen(const torch::Tensor& qkv, const torch::Tensor& cu, int64_t B, int64_t max_seqlen,
+                               int64_t heads) {
+  check_bf16(qkv, "qkv");
+  CHECK_CUDA(cu); CHECK_CONTIG(cu); CHECK_DTYPE(cu, torch::kInt32);
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == 3 * heads * 64, "attention requires qkv [T, 3H] with head_dim 64");
+  TORCH_CHECK(B >= 1 && cu.numel() == B + 1, "cu_seqlens holds B + 1 offsets");
+  TORCH_CHECK(max_seqlen >= 1 && qkv.size(0) >= 1 && B * heads <= 65535 && qkv.size(0) * heads < (int64_t(1) << 31),
+              "attn_varlen sizes");
+#ifdef HSD_DEBUG
+  // the kernels clamp these offsets into [0, T]; a batch that needs the clamp is a packer bug
+  auto h = cu.cpu();
+  const int32_t* c = h.data_ptr<int32_t>();
+  TORCH_CHECK(c[0] == 0, "HSD_DEBUG: cu_seqlens[0] must be 0");
+  for (int64_t b = 0; b < B; ++b)
+    TORCH_CHECK(c[b + 1] > c[b] && c[b + 1] - c[b] <= max_seqlen,
+                "HSD_DEBUG: cu_seqlens must rise by 1..max_seqlen per sequence (sequence ", b, ")");
+  TORCH_CHECK(c[B] <= qkv.size(0), "HSD_DEBUG: cu_seqlens[B] exceeds the packed row count");
+#endif
+  return cu.data_ptr<int32_t>();
+}
+
+void attn_varlen_fwd(torch::Tensor qkv, torch::Tensor cu_seqlens, torch::Tensor out, torch::Tensor lse2, int64_t B,
+                     int64_t max_seqlen, int64_t heads, double p, int64_t seed) {
+  const int* cu = check_varlen(qkv, cu_seqlens, B, max_seqlen, heads);
+  check_bf16(out, "out"); check_f32(lse2, "lse2");
+  const int64_t T = qkv.size(0);
+  TORCH_CHECK(out.numel() == T * heads * 64 && lse2.numel() == heads * T, "attn_varlen_fwd shapes");
+  hsd::launch_attn_varlen_fwd(CBF(qkv), cu, BF(out), lse2.data_ptr<float>(), (int)T, (int)B, (int)max_seqlen,
+                              (int)heads, p, (uint64_t)seed, cur_stream());
+}
+
+void attn_varlen_bwd(torch::Tensor qkv, torch::Tensor cu_seqlens, torch::Tensor o, torch::Tensor dout,
+                     torch::Tensor lse2, torch::Tensor dqkv, int64_t B, int64_t max_seqlen, int64_t heads, double p,
+                     int64_t seed, c10::optional<torch::Tensor> dbias) {
+  const int* cu = check_varlen(qkv, cu_seqlens, B, max_seqlen, heads);
+  check_bf16(o, "o"); check_bf16(dout, "dout"); check_bf16(dqkv, "dqkv"); check_f32(lse2, "lse2");
+  const int64_t T = qkv.size(0);
+  TORCH_CHECK(dqkv.numel() == qkv.numel() && o.numel() == T * heads * 64 && dout.numel() == o.numel() &&
+                  lse2.numel() == heads * T, "attn_varlen_bwd shapes");
+  if (dbias.has_value()) { check_f32(*dbias, "dbias"); TORCH_CHECK(dbias->numel() == 3 * heads * 64, "dbias shape"); }
+  hsd::launch_attn_varlen_bwd(CBF(qkv), cu, CBF(o), CBF(dout), lse2.data_ptr<float>(), BF(dqkv), OPT_F(dbias), (int)T,
+                              (int)B, (int)max_seqlen, (int)heads, p, (uint64_t)seed, cur_stream());
+}
+
 // attention + fp8 copy of its output (forward: e4m3 of the context; backward: dqkv in format qfmt), S > 128 streaming
 // kernels only (attn_q8_supported); amax_in / sinv / amax_track: fp32 [1] delayed-scaling site slots
 static void check_q8(const torch::Tensor& q8, int64_t numel, const torch::Tensor& a, const torch::Tensor& s,
@@ -1276,6 +1322,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("mask"), py::arg("o"), py::arg("dout"), py::arg("lse2"),
         py::arg("dqkv"), py::arg("dq_acc"), py::arg("B"), py::arg("S"), py::arg("heads"), py::arg("p"), py::arg("seed"),
         py::arg("dbias") = py::none(), py::arg("kmask") = py::none(), py::arg("delta_ready") = false);
+  m.def("attn_varlen_fwd", &attn_varlen_fwd, py::arg("qkv"), py::arg("cu_seqlens"), py::arg("out"), py::arg("lse2"),
+        py::arg("B"), py::arg("max_seqlen"), py::arg("heads"), py::arg("p"), py::arg("seed"));
+  m.def("attn_varlen_bwd", &attn_varlen_bwd, py::arg("qkv"), py::arg("cu_seqlens"), py::arg("o"), py::arg("dout"),
+        py::arg("lse2"), py::arg("dqkv"), py::arg("B"), py::arg("max_seqlen"), py::arg("heads"), py::arg("p"),
+        py::arg("seed"), py::arg("dbias") = py::none());
   m.def("gemm", &gemm);
   m.def("gemm2", &gemm2, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("la"), py::arg("lb"), py::arg("epi"),
         py::arg("bias"), py::arg("aux"), py::arg("C2"), py::arg("p"), py::arg("seed"), py::arg("splits"), py::arg("ws"),

@@ -112,6 +112,14 @@ void launch_attnS_bwd_q8(const bf16_t* qkv, const float* mask, const bf16_t* o, 
 void launch_attn_bwd(const bf16_t* qkv, const float* mask, const bf16_t* o, const bf16_t* dout, const float* lse2,
                      bf16_t* dqkv, float* dq_acc, float* dbias, int B, int S, int heads, double p, uint64_t seed,
                      hipStream_t st, const uint32_t* kmask = nullptr, bool delta_ready = false);
+// attention_varlen.hip: padding-free attention over a packed qkv [T, 3H]; sequence b is rows cu_seqlens[b] ..
+// cu_seqlens[b+1]-1 (device int32 [B+1]), rows from cu_seqlens[B] on are dead (written as zeros); lse2 is [heads, T].
+// The backward writes every dqkv element once (no atomics) and adds the column sums of dqkv into dbias when given.
+void launch_attn_varlen_fwd(const bf16_t* qkv, const int* cu_seqlens, bf16_t* out, float* lse2, int T, int B,
+                            int max_seqlen, int heads, double p, uint64_t seed, hipStream_t st);
+void launch_attn_varlen_bwd(const bf16_t* qkv, const int* cu_seqlens, const bf16_t* o, const bf16_t* dout,
+                            const float* lse2, bf16_t* dqkv, float* dbias, int T, int B, int max_seqlen, int heads,
+                            double p, uint64_t seed, hipStream_t st);
 }  // namespace hsd
 
 namespace hsd {

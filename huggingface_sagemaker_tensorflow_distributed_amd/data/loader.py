@@ -16,6 +16,7 @@ import torch
 
 from ..parallel.sampler import ShardSampler
 from .datasets import ArrayDataset
+from .packing import pack_batch
 
 
 class _Failure:
@@ -26,7 +27,13 @@ class _Failure:
 
 
 class BatchLoader:
-    def __init__(self, ds: ArrayDataset, sampler: ShardSampler, device: torch.device, prefetch: int = 3):
+    def __init__(self, ds: ArrayDataset, sampler: ShardSampler, device: torch.device, prefetch: int = 3,
+                 pack: bool = False, pack_rule: Optional[Dict[str, int]] = None):
+        """``pack``: padding-free batches (data/packing.py; ``pack_rule`` = its pad_id / pos_base / pad_pos, see
+        ``packing.position_rule``): the prefetch thread packs each batch into one ``[1, T]`` row buffer with
+        ``position_ids`` and ``cu_seqlens``; ``max_seqlen`` and ``real_tokens`` stay host ints, like ``num_valid``."""
+        self.pack = bool(pack)
+        self.pack_rule = dict(pack_rule or {"pad_id": 0, "pos_base": 0, "pad_pos": 0})
         self.ds = ds
         self.sampler = sampler
         self.device = torch.device(device)
@@ -45,13 +52,20 @@ class BatchLoader:
         labels = self.ds.labels[ix].astype(np.int64)
         if pad.any():
             labels[pad] = -100  # ignored by the loss and by the metric meter
-        b = {
-            "input_ids": torch.from_numpy(self.ds.input_ids[ix].astype(np.int64)),
-            "attention_mask": torch.from_numpy(self.ds.attention_mask[ix].astype(np.int64)),
-            "labels": torch.from_numpy(labels),
-        }
+        ints = {}
+        if self.pack:
+            pk = pack_batch(self.ds.input_ids[ix], self.ds.attention_mask[ix], labels, **self.pack_rule)
+            ints = {k: pk.pop(k) for k in ("max_seqlen", "real_tokens")}
+            b = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in pk.items()}
+        else:
+            b = {
+                "input_ids": torch.from_numpy(self.ds.input_ids[ix].astype(np.int64)),
+                "attention_mask": torch.from_numpy(self.ds.attention_mask[ix].astype(np.int64)),
+                "labels": torch.from_numpy(labels),
+            }
         if self._cuda:
             b = {k: v.pin_memory() for k, v in b.items()}
+        b.update(ints)
         if pad.any():
             b["num_valid"] = int((~pad).sum())  # host int: lets evaluate skip an all-padding batch without a sync
         return b

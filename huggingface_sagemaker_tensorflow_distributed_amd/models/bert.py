@@ -54,16 +54,18 @@ class Embeddings(nn.Module):
         return t
 
     def forward(self, input_ids, token_type_ids, rng: DropoutSeeds, training: bool,
-                q8_for: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``q8_for``: the first encoder layer's QKV weight (fp8 path: the embedding kernel writes its fp8 operand)."""
+                q8_for: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``q8_for``: the first encoder layer's QKV weight (fp8 path: the embedding kernel writes its fp8 operand).
+        ``position_ids``: given for packed batches (data/packing.py), where a row's position is not its column."""
         c = self.cfg
-        pos = self.position_ids(input_ids)
+        pos = self.position_ids(input_ids) if position_ids is None else position_ids
         if token_type_ids is None and self.token_type_embeddings is not None:
             token_type_ids = self._cached("type0", input_ids, lambda: torch.zeros_like(input_ids))
         p = c.hidden_dropout_prob if training else 0.0
         return ops.embed_ln(input_ids, pos, token_type_ids, self.word_embeddings, self.position_embeddings,
                             self.token_type_embeddings, self.ln_weight, self.ln_bias, c.layer_norm_eps,
-                            p, rng.next() if p else 0, pos_is_arange=c.model_type != "roberta", q8_for=q8_for)
+                            p, rng.next() if p else 0,
+                            pos_is_arange=c.model_type != "roberta" and position_ids is None, q8_for=q8_for)
 
 
 class Encoder(nn.Module):
@@ -73,7 +75,13 @@ class Encoder(nn.Module):
         self.embeddings = Embeddings(cfg)
         self.layers = nn.ModuleList([EncoderLayer(cfg) for _ in range(cfg.num_hidden_layers)])
 
-    def forward(self, input_ids, attention_mask, token_type_ids, rng, training) -> torch.Tensor:
+    def forward(self, input_ids, attention_mask, token_type_ids, rng, training, *, cu_seqlens=None, max_seqlen=None,
+                position_ids=None) -> torch.Tensor:
+        """Padded: ``input_ids [B, S]`` -> ``[B, S, H]``. Packed (``cu_seqlens`` given, data/packing.py):
+        ``input_ids`` / ``position_ids`` ``[1, T]``, no attention mask -> ``[T, H]``."""
+        if cu_seqlens is not None:
+            return self._forward_packed(input_ids, attention_mask, token_type_ids, rng, training, cu_seqlens,
+                                        max_seqlen, position_ids)
         B, S = input_ids.shape
         first_qkv = self.layers[0].qkv_weight if len(self.layers) else None
         h = self.embeddings(input_ids, token_type_ids, rng, training, q8_for=first_qkv).view(B * S, -1)
@@ -82,6 +90,29 @@ class Encoder(nn.Module):
         for i, layer in enumerate(self.layers):
             h = layer(h, mask_bias, B, S, rng, training, self.layers[i + 1].qkv_weight if i + 1 < n else None)
         return h.view(B, S, -1)
+
+    def _forward_packed(self, input_ids, attention_mask, token_type_ids, rng, training, cu_seqlens, max_seqlen,
+                        position_ids) -> torch.Tensor:
+        if attention_mask is not None:
+            raise ValueError("a packed batch (cu_seqlens) takes no attention_mask: the offsets say which keys a "
+                             "query sees")
+        if position_ids is None or not max_seqlen:
+            raise ValueError("a packed batch needs position_ids and max_seqlen (data/packing.py pack_batch)")
+        if input_ids.dim() != 2 or input_ids.shape[0] != 1 or position_ids.shape != input_ids.shape:
+            raise ValueError(f"a packed batch holds input_ids / position_ids [1, T], got {tuple(input_ids.shape)} / "
+                             f"{tuple(position_ids.shape)}")
+        T = input_ids.shape[1]
+        cu = cu_seqlens.to(torch.int32)
+        # the embedding kernels are row-wise with explicit position ids, so any [rows, cols] view of the T tokens
+        # computes the same thing; 256 columns keeps their backward's launch geometry (one block column per position
+        # of a chunk of rows) at the size it was tuned for instead of T one-row blocks
+        cols = 256 if T % 256 == 0 else T
+        tt = token_type_ids.view(-1, cols) if token_type_ids is not None else None
+        h = self.embeddings(input_ids.view(-1, cols), tt, rng, training,
+                            position_ids=position_ids.view(-1, cols)).view(T, -1)
+        for layer in self.layers:
+            h = layer(h, None, 1, T, rng, training, None, cu_seqlens=cu, max_seqlen=int(max_seqlen))
+        return h
 
 
 def _init_(module: nn.Module, cfg: ModelConfig, generator: Optional[torch.Generator] = None) -> None:
@@ -184,10 +215,15 @@ class TransformerForSequenceClassification(_Base):
             yield "classifier.weight", "classifier_weight", None, 1
             yield "classifier.bias", "classifier_bias", None, 1
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, *, cu_seqlens=None,
+                max_seqlen=None, position_ids=None):
         c = self.cfg
         training = self.training
-        h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, training)
+        h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, training, cu_seqlens=cu_seqlens,
+                         max_seqlen=max_seqlen, position_ids=position_ids)
+        if cu_seqlens is not None:
+            # packed [T, H]: the first-token row of sequence b is row cu_seqlens[b]
+            h = h.index_select(0, cu_seqlens[:-1].long()).unsqueeze(1)  # [B, 1, H]
         # head on the [CLS] / <s> row (ops.cls_head: one fused kernel per direction after the dense GEMM on GPUs);
         # the dropout seeds are drawn in the same order as the unfused head always drew them
         if c.model_type == "bert":
@@ -250,9 +286,13 @@ class RobertaForMaskedLM(_Base):
         yield "lm_head.layer_norm.bias", "lm_ln_bias", None, 1
         yield "lm_head.bias", "lm_bias", None, 1
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, *, cu_seqlens=None,
+                max_seqlen=None, position_ids=None):
         c = self.cfg
-        h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, self.training)
+        h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, self.training, cu_seqlens=cu_seqlens,
+                         max_seqlen=max_seqlen, position_ids=position_ids)
+        if cu_seqlens is not None:
+            h = h.unsqueeze(0)  # packed [T, H] -> [1, T, H]; labels are the packed [T]
         B, S, H = h.shape
         x = h.view(B * S, H)
         wemb = self.encoder.embeddings.word_embeddings

@@ -22,7 +22,13 @@ logger = logging.getLogger(__name__)
 
 class ThroughputMeter:
     def __init__(self, out_dir: str, per_rank_batch: int, seq_len: int, warmup: int = 3, log_every: int = 50,
-                 info: Optional[Dict] = None):
+                 info: Optional[Dict] = None, packed: bool = False):
+        """``packed`` (--pack_sequences): also report ``real_tokens_per_s`` (tokens that are not padding) and
+        ``padding_fraction`` (the share of the padded batches' tokens that packing dropped), from the trainer's host
+        counters over the timed steps of this rank; the existing fields keep their meaning (``tokens_per_s`` counts
+        padded tokens)."""
+        self.packed = bool(packed)
+        self._real: List[int] = []
         self.out_dir = out_dir
         self.per_rank_batch = int(per_rank_batch)
         self.seq_len = int(seq_len)
@@ -49,6 +55,7 @@ class ThroughputMeter:
 
     def on_train_begin(self, trainer):
         self._events = []
+        self._real = []
         # per-bucket comm timeline (native RCCL engine only; other bucketers report False)
         buck = getattr(trainer, "bucketer", None)
         set_timing = getattr(buck, "set_timing", None)
@@ -56,6 +63,8 @@ class ThroughputMeter:
 
     def on_batch_end(self, trainer, step):
         self._events.append(self._stamp())
+        if self.packed:
+            self._real.append(int(getattr(trainer, "packed_real_tokens", 0)))
         n = len(self._events)
         if self.log_every and backend.rank() == 0 and n > self.warmup + 1 and n % self.log_every == 0:
             if self.cuda:
@@ -63,12 +72,21 @@ class ThroughputMeter:
             ms = self._elapsed_ms(self._events[self.warmup], self._events[-1]) / (n - 1 - self.warmup)
             rec = {"step": trainer.global_step, "ms_per_step": ms,
                    "seq_per_s_rank": self.per_rank_batch * 1e3 / ms, "time": time.time()}
+            if self.packed:
+                rec.update(self._packed_fields(ms, n - 1 - self.warmup, getattr(trainer, "grad_accum", 1), 1))
             if getattr(trainer.optimizer, "max_grad_norm", 0.0) > 0.0:
                 rec["grad_norm"] = trainer.optimizer.grad_norm()  # --max_grad_norm: read at log time only
             self._append(rec)
 
     def on_epoch_end(self, trainer, epoch, logs):
         pass
+
+    def _packed_fields(self, ms: float, timed: int, accum: int, world: int) -> Dict:
+        """Real (non-padding) tokens of this rank's timed steps, scaled to ``world`` ranks."""
+        real = self._real[-1] - self._real[self.warmup]
+        padded = self.per_rank_batch * self.seq_len * max(1, int(accum)) * timed
+        return {"real_tokens_per_s": real * world * 1e3 / (ms * timed),
+                "padding_fraction": 1.0 - real / float(max(1, padded))}
 
     def _append(self, rec: Dict) -> None:
         os.makedirs(self.out_dir, exist_ok=True)
@@ -99,6 +117,8 @@ class ThroughputMeter:
             "warmup_steps": self.warmup, "per_gpu_batch": self.per_rank_batch, "global_batch": self.per_rank_batch * world,
             "seq_len": self.seq_len, **self.info,
         }
+        if self.packed:
+            self.result.update(self._packed_fields(ms, timed, getattr(trainer, "grad_accum", 1), world))
         if comm is not None:
             self.result["comm_overlap"] = comm
         if backend.rank() == 0:

@@ -109,9 +109,18 @@ def dense_residual_ln(x, w, b, residual, ln_w, ln_b, eps, p, seed):
 
 
 def attn_block(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, batch, seq, heads, p_attn, seed_attn,
-               p_hidden, seed_hidden, q8_next=None):
+               p_hidden, seed_hidden, q8_next=None, *, cu_seqlens=None, max_seqlen=0):
     """Self-attention sub-block: ``LN(dropout(attn(h Wqkvᵀ + b) Woᵀ + bo) + h)``. ``q8_next``: the weight of the
-    GEMM that consumes the output (HIP fp8 path: the LayerNorm writes its fp8 input copy)."""
+    GEMM that consumes the output (HIP fp8 path: the LayerNorm writes its fp8 input copy).
+
+    ``cu_seqlens`` (with ``max_seqlen``): ``h`` is a packed ``[T, H]`` buffer (data/packing.py) and the block is the
+    three-op composition below around ``attention_varlen``; ``mask_bias`` / ``batch`` / ``seq`` are not read."""
+    if cu_seqlens is not None:
+        if mask_bias is not None:
+            raise ValueError("attn_block: a packed batch (cu_seqlens) takes no attention mask")
+        qkv = linear(h, qkv_w, qkv_b)
+        ctx = attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p_attn, seed_attn)
+        return dense_residual_ln(ctx, out_w, out_b, h, ln_w, ln_b, eps, p_hidden, seed_hidden)
     if _hip(h) and h.dtype == torch.bfloat16 and qkv_w.shape[0] == 3 * heads * 64 and seq % 2 == 0:
         # (an odd sequence length: the three ops below, with the reference attention -- ops/hip.py attention_ok)
         return _hipmod().attn_block(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, batch, seq, heads,
@@ -140,6 +149,14 @@ def attention(qkv, mask_bias, batch, seq, heads, p, seed):
     if _hip32(qkv):
         return _hip32mod().attention(qkv, mask_bias, batch, seq, heads, p, seed)
     return _ref.attention(qkv, mask_bias, batch, seq, heads, p, seed, p > 0)
+
+
+def attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed):
+    """Attention over packed sequences (``--pack_sequences``): bf16 GPU tensors run the varlen HIP kernels,
+    everything else the reference op."""
+    if _hip(qkv) and qkv.dtype == torch.bfloat16:
+        return _hipmod().attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed)
+    return _ref.attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed, p > 0)
 
 
 def hip_active(device) -> bool:

@@ -575,6 +575,40 @@ def attention(qkv, mask_bias, batch, seq, heads, p, seed):
     return _Attention.apply(qkv, mask_bias, batch, seq, heads, p, seed)
 
 
+class _AttentionVarlen(torch.autograd.Function):
+    """Padding-free attention over packed sequences (csrc/kernels/attention_varlen.hip)."""
+
+    @staticmethod
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, heads, p, seed):
+        qkv = qkv.contiguous()
+        T, H = qkv.shape[0], qkv.shape[-1] // 3
+        B = cu_seqlens.numel() - 1
+        out = torch.empty((T, H), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty(heads * T, dtype=torch.float32, device=qkv.device)
+        _C.attn_varlen_fwd(qkv, cu_seqlens, out, lse, B, int(max_seqlen), heads, float(p), _s64(seed))
+        ctx.save_for_backward(qkv, out, lse, cu_seqlens)
+        ctx.B, ctx.max_seqlen, ctx.heads, ctx.p, ctx.seed = B, int(max_seqlen), heads, float(p), seed
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, cu = ctx.saved_tensors
+        dqkv = torch.empty_like(qkv)
+        _C.attn_varlen_bwd(qkv, cu, out, dout.contiguous(), lse, dqkv, ctx.B, ctx.max_seqlen, ctx.heads, ctx.p,
+                           _s64(ctx.seed))
+        return dqkv, None, None, None, None, None
+
+
+def attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed):
+    """``qkv [T, 3H]`` bf16, ``cu_seqlens`` int32 [B+1] on the device (data/packing.py), head dim 64. There is no
+    other kernel behind this op: an unsupported shape is an error, not a fall-back."""
+    if qkv.dim() != 2 or qkv.shape[-1] != 3 * heads * 64:
+        raise ValueError(f"attention_varlen: qkv {tuple(qkv.shape)} is not [T, 3 * {heads} * 64] (head dim 64 only)")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.device != qkv.device:
+        raise ValueError("attention_varlen: cu_seqlens must be an int32 tensor on qkv's device")
+    return _AttentionVarlen.apply(qkv, cu_seqlens.contiguous(), max_seqlen, heads, p, seed)
+
+
 # ------------------------------------------------------------------------------------------ GEMM helpers
 EPI_STORE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_RES, EPI_DGELU, EPI_F32_ATOMIC = range(7)
 EPI_F32_SLAB, EPI_BIAS_GELU_D, EPI_MUL, EPI_STORE_RDOT = 7, 8, 9, 10  # gemm2 only

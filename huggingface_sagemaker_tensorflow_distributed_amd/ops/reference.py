@@ -86,6 +86,38 @@ def attention(qkv: torch.Tensor, mask_bias: Optional[torch.Tensor], batch: int, 
     return o.permute(0, 2, 1, 3).reshape(batch * seq, H).to(qkv.dtype)
 
 
+def attention_varlen(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int, heads: int, p: float, seed: int,
+                     training: bool) -> torch.Tensor:
+    """Self-attention over packed sequences: ``qkv [T, 3H]`` with sequence ``b`` in rows ``cu_seqlens[b] ..
+    cu_seqlens[b+1]-1`` (data/packing.py) -> ``[T, H]`` context. A query sees the keys of its own sequence only; the
+    dead rows (from ``cu_seqlens[-1]`` on) come back as zeros.
+
+    Dropout on the probabilities: head ``h``, packed row ``t``, key ``j`` within the sequence is row ``h*T + t``,
+    column ``j`` of the site (ops/rng.py)."""
+    T, H3 = qkv.shape
+    H = H3 // 3
+    d = H // heads
+    cu = [int(c) for c in cu_seqlens.tolist()]
+    keep = None
+    if training and p > 0.0:
+        keep = keep_mask(seed, (heads * T, int(max_seqlen)), p, device=qkv.device).view(heads, T, int(max_seqlen))
+    outs = []
+    for b in range(len(cu) - 1):
+        s0, s1 = cu[b], cu[b + 1]
+        L = s1 - s0
+        # the same op sequence as ``attention`` on a batch of one sequence of length L (bit-identical without dropout)
+        x = qkv[s0:s1].view(1, L, 3, heads, d).permute(2, 0, 3, 1, 4).float()  # [3,1,h,L,d]
+        s = torch.matmul(x[0], x[1].transpose(-1, -2)) * (1.0 / math.sqrt(d))
+        pr = torch.softmax(s, dim=-1)
+        if keep is not None:
+            pr = pr * keep[:, s0:s1, :L].unsqueeze(0).to(pr.dtype) * (1.0 / (1.0 - p))
+        o = torch.matmul(pr, x[2])  # [1,h,L,d]
+        outs.append(o.permute(0, 2, 1, 3).reshape(L, H).to(qkv.dtype))
+    if cu[-1] < T:
+        outs.append(qkv.new_zeros((T - cu[-1], H)))
+    return torch.cat(outs, dim=0)
+
+
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     """SparseCategoricalCrossentropy(from_logits=True), SUM_OVER_BATCH_SIZE (``scripts/train.py:118``)."""
     return F.cross_entropy(logits.float(), labels.long())

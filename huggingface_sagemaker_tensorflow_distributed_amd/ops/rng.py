@@ -17,6 +17,13 @@ viewed as ``[rows, W]``; element ``(r, c)`` belongs to column pair ``cp = c // 2
 * column ``2cp`` keeps iff ``(h & 0xFFFF) >= thr``; column ``2cp+1`` keeps iff ``(h >> 16) >= thr``;
   ``thr = round(p * 65536)``.
 
+Attention sites. Padded attention (``ops.attention``): probability element (batch ``b``, head ``h``, query ``i``,
+key ``j``) is row ``(b*heads + h)*S + i``, column ``j``. Packed attention (``ops.attention_varlen``,
+``--pack_sequences``): element (head ``h``, packed query row ``t``, key ``j`` counted within ``t``'s own sequence) is
+row ``h*T + t``, column ``j``, with ``T`` the packed row count. ``keep(r, c)`` above does not depend on the row
+width, so sequences of any (odd) length need no special case; the reference builds the mask at width
+``max_seqlen`` and slices it. The backward regenerates the bits: no keep-mask buffer.
+
 Per element pair a kernel spends one XOR, one multiply and one XOR (round 4: two lowbias32 multiplies, three
 xor-shifts and the pair arithmetic per pair). Statistics: ``tests/test_rng.py`` (keep rate over 1e8 draws, neighbour
 correlations, 2x2 block patterns), ``tools/rng_quality.py`` (the candidate screen).

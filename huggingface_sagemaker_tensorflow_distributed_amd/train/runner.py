@@ -75,7 +75,8 @@ def _provenance(args, model, rank: int, n_train: int, n_eval: int, batch_plan=No
     synthetic = args.dataset == "synthetic"
     info = {"dataset": args.dataset, "synthetic_data": synthetic, "weights": weights,
             "model_name_or_path": args.model_name_or_path, "num_train_examples": n_train,
-            "num_eval_examples": n_eval, "train_batch_size": args.train_batch_size}
+            "num_eval_examples": n_eval, "train_batch_size": args.train_batch_size,
+            "pack_sequences": bool(getattr(args, "pack_sequences", False))}
     if batch_plan is not None:
         info["auto_batch"] = batch_plan.as_dict()
     if synthetic or weights == "random-init":
@@ -99,6 +100,10 @@ def build(args, mode: str):
     on_gpu = dev.type == "cuda"
     dtype_name = args.dtype or ("bf16" if on_gpu else "fp32")
     compute_dtype = _DTYPES[dtype_name]
+    pack = bool(getattr(args, "pack_sequences", False))
+    if pack and (dtype_name == "fp8" or (dtype_name == "fp32" and on_gpu)):
+        raise ValueError(f"--pack_sequences true runs in bf16 on the GPU (the variable-length attention kernels are "
+                         f"bf16; CPU fp32 runs the reference ops): --dtype {dtype_name} is not supported with it")
     grad_dtype = {"fp32": torch.float32, "bf16": torch.bfloat16}[args.grad_dtype or "fp32"]
     torch.manual_seed(args.seed)
 
@@ -157,11 +162,16 @@ def build(args, mode: str):
     if world > 1:
         logger.info("gradient wire format: %s (--grad_compression %s)", wire, getattr(args, "grad_compression", "none"))
     bucketer = GradBucketer(store, bucket_mb=args.bucket_mb, compression=wire) if world > 1 else None
+    hip_graph = getattr(args, "hip_graph", False)
+    if pack:
+        # data-dependent shapes: auto resolves to off; an explicit true is refused (loudly) by enable_hip_graph
+        hip_graph = False if hip_graph == "auto" else hip_graph
     trainer = Trainer(model, store, opt, bucketer, dev, grad_accum=args.gradient_accumulation_steps,
+                      pack_sequences=pack,
                       lr_schedule=getattr(args, "lr_schedule", "constant"),
                       lr_warmup_steps=getattr(args, "lr_warmup_steps", 0),
                       check_sync=args.check_sync, log_every=args.log_every, step_watchdog=args.step_watchdog,
-                      hip_graph=resolve_hip_graph(getattr(args, "hip_graph", False), on_gpu, world,
+                      hip_graph=resolve_hip_graph(hip_graph, on_gpu, world,
                                                   per_rank * max_len, args.gradient_accumulation_steps),
                       eval_hip_graph=getattr(args, "eval_hip_graph", "auto"))
     initial_epoch = 0
@@ -221,13 +231,21 @@ def run(argv: Optional[Sequence[str]] = None, mode: str = "train") -> dict:
         logger.info("evaluate: eval_batch_size %d per rank, %d batches per forward (%d sequences; "
                     "--eval_coalesce_tokens %d)", per_rank_eval, coalesce, per_rank_eval_fwd, args.eval_coalesce_tokens)
 
+    pack_kw = {}
+    if getattr(args, "pack_sequences", False):
+        pack_kw = {"pack": True, "pack_rule": hdata.position_rule(cfg)}
     train_loader = hdata.BatchLoader(train_ds, ShardSampler(len(train_ds), rank, world, shuffle=False, seed=args.seed,
-                                                             batch_size=per_rank_train), dev)
+                                                             batch_size=per_rank_train), dev, **pack_kw)
     # eval scores every test example once (reference model.evaluate, scripts/train.py:170): shards padded with
     # ignored rows, the last partial batch kept
     test_loader = hdata.BatchLoader(test_ds, ShardSampler(len(test_ds), rank, world, shuffle=False, seed=args.seed,
                                                            drop_last=False, mark_padding=True,
-                                                           batch_size=per_rank_eval_fwd), dev)
+                                                           batch_size=per_rank_eval_fwd), dev, **pack_kw)
+    if pack_kw and len(train_loader):
+        b0 = train_loader._host_batch(next(iter(train_loader.sampler.batches())))
+        logger.info("--pack_sequences: first batch holds %d real tokens of %d padded (%.1f %% padding), packed into "
+                    "%d rows", b0["real_tokens"], per_rank_train * max_len,
+                    100.0 * (1.0 - b0["real_tokens"] / float(per_rank_train * max_len)), b0["input_ids"].shape[-1])
     _provenance(args, model, rank, len(train_ds), len(test_ds), parts["batch_plan"])
     out = {"args": args}
     callbacks = [FaultInjection()]
@@ -236,7 +254,7 @@ def run(argv: Optional[Sequence[str]] = None, mode: str = "train") -> dict:
 
         if args.benchmark:
             callbacks.append(ThroughputMeter(args.output_data_dir, per_rank_train, max_len, warmup=args.warmup_steps,
-                                             log_every=args.log_every,
+                                             log_every=args.log_every, packed=bool(pack_kw),
                                              info={"model": args.model_name_or_path, "dtype": parts["dtype"],
                                                    "script": mode, "data": args.dataset}))
         if args.profile:

@@ -106,7 +106,8 @@ class Trainer:
 
     def __init__(self, model, store, optimizer, bucketer=None, device=None, grad_accum: int = 1,
                  check_sync: int = 0, log_every: int = 50, step_watchdog: float = 0.0, hip_graph: bool = False,
-                 lr_schedule: str = "constant", lr_warmup_steps: int = 0, eval_hip_graph="auto"):
+                 lr_schedule: str = "constant", lr_warmup_steps: int = 0, eval_hip_graph="auto",
+                 pack_sequences: bool = False):
         self.model = model
         self.store = store
         self.optimizer = optimizer
@@ -129,6 +130,13 @@ class Trainer:
         self._graph_replay = True  # tests: False = graph-mode seeding with eager kernels
         self._opt_overlap = None  # LocalOverlap (one process) | "engine" (DP ranks) | None
         self._grads_clear = False  # the last eager step's optimizer left the gradient buffer zeroed
+        # --pack_sequences: packed batches have data-dependent shapes, so their steps and eval forwards stay eager;
+        # the counters are host sums over the training micro-batches (obs/throughput.py reads them)
+        self.pack_sequences = bool(pack_sequences)
+        if self.pack_sequences:
+            self._graph_replay = False
+        self.packed_real_tokens = 0
+        self.packed_rows = 0
         # learning-rate schedule: the reference's Keras Adam uses a constant rate (scripts/train.py:113); linear =
         # warmup to the base rate, then linear decay to 0 over the steps fit() is asked to run
         if lr_schedule not in ("constant", "linear"):
@@ -174,6 +182,9 @@ class Trainer:
         models without data-dependent shapes; otherwise stays eager (returns False)."""
         if self.device.type != "cuda":
             logger.warning("--hip_graph: needs a GPU")
+            return False
+        if self.pack_sequences:
+            logger.warning("--hip_graph: --pack_sequences batches have data-dependent shapes; staying eager")
             return False
         if self.bucketer is not None or self.world > 1:
             # data parallel: only the whole-step graph over the native RCCL engine captures the collectives. It is
@@ -231,6 +242,12 @@ class Trainer:
         return self.base_lr * f
 
     def _forward_loss(self, batch):
+        if "cu_seqlens" in batch:  # a packed batch (data/packing.py): no mask, offsets and position ids instead
+            if self.model.training:
+                self.packed_real_tokens += int(batch["real_tokens"])
+                self.packed_rows += int(batch["input_ids"].shape[-1])
+            return self.model(batch["input_ids"], labels=batch["labels"], cu_seqlens=batch["cu_seqlens"],
+                              max_seqlen=batch["max_seqlen"], position_ids=batch["position_ids"])
         loss, logits = self.model(batch["input_ids"], attention_mask=batch["attention_mask"],
                                   labels=batch["labels"])
         return loss, logits
@@ -452,7 +469,7 @@ class Trainer:
     def _eval_forward(self, b):
         """(loss, logits, static): a captured replay when the eval graph is on for this shape, else eager."""
         ids = b["input_ids"]
-        if self._eval_graph_wanted(ids.numel()):
+        if "cu_seqlens" not in b and self._eval_graph_wanted(ids.numel()):
             key = tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(b.items()) if torch.is_tensor(v))
             g = self._eval_graphs.get(key)
             if g is None and key not in self._eval_graphs:

@@ -110,6 +110,15 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
                    help="replay the whole step from a captured HIP graph (single-process GPU runs); auto (default) = "
                         "on for launch-bound steps of <= HSD_GRAPH_AUTO_MAX_TOKENS (2,048) tokens, one micro-step, one "
                         "process (bert-base S=128 B=1-16: 1.04-1.5x eager; B>=32: eager faster)")
+    g.add_argument("--pack_sequences", type=str2bool, default=False,
+                   help="padding-free batches: each per-rank batch (training and evaluation) is packed on the host into "
+                        "one [T] row buffer without its padding tokens (T = real tokens rounded up to 256) and the step "
+                        "runs on T rows through the variable-length HIP attention kernels; loss and gradients are those "
+                        "of the padded batch. bf16 only (CPU fp32 runs the reference ops); steps stay eager (no HIP "
+                        "graph: shapes depend on the data). --train_batch_size auto still probes all-full-length "
+                        "batches, a valid worst case. One MI355X, synthetic lengths in [S/4, S]: 1.11x at bert-large "
+                        "S=512 B=64, 1.27x at bert-base S=128 B=1024, but SLOWER (0.93x) at bert-large S=512 B=8: leave "
+                        "it off for small batches and for batches that are already full length (README)")
     g.add_argument("--eval_hip_graph", type=bool_or_auto, default="auto",
                    help="evaluate by replaying a captured forward graph per batch shape; auto = for eval batches of <= "
                         "HSD_EVAL_GRAPH_MAX_TOKENS (16,384) tokens on the GPU (the reference's eval_batch_size 2: "
