@@ -247,7 +247,8 @@ void check_f32(const torch::Tensor& t, const char* name) {
 // y [rows,H] (+ residual) -> z (saved), out, mean, rstd
 void ln_fwd(torch::Tensor y, c10::optional<torch::Tensor> res, torch::Tensor gamma, torch::Tensor beta,
             c10::optional<torch::Tensor> z, torch::Tensor out, torch::Tensor mean, torch::Tensor rstd, double eps,
-            double p, int64_t seed) {
+            double p, int64_t seed, int64_t row_mul) {
+  TORCH_CHECK(row_mul >= 1 && row_mul <= 0x7fffffff, "ln_fwd row_mul");
   check_bf16(y, "y"); check_bf16(out, "out"); check_bf16(gamma, "gamma"); check_bf16(beta, "beta");
   check_f32(mean, "mean"); check_f32(rstd, "rstd");
   const int H = (int)y.size(-1);
@@ -258,7 +259,7 @@ void ln_fwd(torch::Tensor y, c10::optional<torch::Tensor> res, torch::Tensor gam
   if (z.has_value()) { check_bf16(*z, "z"); TORCH_CHECK(z->numel() == y.numel(), "z shape"); }
   hsd::launch_ln_fwd(CBF(y), res.has_value() ? CBF(*res) : nullptr, CBF(gamma), CBF(beta), OPT_BF(z), BF(out),
                      mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, H, (float)eps, p, (uint64_t)seed,
-                     cur_stream());
+                     cur_stream(), (uint32_t)row_mul);
 }
 
 // LN forward + the output's fp8 e4m3 copy (delayed scaling: amax_in = the site's previous amax, fp32 [1]; sinv fp32 [1]
@@ -282,7 +283,9 @@ void ln_fwd_q8(torch::Tensor y, torch::Tensor gamma, torch::Tensor beta, torch::
 
 void ln_bwd(torch::Tensor dout, torch::Tensor z, torch::Tensor mean, torch::Tensor rstd, torch::Tensor gamma,
             c10::optional<torch::Tensor> dz, c10::optional<torch::Tensor> dy, c10::optional<torch::Tensor> dres_add,
-            torch::Tensor dgamma, torch::Tensor dbeta, c10::optional<torch::Tensor> dbias, double p, int64_t seed) {
+            torch::Tensor dgamma, torch::Tensor dbeta, c10::optional<torch::Tensor> dbias, double p, int64_t seed,
+            int64_t row_mul) {
+  TORCH_CHECK(row_mul >= 1 && row_mul <= 0x7fffffff, "ln_bwd row_mul");
   check_bf16(dout, "dout"); check_bf16(z, "z"); check_bf16(gamma, "gamma");
   check_f32(mean, "mean"); check_f32(rstd, "rstd"); check_f32(dgamma, "dgamma"); check_f32(dbeta, "dbeta");
   const int H = (int)z.size(-1);
@@ -295,7 +298,8 @@ void ln_bwd(torch::Tensor dout, torch::Tensor z, torch::Tensor mean, torch::Tens
   if (dbias.has_value()) { check_f32(*dbias, "dbias"); TORCH_CHECK(dbias->numel() == H, "dbias shape"); }
   hsd::launch_ln_bwd(CBF(dout), CBF(z), mean.data_ptr<float>(), rstd.data_ptr<float>(), CBF(gamma), OPT_BF(dz),
                      OPT_BF(dy), dres_add.has_value() ? CBF(*dres_add) : nullptr, dgamma.data_ptr<float>(),
-                     dbeta.data_ptr<float>(), OPT_F(dbias), rows, H, p, (uint64_t)seed, cur_stream());
+                     dbeta.data_ptr<float>(), OPT_F(dbias), rows, H, p, (uint64_t)seed, cur_stream(),
+                     (uint32_t)row_mul);
 }
 
 // ln_bwd + dy's fp8 copy (qfmt 0 e4m3 / 1 e5m2) for the fp8 dgrad GEMM; dy required
@@ -415,12 +419,13 @@ void colsum(torch::Tensor x, torch::Tensor dbias) {
   hsd::launch_colsum(CBF(x), dbias.data_ptr<float>(), rows, N, cur_stream());
 }
 
-void dropout(torch::Tensor x, torch::Tensor out, double p, int64_t seed) {
+void dropout(torch::Tensor x, torch::Tensor out, double p, int64_t seed, int64_t row_mul) {
+  TORCH_CHECK(row_mul >= 1 && row_mul <= 0x7fffffff, "dropout row_mul");
   check_bf16(x, "x"); check_bf16(out, "out");
   // the mask's row width is the last dimension (ops/rng.py); 4-element vectors never straddle a row
   const int64_t W = x.dim() ? x.size(-1) : 1;
   TORCH_CHECK(x.numel() == out.numel() && W % 4 == 0, "dropout shapes");
-  hsd::launch_dropout(CBF(x), BF(out), x.numel(), (int)W, p, (uint64_t)seed, cur_stream());
+  hsd::launch_dropout(CBF(x), BF(out), x.numel(), (int)W, p, (uint64_t)seed, cur_stream(), (uint32_t)row_mul);
 }
 
 static uint32_t* keep_mask_ptr(const c10::optional<torch::Tensor>& km, int64_t B, int64_t S, int64_t heads) {
@@ -463,6 +468,40 @@ void attn_bwd(torch::Tensor qkv, c10::optional<torch::Tensor> mask, torch::Tenso
   hsd::launch_attn_bwd(CBF(qkv), OPT_F(mask), CBF(o), CBF(dout), lse2.data_ptr<float>(), BF(dqkv), OPT_F(dq_acc),
                        OPT_F(dbias), (int)B, (int)S, (int)heads, p, (uint64_t)seed, cur_stream(),
                        keep_mask_ptr(kmask, B, S, heads), delta_ready);
+}
+
+// attention of the first query row of each sequence (attention_cls.hip): qkv [B*S, 3H] -> out [B, H], lse2 [B*heads]
+void attn_cls_fwd(torch::Tensor qkv, c10::optional<torch::Tensor> mask, torch::Tensor out, torch::Tensor lse2,
+                  int64_t B, int64_t S, int64_t heads, double p, int64_t seed) {
+  check_bf16(qkv, "qkv"); check_bf16(out, "out"); check_f32(lse2, "lse2");
+  TORCH_CHECK(B > 0 && heads > 0 && hsd::attn_cls_supported((int)S, 64), "attn_cls: even S in [2, 4096]");
+  TORCH_CHECK(qkv.numel() == B * S * 3 * heads * 64 && out.numel() == B * heads * 64, "attn_cls shapes (head_dim 64)");
+  TORCH_CHECK(lse2.numel() == B * heads, "attn_cls lse2 shape");
+  if (mask.has_value()) { check_f32(*mask, "mask"); TORCH_CHECK(mask->numel() == B * S, "mask shape"); }
+  hsd::launch_attn_cls_fwd(CBF(qkv), OPT_F(mask), BF(out), lse2.data_ptr<float>(), (int)B, (int)S, (int)heads, p,
+                           (uint64_t)seed, cur_stream());
+}
+
+void attn_cls_bwd(torch::Tensor qkv, c10::optional<torch::Tensor> mask, torch::Tensor dctx, torch::Tensor lse2,
+                  torch::Tensor dqkv, int64_t B, int64_t S, int64_t heads, double p, int64_t seed,
+                  c10::optional<torch::Tensor> dbias) {
+  check_bf16(qkv, "qkv"); check_bf16(dctx, "dctx"); check_bf16(dqkv, "dqkv"); check_f32(lse2, "lse2");
+  TORCH_CHECK(B > 0 && heads > 0 && hsd::attn_cls_supported((int)S, 64), "attn_cls: even S in [2, 4096]");
+  TORCH_CHECK(qkv.numel() == B * S * 3 * heads * 64 && dqkv.numel() == qkv.numel() && dctx.numel() == B * heads * 64,
+              "attn_cls_bwd shapes (head_dim 64)");
+  TORCH_CHECK(lse2.numel() == B * heads, "attn_cls lse2 shape");
+  if (mask.has_value()) { check_f32(*mask, "mask"); TORCH_CHECK(mask->numel() == B * S, "mask shape"); }
+  if (dbias.has_value()) { check_f32(*dbias, "dbias"); TORCH_CHECK(dbias->numel() == 3 * heads * 64, "dbias shape"); }
+  hsd::launch_attn_cls_bwd(CBF(qkv), OPT_F(mask), CBF(dctx), lse2.data_ptr<float>(), BF(dqkv), OPT_F(dbias), (int)B,
+                           (int)S, (int)heads, p, (uint64_t)seed, cur_stream());
+}
+
+// dst [B*S, H] (contiguous): dst[b*S] += src[b], src [B, H]
+void add_rows_strided(torch::Tensor dst, torch::Tensor src, int64_t S) {
+  check_bf16(dst, "dst"); check_bf16(src, "src");
+  TORCH_CHECK(src.dim() == 2 && S > 0 && src.size(1) % 8 == 0 && dst.numel() == src.numel() * S,
+              "add_rows_strided: src [B, H] (H % 8 == 0), dst [B * S, H]");
+  hsd::launch_add_rows_strided(BF(dst), CBF(src), (int)src.size(0), (int)S, (int)src.size(1), cur_stream());
 }
 
 // padding-free attention over packed sequences (attention_varlen.hip): qkv [T, 3H], cu_seqlens int32 [B+1] on the
@@ -560,7 +599,9 @@ void attn_bwd_q8(torch::Tensor qkv, c10::optional<torch::Tensor> mask, torch::Te
 // C[M,N] (+)= A·B with fused epilogue. la=0: A [M,K]; la=1: A [K,M]. lb=0: B [N,K]; lb=1: B [K,N].
 void gemm(torch::Tensor A, torch::Tensor B, torch::Tensor C, int64_t la, int64_t lb, int64_t epi,
           c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> aux, c10::optional<torch::Tensor> C2,
-          double p, int64_t seed, int64_t splits) {
+          double p, int64_t seed, int64_t splits, int64_t row_mul) {
+  TORCH_CHECK(row_mul >= 1 && row_mul <= 0x7fffffff && (row_mul == 1 || epi == 3),
+              "gemm row_mul: a dropout row multiplier goes with the BIAS_DROP_RES epilogue only");
   TORCH_CHECK(A.is_cuda() && B.is_cuda() && C.is_cuda(), "gemm operands must be GPU tensors");
   TORCH_CHECK(A.scalar_type() == torch::kBFloat16 && B.scalar_type() == torch::kBFloat16, "gemm inputs must be bf16");
   TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && C.dim() == 2, "gemm operands must be 2-D");
@@ -591,7 +632,8 @@ void gemm(torch::Tensor A, torch::Tensor B, torch::Tensor C, int64_t la, int64_t
   hsd::launch_gemm((int)la, (int)lb, (int)epi, CBF(A), A.stride(0), CBF(B), B.stride(0), (int)M, (int)N, (int)K,
                    C.data_ptr(), C.stride(0), bias.has_value() ? CBF(*bias) : nullptr,
                    aux.has_value() ? CBF(*aux) : nullptr, aux.has_value() ? aux->stride(0) : 0,
-                   C2.has_value() ? BF(*C2) : nullptr, p, (uint64_t)seed, (int)splits, cur_stream());
+                   C2.has_value() ? BF(*C2) : nullptr, p, (uint64_t)seed, (int)splits, cur_stream(),
+                   (uint32_t)row_mul);
 }
 
 // gemm2: la=lb=0 -> NT (A [M,K], B [N,K]) bf16 C with epilogue 0..5;
@@ -762,7 +804,9 @@ void set_dropout_device_seed(c10::optional<torch::Tensor> t) {
 void gemm2(torch::Tensor A, torch::Tensor B, torch::Tensor C, int64_t la, int64_t lb, int64_t epi,
            c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> aux, c10::optional<torch::Tensor> C2,
            double p, int64_t seed, int64_t splits, c10::optional<torch::Tensor> ws,
-           c10::optional<torch::Tensor> dbias, c10::optional<torch::Tensor> rd, int64_t rd_seq) {
+           c10::optional<torch::Tensor> dbias, c10::optional<torch::Tensor> rd, int64_t rd_seq, int64_t row_mul) {
+  TORCH_CHECK(row_mul >= 1 && row_mul <= 0x7fffffff && (row_mul == 1 || epi == hsd::E2_BIAS_DROP_RES),
+              "gemm2 row_mul: a dropout row multiplier goes with the BIAS_DROP_RES epilogue only");
   TORCH_CHECK(A.is_cuda() && B.is_cuda() && C.is_cuda(), "gemm2 operands must be GPU tensors");
   TORCH_CHECK(A.scalar_type() == torch::kBFloat16 && B.scalar_type() == torch::kBFloat16, "gemm2 inputs must be bf16");
   TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && C.dim() == 2, "gemm2 operands must be 2-D");
@@ -791,7 +835,7 @@ void gemm2(torch::Tensor A, torch::Tensor B, torch::Tensor C, int64_t la, int64_
                     C.data_ptr(), C.stride(0), bias.has_value() ? CBF(*bias) : nullptr,
                     aux.has_value() ? CBF(*aux) : nullptr, aux.has_value() ? aux->stride(0) : 0,
                     C2.has_value() ? BF(*C2) : nullptr, p, (uint64_t)seed, (int)splits, wsp, eo.dbias, cur_stream(),
-                    eo.rd, (int)rd_seq, &pl);
+                    eo.rd, (int)rd_seq, &pl, (uint32_t)row_mul);
 }
 
 // ---- fp32 step (fp32.hip, ops/hip32.py) ---------------------------------------------------------------------------
@@ -1045,7 +1089,7 @@ void gemm2_on(int64_t stream_ptr, torch::Tensor A, torch::Tensor B, torch::Tenso
               c10::optional<torch::Tensor> dbias) {
   c10::hip::HIPStreamGuard guard(
       c10::hip::getStreamFromExternal(reinterpret_cast<hipStream_t>(stream_ptr), A.get_device()));
-  gemm2(A, B, C, la, lb, epi, bias, aux, C2, p, seed, splits, ws, dbias, c10::nullopt, 0);
+  gemm2(A, B, C, la, lb, epi, bias, aux, C2, p, seed, splits, ws, dbias, c10::nullopt, 0, 1);
 }
 
 // logits [R, V] (bf16 | fp32), labels int64 [R] (-100 = ignore); stats fp32 [2] += {Σ loss, correct};
@@ -1255,8 +1299,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dbias"), py::arg("q8"), py::arg("amax_in"), py::arg("sinv"), py::arg("amax_track"), py::arg("qfmt"),
         py::arg("kmask") = py::none(), py::arg("delta_ready") = false, py::arg("q8_only") = false);
   m.def("attn_q8_supported", [](int64_t S) { return S > 128 && hsd::attn_streaming((int)S); });
-  m.def("ln_fwd", &ln_fwd);
-  m.def("ln_bwd", &ln_bwd);
+  m.def("ln_fwd", &ln_fwd, py::arg("y"), py::arg("res"), py::arg("gamma"), py::arg("beta"), py::arg("z"),
+        py::arg("out"), py::arg("mean"), py::arg("rstd"), py::arg("eps"), py::arg("p"), py::arg("seed"),
+        py::arg("row_mul") = 1);
+  m.def("ln_bwd", &ln_bwd, py::arg("dout"), py::arg("z"), py::arg("mean"), py::arg("rstd"), py::arg("gamma"),
+        py::arg("dz"), py::arg("dy"), py::arg("dres_add"), py::arg("dgamma"), py::arg("dbeta"), py::arg("dbias"),
+        py::arg("p"), py::arg("seed"), py::arg("row_mul") = 1);
   m.def("embed_fwd", &embed_fwd, py::arg("ids"), py::arg("pos_ids"), py::arg("type_ids"), py::arg("word"),
         py::arg("pos"), py::arg("type"), py::arg("gamma"), py::arg("beta"), py::arg("out"), py::arg("mean"),
         py::arg("rstd"), py::arg("eps"), py::arg("p"), py::arg("seed"), py::arg("q8") = py::none(),
@@ -1265,7 +1313,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelu_fwd", &gelu_fwd);
   m.def("gelu_bwd_colsum", &gelu_bwd_colsum);
   m.def("colsum", &colsum);
-  m.def("dropout", &dropout);
+  m.def("dropout", &dropout, py::arg("x"), py::arg("out"), py::arg("p"), py::arg("seed"), py::arg("row_mul") = 1);
   m.def("set_dropout_device_seed", &set_dropout_device_seed);
   m.def("cu_hog", [](int64_t blocks, double usec) { hsd::launch_cu_hog((int)blocks, usec, cur_stream()); },
         "contention emulation: hold `blocks` whole CUs for `usec` us on the current stream");
@@ -1322,15 +1370,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("mask"), py::arg("o"), py::arg("dout"), py::arg("lse2"),
         py::arg("dqkv"), py::arg("dq_acc"), py::arg("B"), py::arg("S"), py::arg("heads"), py::arg("p"), py::arg("seed"),
         py::arg("dbias") = py::none(), py::arg("kmask") = py::none(), py::arg("delta_ready") = false);
+  m.def("attn_cls_fwd", &attn_cls_fwd, py::arg("qkv"), py::arg("mask"), py::arg("out"), py::arg("lse2"), py::arg("B"),
+        py::arg("S"), py::arg("heads"), py::arg("p"), py::arg("seed"));
+  m.def("attn_cls_bwd", &attn_cls_bwd, py::arg("qkv"), py::arg("mask"), py::arg("dctx"), py::arg("lse2"),
+        py::arg("dqkv"), py::arg("B"), py::arg("S"), py::arg("heads"), py::arg("p"), py::arg("seed"),
+        py::arg("dbias") = py::none());
+  m.def("attn_cls_supported", [](int64_t S) { return S > 0 && S <= 4096 && hsd::attn_cls_supported((int)S, 64); });
+  m.def("add_rows_strided", &add_rows_strided);
   m.def("attn_varlen_fwd", &attn_varlen_fwd, py::arg("qkv"), py::arg("cu_seqlens"), py::arg("out"), py::arg("lse2"),
         py::arg("B"), py::arg("max_seqlen"), py::arg("heads"), py::arg("p"), py::arg("seed"));
   m.def("attn_varlen_bwd", &attn_varlen_bwd, py::arg("qkv"), py::arg("cu_seqlens"), py::arg("o"), py::arg("dout"),
         py::arg("lse2"), py::arg("dqkv"), py::arg("B"), py::arg("max_seqlen"), py::arg("heads"), py::arg("p"),
         py::arg("seed"), py::arg("dbias") = py::none());
-  m.def("gemm", &gemm);
+  m.def("gemm", &gemm, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("la"), py::arg("lb"), py::arg("epi"),
+        py::arg("bias"), py::arg("aux"), py::arg("C2"), py::arg("p"), py::arg("seed"), py::arg("splits"),
+        py::arg("row_mul") = 1);
   m.def("gemm2", &gemm2, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("la"), py::arg("lb"), py::arg("epi"),
         py::arg("bias"), py::arg("aux"), py::arg("C2"), py::arg("p"), py::arg("seed"), py::arg("splits"), py::arg("ws"),
-        py::arg("dbias"), py::arg("rd") = py::none(), py::arg("rd_seq") = 0);
+        py::arg("dbias"), py::arg("rd") = py::none(), py::arg("rd_seq") = 0, py::arg("row_mul") = 1);
   m.def("gemm2_splits", &gemm2_splits);
   m.def("gemm8_wgrad", &gemm8_wgrad);
   m.def("gemm8_wgrad_supported", [](int64_t M, int64_t N, int64_t T) {

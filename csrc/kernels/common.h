@@ -180,6 +180,9 @@ struct DropoutParams {
   uint32_t thr;     // keep iff bits16 >= thr
   float scale;      // 1/(1-p)
   int enabled;
+  // row r of the kernel's [rows, W] view is row r * row_mul of the dropout site (1 everywhere except the first-token
+  // rows of the last encoder layer, ops/hip.py _AttnBlockCls: a gathered row b is row b * S of the [B * S, W] site)
+  uint32_t row_mul;
   // optional device-side step seed XORed into (seed_lo, seed_hi): lets a captured HIP graph replay with
   // fresh dropout masks every step (the per-site host seeds are baked into the graph)
   const uint32_t* dev_seed;
@@ -188,8 +191,9 @@ struct DropoutParams {
 // process-wide device step seed (uint32 [2]) picked up by every make_dropout (null = off)
 inline const uint32_t* g_dropout_dev_seed = nullptr;
 
-__host__ inline DropoutParams make_dropout(double p, uint64_t seed) {
+__host__ inline DropoutParams make_dropout(double p, uint64_t seed, uint32_t row_mul = 1) {
   DropoutParams d;
+  d.row_mul = row_mul;
   d.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull);
   d.seed_hi = (uint32_t)(seed >> 32);
   d.key = dropout_key(d.seed_lo, d.seed_hi);
@@ -221,6 +225,12 @@ __device__ __forceinline__ uint32_t dropout_key_of(const DropoutParams& d) {
 // the row word of row `row` of a site (R(r))
 __device__ __forceinline__ uint32_t dropout_row(uint32_t row, const DropoutParams& d) {
   return drop_row(row, dropout_key_of(d));
+}
+// ... of row `row` of a kernel's view of the site (R(row * row_mul): one integer multiply per row): the kernels whose
+// launchers take a row multiplier (GEMM dropout epilogues, LayerNorm, the dropout kernel). Attention, embedding,
+// cls-head, fp8 and fp32 kernels never see one and keep dropout_row
+__device__ __forceinline__ uint32_t dropout_row_mul(uint32_t row, const DropoutParams& d) {
+  return drop_row(row * d.row_mul, dropout_key_of(d));
 }
 
 // bits of column pair `cp` given its row word (generic path: C(cp) computed at run time when cp is not a literal)

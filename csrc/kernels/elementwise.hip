@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void dropout_kernel(const bf16_t* __restrict__
     // 4 elements of one row (W % 4 == 0): column pairs cp0 (even) and cp0 + 1 = cp0 ^ 1
     const int64_t row = (i * 4) / W;
     const uint32_t cp0 = (uint32_t)((i * 4 - row * W) >> 1);
-    const uint32_t xw = drop_row((uint32_t)row, dp.key) ^ drop_col(cp0);
+    const uint32_t xw = drop_row((uint32_t)row * dp.row_mul, dp.key) ^ drop_col(cp0);
     const uint32_t b0 = drop_fin(xw), b1 = drop_fin(xw ^ drop_col(1));
     u32x2 o;
     o.x = pack_bf2(lo_bf(w.x) * keep_factor(b0, 0, dp), hi_bf(w.x) * keep_factor(b0, 1, dp));
@@ -185,10 +185,33 @@ uint32_t dropout_pair_bits_host(uint64_t seed, uint32_t row, uint32_t cp) {
   return drop_fin(drop_row(row, d.key) ^ drop_col(cp));
 }
 
-void launch_dropout(const bf16_t* x, bf16_t* out, int64_t n, int W, double p, uint64_t seed, hipStream_t st) {
-  DropoutParams dp = make_dropout(p, seed);
+void launch_dropout(const bf16_t* x, bf16_t* out, int64_t n, int W, double p, uint64_t seed, hipStream_t st,
+                    uint32_t row_mul) {
+  DropoutParams dp = make_dropout(p, seed, row_mul);
   int64_t n4 = n / 4;  // caller guarantees n % 4 == 0
   hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n4)), dim3(256), 0, st, x, out, n4, W, dp);
+  HSD_CHECK_LAUNCH();
+}
+
+// dst[b * S][:] += src[b][:]: the first-token rows' residual gradient added into the QKV dgrad's [B * S, H] output
+// (ops/hip.py _AttnBlockCls; every other row's residual gradient is zero). One 16-B chunk per thread.
+__global__ __launch_bounds__(256) void add_rows_strided_kernel(bf16_t* __restrict__ dst, const bf16_t* __restrict__ src,
+                                                               int B, int S, int H8) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * H8) return;
+  const int b = i / H8, c = i % H8;
+  u32x4* d = reinterpret_cast<u32x4*>(dst + (int64_t)b * S * H8 * 8) + c;
+  const u32x4 s = reinterpret_cast<const u32x4*>(src)[i];
+  u32x4 v = *d;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = pack_bf2(lo_bf(v[k]) + lo_bf(s[k]), hi_bf(v[k]) + hi_bf(s[k]));
+  *d = v;
+}
+
+void launch_add_rows_strided(bf16_t* dst, const bf16_t* src, int B, int S, int H, hipStream_t st) {
+  if (H % 8 || B <= 0 || S <= 0) abort();
+  const int n = B * (H / 8);
+  hipLaunchKernelGGL(add_rows_strided_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dst, src, B, S, H / 8);
   HSD_CHECK_LAUNCH();
 }
 

@@ -171,7 +171,7 @@ __device__ __forceinline__ void epi_block(const f32x16& a, int mb, int nb, int l
         for (int e = 0; e < 4; ++e) v[e] = bf2f(f2bf(v[e]));
         if (p.dp.enabled) {
           uint32_t b0, b1;
-          dropout_bits4((uint32_t)m, (uint32_t)n, p.dp, b0, b1);  // mask row m of width N, n % 4 == 0
+          dropout_bits4((uint32_t)m * p.dp.row_mul, (uint32_t)n, p.dp, b0, b1);  // mask row m of width N, n % 4 == 0
           v[0] = __builtin_fmaf(v[0], keep_factor(b0, 0, p.dp), lo_bf(xw[q4].x));
           v[1] = __builtin_fmaf(v[1], keep_factor(b0, 1, p.dp), hi_bf(xw[q4].x));
           v[2] = __builtin_fmaf(v[2], keep_factor(b1, 0, p.dp), lo_bf(xw[q4].y));
@@ -461,11 +461,12 @@ static void gemm_launch(const GemmParams& p0, int splits, hipStream_t st) {
 // Public entry: layouts + epilogue chosen at run time.
 void launch_gemm(int la, int lb, int epi, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N,
                  int K, void* C, int64_t ldc, const bf16_t* bias, const bf16_t* aux, int64_t ldaux, bf16_t* C2,
-                 double p_drop, uint64_t seed, int splits, hipStream_t st) {
+                 double p_drop, uint64_t seed, int splits, hipStream_t st, uint32_t row_mul) {
   GemmParams p{};
   p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.M = M; p.N = N; p.K = K; p.C = C; p.ldc = ldc;
   p.bias = bias; p.aux = aux; p.ldaux = ldaux; p.C2 = C2;
-  p.dp = make_dropout(p_drop, seed);
+  if (row_mul != 1 && epi != EPI_BIAS_DROP_RES) abort();  // only the dropout epilogue has a row word
+  p.dp = make_dropout(p_drop, seed, row_mul);
   // the v2 (LDS-DMA) kernel where the shape tiles it; the v1 register-staged kernel for the rest (K % 64, tiny M / N)
   const bool dma = (K % 64 == 0) && (M >= 128) && (N >= 128);
   if (dma) {

@@ -1065,7 +1065,7 @@ __global__ __launch_bounds__(256) void splitk_epi_kernel(const float* __restrict
       u32x4 x = {0, 0, 0, 0};
       if constexpr (epi_aux(EPI)) x = *reinterpret_cast<const u32x4*>(p.aux + (int64_t)m * p.ldaux + n);
       epi_chunk<EPI>(o, o2, x, m, n, p, csum,
-                     EPI == E2_BIAS_DROP_RES && p.dp.enabled ? drop_row((uint32_t)m, p.dp.key) ^ cw : 0u);
+                     EPI == E2_BIAS_DROP_RES && p.dp.enabled ? drop_row((uint32_t)m * p.dp.row_mul, p.dp.key) ^ cw : 0u);
       if constexpr (EPI == E2_STORE_RDOT) rdot_group(o, x, m, n, p, c8 == 0, true);  // 8 lanes of one row, all in
       st16(C + (int64_t)m * p.ldc + n, o, p.nt_store);
       if constexpr (epi_two_out(EPI)) st16(p.C2 + (int64_t)m * p.ldc + n, o2, p.nt_store);
@@ -1480,7 +1480,7 @@ void gemm2_set_diag(void* p) { g_diag = (unsigned long long*)p; }
 void launch_gemm2(int la, int lb, int epi, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N,
                   int K, void* C, int64_t ldc, const bf16_t* bias, const bf16_t* aux, int64_t ldaux, bf16_t* C2,
                   double p_drop, uint64_t seed, int splits, float* ws, float* dbias, hipStream_t st, float* rd,
-                  int rd_seq, const GemmPlan* planned) {
+                  int rd_seq, const GemmPlan* planned, uint32_t row_mul) {
   G2Params p{};
   p.dbias = dbias;
   p.rd = rd;
@@ -1490,7 +1490,8 @@ void launch_gemm2(int la, int lb, int epi, const bf16_t* A, int64_t lda, const b
   p.nt_store = 1;  // non-temporal epilogue stores (profiles/store_policy_r3.log)
   p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.M = M; p.N = N; p.K = K; p.C = C; p.ldc = ldc;
   p.bias = bias; p.aux = aux; p.ldaux = ldaux; p.C2 = C2;
-  p.dp = make_dropout(p_drop, seed);
+  if (row_mul != 1 && epi != E2_BIAS_DROP_RES) abort();  // only the dropout epilogue has a row word
+  p.dp = make_dropout(p_drop, seed, row_mul);
   if (la == 0 && epi == E2_F32_SLAB && ldc != N) abort();  // fp32 NT output: [M][N]
   const GemmPlan pl = planned != nullptr ? *planned
                                          : plan::plan_gemm2(la, lb, epi, M, N, K, la == 0 && splits <= 0 ? 1 : splits,

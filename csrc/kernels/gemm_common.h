@@ -431,7 +431,7 @@ __device__ __forceinline__ void epilogue_bf16(f32x4 (&acc)[MB][BN / 64], const G
       epi_aux_regs<EPI, BN, PB>(xv, p, lane, mw, nw, h);
     }
     uint32_t rw_lane = 0u;  // R(row `lane` of this pass)
-    if (kDrop && drop_on && kColFixed) rw_lane = drop_row((uint32_t)(mw + 16 * PB * h + lane), p.dp.key);
+    if (kDrop && drop_on && kColFixed) rw_lane = drop_row((uint32_t)(mw + 16 * PB * h + lane) * p.dp.row_mul, p.dp.key);
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
       const int idx = lane + 64 * it;
@@ -441,7 +441,7 @@ __device__ __forceinline__ void epilogue_bf16(f32x4 (&acc)[MB][BN / 64], const G
       uint32_t xw = 0u;
       if (kDrop && drop_on) {
         xw = kColFixed ? (uint32_t)__builtin_amdgcn_ds_bpermute(4 * row, (int)rw_lane) ^ cw
-                       : drop_row((uint32_t)m, p.dp.key) ^ epi_col_word<EPI>(n, p);
+                       : drop_row((uint32_t)m * p.dp.row_mul, p.dp.key) ^ epi_col_word<EPI>(n, p);
       }
       if constexpr (EPI == E2_STORE_RDOT) {
         static_assert(CPR == 8, "row dots: 8 chunks (one 64-column head) per row");

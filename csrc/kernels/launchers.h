@@ -43,7 +43,7 @@ namespace hsd {
 // layernorm.hip
 void launch_ln_fwd(const bf16_t* y, const bf16_t* res, const bf16_t* gamma, const bf16_t* beta, bf16_t* z,
                    bf16_t* out, float* mean, float* rstd, int rows, int H, float eps, double p, uint64_t seed,
-                   hipStream_t st);
+                   hipStream_t st, uint32_t row_mul = 1);
 void launch_ln_fwd_q8(const bf16_t* y, const bf16_t* gamma, const bf16_t* beta, bf16_t* out, float* mean, float* rstd,
                       int rows, int H, float eps, uint8_t* q8, const float* amax_in, float* sinv, float* amax_track,
                       hipStream_t st);
@@ -53,7 +53,7 @@ void launch_ln_bwd_q8(const bf16_t* dout, const bf16_t* z, const float* mean, co
                       float* amax_track, int qfmt, hipStream_t st, bool q8_only = false);
 void launch_ln_bwd(const bf16_t* dout, const bf16_t* z, const float* mean, const float* rstd, const bf16_t* gamma,
                    bf16_t* dz, bf16_t* dy, const bf16_t* dres_add, float* dgamma, float* dbeta, float* dbias,
-                   int rows, int H, double p, uint64_t seed, hipStream_t st);
+                   int rows, int H, double p, uint64_t seed, hipStream_t st, uint32_t row_mul = 1);
 // embedding.hip
 void launch_embed_fwd(const int64_t* ids, const int64_t* pos_ids, const int64_t* type_ids, const bf16_t* word,
                       const bf16_t* pos, const bf16_t* type, const bf16_t* gamma, const bf16_t* beta, bf16_t* out,
@@ -71,7 +71,11 @@ void launch_gelu_bwd_colsum(const bf16_t* dg, const bf16_t* y, bf16_t* da, float
 void launch_colsum(const bf16_t* x, float* dbias, int rows, int N, hipStream_t st);
 // the 32 mask bits of column pair cp of row `row` of a dropout site with 64-bit `seed` (common.h), on the host
 uint32_t dropout_pair_bits_host(uint64_t seed, uint32_t row, uint32_t cp);
-void launch_dropout(const bf16_t* x, bf16_t* out, int64_t n, int W, double p, uint64_t seed, hipStream_t st);
+// row_mul: row r of x is row r * row_mul of the dropout site (common.h DropoutParams)
+void launch_dropout(const bf16_t* x, bf16_t* out, int64_t n, int W, double p, uint64_t seed, hipStream_t st,
+                    uint32_t row_mul = 1);
+// dst[b * S][:] += src[b][:] (bf16, H % 8 == 0): the first-token rows' residual gradient into a [B * S, H] buffer
+void launch_add_rows_strided(bf16_t* dst, const bf16_t* src, int B, int S, int H, hipStream_t st);
 void launch_mask_bias(const void* mask, bool i64, float* out, int64_t n, hipStream_t st);
 // C[N][K] (fp32, ldc) += dy[T][N]ᵀ · x[T][K] for small T (K % 4 == 0)
 void launch_small_wgrad(const bf16_t* dy, int64_t ldy, const bf16_t* x, int64_t ldx, float* C, int64_t ldc, int T,
@@ -112,6 +116,14 @@ void launch_attnS_bwd_q8(const bf16_t* qkv, const float* mask, const bf16_t* o, 
 void launch_attn_bwd(const bf16_t* qkv, const float* mask, const bf16_t* o, const bf16_t* dout, const float* lse2,
                      bf16_t* dqkv, float* dq_acc, float* dbias, int B, int S, int heads, double p, uint64_t seed,
                      hipStream_t st, const uint32_t* kmask = nullptr, bool delta_ready = false);
+// attention_cls.hip: attention of query row 0 only (the first token of each sequence; head_dim 64, even S <= 4096).
+// Forward: out [B, H], lse2 [B * heads]. Backward: the full dqkv [B * S, 3H] (dK / dV of every key, dQ of row 0, zeros
+// in every other dQ row) and, with dbias, fp32 [3H] += its column sums. Dropout rows are the full kernels' rows.
+bool attn_cls_supported(int S, int head_dim);
+void launch_attn_cls_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse2, int B, int S, int heads,
+                         double p, uint64_t seed, hipStream_t st);
+void launch_attn_cls_bwd(const bf16_t* qkv, const float* mask, const bf16_t* dctx, const float* lse2, bf16_t* dqkv,
+                         float* dbias, int B, int S, int heads, double p, uint64_t seed, hipStream_t st);
 // attention_varlen.hip: padding-free attention over a packed qkv [T, 3H]; sequence b is rows cu_seqlens[b] ..
 // cu_seqlens[b+1]-1 (device int32 [B+1]), rows from cu_seqlens[B] on are dead (written as zeros); lse2 is [heads, T].
 // The backward writes every dqkv element once (no atomics) and adds the column sums of dqkv into dbias when given.
@@ -126,7 +138,7 @@ namespace hsd {
 // gemm.hip — la: 0 A[M][K], 1 A[K][M];  lb: 0 B[N][K], 1 B[K][N];  epi: see gemm.hip Epi
 void launch_gemm(int la, int lb, int epi, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N,
                  int K, void* C, int64_t ldc, const bf16_t* bias, const bf16_t* aux, int64_t ldaux, bf16_t* C2,
-                 double p_drop, uint64_t seed, int splits, hipStream_t st);
+                 double p_drop, uint64_t seed, int splits, hipStream_t st, uint32_t row_mul = 1);
 // device step seed for dropout (common.h g_dropout_dev_seed); nullptr = off
 void set_dropout_dev_seed(const uint32_t* p);
 // HSD_* knobs are cached per generation (common.h HSD_KNOB); this re-reads them at their next use
@@ -188,7 +200,7 @@ void gemm2_set_diag(void* p);  // diagnostic timestamps of the persistent NT ker
 void launch_gemm2(int la, int lb, int epi, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N,
                   int K, void* C, int64_t ldc, const bf16_t* bias, const bf16_t* aux, int64_t ldaux, bf16_t* C2,
                   double p_drop, uint64_t seed, int splits, float* ws, float* dbias, hipStream_t st,
-                  float* rd = nullptr, int rd_seq = 0, const GemmPlan* planned = nullptr);
+                  float* rd = nullptr, int rd_seq = 0, const GemmPlan* planned = nullptr, uint32_t row_mul = 1);
 bool gemm2_supported(int la, int lb, int epi, int M, int N, int K);
 int gemm2_wgrad_splits(int M, int N, int K);
 int gemm2_nt_splits(int M, int N, int K);

@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ 
   if (row >= rows) return;
   const int nq = H >> 2;  // 4-element chunks in the row
   // dropout: mask row `row`, pairs 2c and 2c + 1 of chunk c = lane + 64 i: C(2c) = C(2 lane) ^ C(128 i)
-  const uint32_t xr = dp.enabled ? dropout_row((uint32_t)row, dp) ^ drop_col(2u * (uint32_t)lane) : 0u;
+  const uint32_t xr = dp.enabled ? dropout_row_mul((uint32_t)row, dp) ^ drop_col(2u * (uint32_t)lane) : 0u;
   float v[NCH][4];
   float s = 0.f;
 #pragma unroll
@@ -157,8 +157,10 @@ __device__ __forceinline__ void ln_bwd_load(const bf16_t* __restrict__ dout, con
   }
 }
 
-// QF >= 0: also dy's fp8 copy (QF = format) into q8 with scale qs, max |dy| into qm
-template <int NCH, int QF = -1>
+// QF >= 0: also dy's fp8 copy (QF = format) into q8 with scale qs, max |dy| into qm. RM: the dropout row is
+// row * dp.row_mul (a template switch: with the multiply compiled into every instance the headline's <3, -1> kernel
+// took 162 VGPRs instead of 154 and the fp8 instances lost a wave per SIMD)
+template <int NCH, int QF = -1, bool RM = false>
 __device__ __forceinline__ void ln_bwd_row(const u32x2 (&zw)[NCH], const u32x2 (&dw)[NCH], float mean, float rstd,
                                            const float (&gam)[NCH][4], int row, int H, int lane,
                                            bf16_t* __restrict__ dz_out, bf16_t* __restrict__ dy_out,
@@ -206,7 +208,8 @@ __device__ __forceinline__ void ln_bwd_row(const u32x2 (&zw)[NCH], const u32x2 (
       float dy[4] = {dz[0], dz[1], dz[2], dz[3]};
       if (dp.enabled) {
         // mask row `row`, pairs 2c and 2c + 1: C(2c) = C(2 lane) ^ C(128 i) (C(2 lane) is loop-invariant: hoisted)
-        const uint32_t x = dropout_row((uint32_t)row, dp) ^ drop_col(2u * (uint32_t)lane) ^ drop_col(128u * (uint32_t)i);
+        const uint32_t x = (RM ? dropout_row_mul((uint32_t)row, dp) : dropout_row((uint32_t)row, dp)) ^
+                           drop_col(2u * (uint32_t)lane) ^ drop_col(128u * (uint32_t)i);
         const uint32_t b0 = drop_fin(x), b1 = drop_fin(x ^ drop_col(1));
         dy[0] *= keep_factor(b0, 0, dp);
         dy[1] *= keep_factor(b0, 1, dp);
@@ -233,7 +236,7 @@ __device__ __forceinline__ void ln_bwd_row(const u32x2 (&zw)[NCH], const u32x2 (
 // row reduces), keeps dgamma / dbeta / dbias column partials in registers, and the block reduces its 4
 // waves' partials through LDS into one fp32 atomic per column per block. Reads dout, z once; writes
 // dz, dy once (the round-1 split rows + columns passes read dout / z twice: 170 -> ~120 us at the headline shape).
-template <int NCH, int QF>
+template <int NCH, int QF, bool RM = false>
 __global__ __launch_bounds__(256) void ln_bwd_fused_kernel(const bf16_t* __restrict__ dout,
                                                            const bf16_t* __restrict__ z,
                                                            const float* __restrict__ mean_in,
@@ -280,7 +283,7 @@ __global__ __launch_bounds__(256) void ln_bwd_fused_kernel(const bf16_t* __restr
         mu2 = mean_in[r + 1];
         rs2 = rstd_in[r + 1];
       }
-      ln_bwd_row<NCH, QF>(za, da, mu, rs, gam, r, H, lane, dz_out, dy_out, dres_add, dp, ag, ab, ad, q8o.q, qs, &qm,
+      ln_bwd_row<NCH, QF, RM>(za, da, mu, rs, gam, r, H, lane, dz_out, dy_out, dres_add, dp, ag, ab, ad, q8o.q, qs, &qm,
                           q8only);
       if (!more) break;
       const bool more2 = r + 2 < r1;
@@ -289,7 +292,7 @@ __global__ __launch_bounds__(256) void ln_bwd_fused_kernel(const bf16_t* __restr
         mu = mean_in[r + 2];
         rs = rstd_in[r + 2];
       }
-      ln_bwd_row<NCH, QF>(zb, db, mu2, rs2, gam, r + 1, H, lane, dz_out, dy_out, dres_add, dp, ag, ab, ad, q8o.q, qs,
+      ln_bwd_row<NCH, QF, RM>(zb, db, mu2, rs2, gam, r + 1, H, lane, dz_out, dy_out, dres_add, dp, ag, ab, ad, q8o.q, qs,
                           &qm, q8only);
     }
   }
@@ -337,8 +340,8 @@ static void ln_fwd_t(const bf16_t* y, const bf16_t* res, const bf16_t* gamma, co
 
 void launch_ln_fwd(const bf16_t* y, const bf16_t* res, const bf16_t* gamma, const bf16_t* beta, bf16_t* z,
                    bf16_t* out, float* mean, float* rstd, int rows, int H, float eps, double p, uint64_t seed,
-                   hipStream_t st) {
-  DropoutParams dp = make_dropout(p, seed);
+                   hipStream_t st, uint32_t row_mul) {
+  DropoutParams dp = make_dropout(p, seed, row_mul);
   int nch = (H / 4 + 63) / 64;
   if (nch <= 1) ln_fwd_t<1>(y, res, gamma, beta, z, out, mean, rstd, rows, H, eps, dp, st);
   else if (nch <= 2) ln_fwd_t<2>(y, res, gamma, beta, z, out, mean, rstd, rows, H, eps, dp, st);
@@ -364,7 +367,11 @@ static void ln_bwd_t(const bf16_t* dout, const bf16_t* z, const float* mean, con
   const int blocks = (waves + kLnWaves - 1) / kLnWaves;
   // dbias sums the gradient that enters the GEMM: dy (or dz, which equals dy when there is no dropout)
   bf16_t* ysink = dy ? dy : nullptr;
-  if (qfmt == 0)
+  if (dp.row_mul != 1) {
+    if (qfmt >= 0) abort();  // the fp8 variants take no row multiplier
+    hipLaunchKernelGGL((ln_bwd_fused_kernel<NCH, -1, true>), dim3(blocks), dim3(256), 0, st, dout, z, mean, rstd, gamma,
+                       dz, ysink, dres_add, dgamma, dbeta, dbias, rows, H, rpw, dp, q8o);
+  } else if (qfmt == 0)
     hipLaunchKernelGGL((ln_bwd_fused_kernel<NCH, 0>), dim3(blocks), dim3(256), 0, st, dout, z, mean, rstd, gamma, dz,
                        ysink, dres_add, dgamma, dbeta, dbias, rows, H, rpw, dp, q8o);
   else if (qfmt == 1)
@@ -414,8 +421,8 @@ void launch_ln_bwd_q8(const bf16_t* dout, const bf16_t* z, const float* mean, co
 
 void launch_ln_bwd(const bf16_t* dout, const bf16_t* z, const float* mean, const float* rstd, const bf16_t* gamma,
                    bf16_t* dz, bf16_t* dy, const bf16_t* dres_add, float* dgamma, float* dbeta, float* dbias,
-                   int rows, int H, double p, uint64_t seed, hipStream_t st) {
-  DropoutParams dp = make_dropout(p, seed);
+                   int rows, int H, double p, uint64_t seed, hipStream_t st, uint32_t row_mul) {
+  DropoutParams dp = make_dropout(p, seed, row_mul);
   int nch = (H / 4 + 63) / 64;
   if (nch <= 1) ln_bwd_t<1>(dout, z, mean, rstd, gamma, dz, dy, dres_add, dgamma, dbeta, dbias, rows, H, dp, st);
   else if (nch <= 2) ln_bwd_t<2>(dout, z, mean, rstd, gamma, dz, dy, dres_add, dgamma, dbeta, dbias, rows, H, dp, st);

@@ -76,9 +76,15 @@ class Encoder(nn.Module):
         self.layers = nn.ModuleList([EncoderLayer(cfg) for _ in range(cfg.num_hidden_layers)])
 
     def forward(self, input_ids, attention_mask, token_type_ids, rng, training, *, cu_seqlens=None, max_seqlen=None,
-                position_ids=None) -> torch.Tensor:
+                position_ids=None, first_token_only=False) -> torch.Tensor:
         """Padded: ``input_ids [B, S]`` -> ``[B, S, H]``. Packed (``cu_seqlens`` given, data/packing.py):
-        ``input_ids`` / ``position_ids`` ``[1, T]``, no attention mask -> ``[T, H]``."""
+        ``input_ids`` / ``position_ids`` ``[1, T]``, no attention mask -> ``[T, H]``.
+
+        ``first_token_only``: the caller reads only the first-token row of each sequence (the classification heads).
+        The last layer then runs everything after its attention scores on those B rows and the result is
+        ``[B, 1, H]`` -- where ``ops.attn_block_cls_ok`` takes the tensors (padded batch, even S, reference ops or
+        bf16 HIP ops with fp8 off) and ``HSD_CLS_ROWS_ONLY`` is not 0; otherwise, and always without the flag, all
+        hidden states ``[B, S, H]``."""
         if cu_seqlens is not None:
             return self._forward_packed(input_ids, attention_mask, token_type_ids, rng, training, cu_seqlens,
                                         max_seqlen, position_ids)
@@ -87,9 +93,12 @@ class Encoder(nn.Module):
         h = self.embeddings(input_ids, token_type_ids, rng, training, q8_for=first_qkv).view(B * S, -1)
         mask_bias = ops.key_mask_bias(attention_mask) if attention_mask is not None else None
         n = len(self.layers)
+        prune = bool(first_token_only and n and ops.CLS_ROWS_ONLY
+                     and ops.attn_block_cls_ok(h, self.layers[-1].qkv_weight, B, S, self.cfg.num_attention_heads))
         for i, layer in enumerate(self.layers):
-            h = layer(h, mask_bias, B, S, rng, training, self.layers[i + 1].qkv_weight if i + 1 < n else None)
-        return h.view(B, S, -1)
+            h = layer(h, mask_bias, B, S, rng, training, self.layers[i + 1].qkv_weight if i + 1 < n else None,
+                      first_token_only=prune and i == n - 1)
+        return h.view(B, 1 if prune else S, -1)
 
     def _forward_packed(self, input_ids, attention_mask, token_type_ids, rng, training, cu_seqlens, max_seqlen,
                         position_ids) -> torch.Tensor:
@@ -220,7 +229,7 @@ class TransformerForSequenceClassification(_Base):
         c = self.cfg
         training = self.training
         h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, training, cu_seqlens=cu_seqlens,
-                         max_seqlen=max_seqlen, position_ids=position_ids)
+                         max_seqlen=max_seqlen, position_ids=position_ids, first_token_only=cu_seqlens is None)
         if cu_seqlens is not None:
             # packed [T, H]: the first-token row of sequence b is row cu_seqlens[b]
             h = h.index_select(0, cu_seqlens[:-1].long()).unsqueeze(1)  # [B, 1, H]

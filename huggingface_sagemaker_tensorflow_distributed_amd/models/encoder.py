@@ -48,14 +48,25 @@ class EncoderLayer(nn.Module):
 
     def forward(self, h: torch.Tensor, mask_bias: Optional[torch.Tensor], batch: int, seq: int,
                 rng: DropoutSeeds, training: bool, next_qkv: Optional[torch.Tensor] = None, *,
-                cu_seqlens: Optional[torch.Tensor] = None, max_seqlen: int = 0) -> torch.Tensor:
+                cu_seqlens: Optional[torch.Tensor] = None, max_seqlen: int = 0,
+                first_token_only: bool = False) -> torch.Tensor:
         """``next_qkv``: the next layer's QKV weight (fp8 path: this layer's last LayerNorm quantises for it).
-        ``cu_seqlens`` / ``max_seqlen``: ``h`` is a packed ``[T, H]`` buffer (data/packing.py)."""
+        ``cu_seqlens`` / ``max_seqlen``: ``h`` is a packed ``[T, H]`` buffer (data/packing.py).
+        ``first_token_only`` (padded batches, the last layer of a classification model): K and V at every position,
+        everything after the attention scores on the first-token row of each sequence -> ``[B, H]``; the dropout seeds
+        are drawn in the same order and the first-token rows see the same masks."""
         c = self.cfg
         p_h = c.hidden_dropout_prob if training else 0.0
         p_a = c.attention_probs_dropout_prob if training else 0.0
         seed_a = rng.next() if p_a else 0
         seed_h1 = rng.next() if p_h else 0
+        if first_token_only:
+            h1 = ops.attn_block_cls(h, self.qkv_weight, self.qkv_bias, self.attn_out_weight, self.attn_out_bias,
+                                    self.ln1_weight, self.ln1_bias, c.layer_norm_eps, mask_bias, batch, seq,
+                                    c.num_attention_heads, p_a, seed_a, p_h, seed_h1)
+            seed_h2 = rng.next() if p_h else 0
+            return ops.ffn_block(h1, self.ffn1_weight, self.ffn1_bias, self.ffn2_weight, self.ffn2_bias,
+                                 self.ln2_weight, self.ln2_bias, c.layer_norm_eps, p_h, seed_h2, drop_row_mul=seq)
         h1 = ops.attn_block(h, self.qkv_weight, self.qkv_bias, self.attn_out_weight, self.attn_out_bias,
                             self.ln1_weight, self.ln1_bias, c.layer_norm_eps, mask_bias, batch, seq,
                             c.num_attention_heads, p_a, seed_a, p_h, seed_h1, q8_next=self.ffn1_weight,

@@ -8,7 +8,8 @@
 * CPU tensors -> :mod:`.reference` (plain torch; also the numerics oracle for the kernel tests).
 
 ``HSD_OPS=torch`` forces the reference path on GPU (only for A/B measurements of the kernels); ``HSD_FP32_OPS=torch``
-does so for fp32 tensors only.
+does so for fp32 tensors only. ``HSD_CLS_ROWS_ONLY=0`` keeps the last encoder layer of a sequence-classification
+model on all rows (:func:`attn_block_cls`; tests and same-process A/Bs).
 """
 from __future__ import annotations
 
@@ -21,6 +22,8 @@ from . import reference as _ref
 
 _FORCE_TORCH = os.environ.get("HSD_OPS", "").lower() == "torch"
 _FP32_TORCH = os.environ.get("HSD_FP32_OPS", "").lower() == "torch"
+# the last encoder layer of a sequence-classification model on its first-token rows only (attn_block_cls)
+CLS_ROWS_ONLY = os.environ.get("HSD_CLS_ROWS_ONLY", "1").strip().lower() not in ("0", "off", "false")
 
 
 def _hip(x: torch.Tensor) -> bool:
@@ -99,13 +102,42 @@ def layer_norm(x, w, b, eps):
     return _ref.layer_norm(x, w, b, eps)
 
 
-def dense_residual_ln(x, w, b, residual, ln_w, ln_b, eps, p, seed):
-    """``LN(dropout(x Wᵀ + b) + residual)`` — the post-LN block tail."""
+def dense_residual_ln(x, w, b, residual, ln_w, ln_b, eps, p, seed, row_mul=1):
+    """``LN(dropout(x Wᵀ + b) + residual)`` — the post-LN block tail. ``row_mul``: row r is row ``r * row_mul`` of the
+    dropout site (ops/rng.py keep_mask)."""
     if _hip(x):
-        return _hipmod().dense_residual_ln(x, w, b, residual, ln_w, ln_b, eps, p, seed)
-    if _hip32(x) and w.shape[0] % 4 == 0 and w.shape[0] <= 1024:
+        return _hipmod().dense_residual_ln(x, w, b, residual, ln_w, ln_b, eps, p, seed, row_mul)
+    if row_mul == 1 and _hip32(x) and w.shape[0] % 4 == 0 and w.shape[0] <= 1024:
         return _hip32mod().dense_residual_ln(x, w, b, residual, ln_w, ln_b, eps, p, seed)
-    return _ref.layer_norm(_ref.linear_dropout_residual(x, w, b, residual, p, seed, p > 0), ln_w, ln_b, eps)
+    return _ref.layer_norm(_ref.linear_dropout_residual(x, w, b, residual, p, seed, p > 0, row_mul), ln_w, ln_b, eps)
+
+
+def attn_block_cls_ok(h, qkv_w, batch, seq, heads) -> bool:
+    """Whether :func:`attn_block_cls` takes these tensors (``models.bert.Encoder`` asks before it prunes the last
+    layer): an even S, and either the reference ops (CPU tensors, ``HSD_OPS=torch``) or the bf16 HIP ops with fp8 off
+    (``ops/hip.py attn_block_cls_ok``). fp32 GPU tensors keep the full layer."""
+    if seq % 2:
+        return False
+    if not h.is_cuda or _FORCE_TORCH:
+        return True
+    return _hip(h) and _hipmod().attn_block_cls_ok(h, qkv_w, batch, seq, heads)
+
+
+def attn_block_cls(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, batch, seq, heads, p_attn, seed_attn,
+                   p_hidden, seed_hidden):
+    """:func:`attn_block` for the first-token row of each sequence only: ``h [B·S, H]`` -> ``[B, H]``, the rows
+    ``b·S`` of what :func:`attn_block` returns (same function, same dropout bits; bf16 / fp32 rounding differs). The
+    last encoder layer of a sequence-classification model: its head reads nothing else. K and V are computed at
+    every position, everything after the scores for one query per sequence; the hidden dropout draws row ``b·S`` of
+    the ``[B·S, H]`` site (``row_mul = seq``)."""
+    if _hip(h):
+        return _hipmod().attn_block_cls(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, batch, seq, heads,
+                                        p_attn, seed_attn, p_hidden, seed_hidden)
+    qkv = _ref.linear(h.reshape(batch * seq, -1), qkv_w, qkv_b)
+    ctx0 = _ref.attention_cls(qkv, mask_bias, batch, seq, heads, p_attn, seed_attn, p_attn > 0)
+    x0 = h.reshape(batch, seq, -1)[:, 0]
+    z = _ref.linear_dropout_residual(ctx0, out_w, out_b, x0, p_hidden, seed_hidden, p_hidden > 0, seq)
+    return _ref.layer_norm(z, ln_w, ln_b, eps)
 
 
 def attn_block(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, batch, seq, heads, p_attn, seed_attn,
@@ -133,14 +165,15 @@ def attn_block(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, batch,
     return dense_residual_ln(ctx, out_w, out_b, h, ln_w, ln_b, eps, p_hidden, seed_hidden)
 
 
-def ffn_block(h, w1, b1, w2, b2, ln_w, ln_b, eps, p, seed, q8_next=None):
-    """Feed-forward sub-block: ``LN(dropout(gelu(h W1ᵀ + b1) W2ᵀ + b2) + h)``."""
+def ffn_block(h, w1, b1, w2, b2, ln_w, ln_b, eps, p, seed, q8_next=None, drop_row_mul=1):
+    """Feed-forward sub-block: ``LN(dropout(gelu(h W1ᵀ + b1) W2ᵀ + b2) + h)``. ``drop_row_mul``: row r of ``h`` is row
+    ``r * drop_row_mul`` of the dropout site (the first-token rows after :func:`attn_block_cls`)."""
     if _hip(h) and h.dtype == torch.bfloat16:
-        return _hipmod().ffn_block(h, w1, b1, w2, b2, ln_w, ln_b, eps, p, seed, q8_next)
-    if _hip32(h) and _hip32mod().ffn_block_ok(h, w1):
+        return _hipmod().ffn_block(h, w1, b1, w2, b2, ln_w, ln_b, eps, p, seed, q8_next, drop_row_mul)
+    if drop_row_mul == 1 and _hip32(h) and _hip32mod().ffn_block_ok(h, w1):
         return _hip32mod().ffn_block(h, w1, b1, w2, b2, ln_w, ln_b, eps, p, seed)
     a = linear_gelu(h, w1, b1)
-    return dense_residual_ln(a, w2, b2, h, ln_w, ln_b, eps, p, seed)
+    return dense_residual_ln(a, w2, b2, h, ln_w, ln_b, eps, p, seed, drop_row_mul)
 
 
 def attention(qkv, mask_bias, batch, seq, heads, p, seed):
@@ -187,7 +220,8 @@ def cross_entropy(logits, labels):
 
 
 def cls_head(h, w1, b1, w2, b2, labels, act: str, p_in: float, seed_in: int, p: float, seed: int):
-    """Classification head on the first token of ``h`` [B, S, H] (+ the loss when ``labels`` is given).
+    """Classification head on the first token of ``h`` [B, S, H] (+ the loss when ``labels`` is given). ``S`` is 1 when
+    the encoder already pruned its last layer to the first-token rows (``Encoder.forward(first_token_only=True)``).
 
     Returns ``logits`` without labels, else ``(loss, logits)`` with the argmax-hit count on ``loss._hsd_correct``
     and the fused {mean loss, hits, rows, loss sum} on ``loss._hsd_stats`` (HIP path). On GPUs the dense layer runs on gemm2 and everything after it (activation, dropout, classifier, CE,

@@ -199,13 +199,19 @@ def _end_of_backward() -> None:
     join_side_streams()
 
 
+def _wgrad_plan(N: int, K: int, T: int):
+    """``_C.gemm2_wgrad_plan`` for token counts the TT kernels tile (one 64-token k-tile at least): the B first-token
+    rows of a small batch (:class:`_AttnBlockCls`) go to the 128-tile kernel's atomic epilogue instead."""
+    return _C.gemm2_wgrad_plan(N, K, T) if T >= 64 else (False, 0, 0)
+
+
 def _launch_wgrad(s, g: "_Grad", dy, x, dyq, xq):
     """g += dyᵀ·x on the side stream ``s`` (already ordered after dy / x); the g.done() result."""
     N, K, T = dy.shape[1], x.shape[1], dy.shape[0]
     if g.buf is g.mg and _wgrad8_ok(dyq, xq, N, K, T):
         _wgrad8(g.buf, dyq, xq, N, K, T, s)
         return None
-    ok, sp, ws = _C.gemm2_wgrad_plan(N, K, T) if g.buf is g.mg else (False, 0, 0)
+    ok, sp, ws = _wgrad_plan(N, K, T) if g.buf is g.mg else (False, 0, 0)
     if ok:
         # the common case without any Python stream plumbing: TT GEMM (+ split-K reduce) launched on the side stream
         # (fp32 atomics per K-split instead of slabs + one reduce pass: headline -5.7 %, bert-large B = 64 -13.5 %,
@@ -225,6 +231,12 @@ def wgrad_done(g: "_Grad", dy: torch.Tensor, x: torch.Tensor, dyq=None, xq=None)
     (One fork per weight gradient: deferring the first weight gradient of each block half to the second one's fork,
     one compute-stream event instead of two, measured 0.8 % slower at bert-large B = 8 and 0.2 % at the headline --
     the side stream starts later -- profiles/r6/fork_merge_defer_ab_r6.log.)"""
+    if (dy.shape[0] < 64 and dyq is None and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+            and x.shape[1] % 4 == 0 and x.stride(0) % 4 == 0):
+        # under one 64-token k-tile (the B first-token rows of a small batch, :class:`_AttnBlockCls`): the small-T
+        # kernel on the compute stream -- a few us; the side stream's fork and the TT kernels' split plan buy nothing
+        _C.small_wgrad(dy, x, g.buf.view(dy.shape[1], x.shape[1]))
+        return g.done()
     s = side_stream(dy.device) if (g.mg is not None and g.buf is g.mg and _use_side_stream(dy.shape[0])) else None
     if s is None:
         gemm_wgrad_(g, dy, x, dyq, xq)
@@ -379,7 +391,7 @@ def linear_gelu(x, w, b):
 # ------------------------------------------------------------------------------------------ LN tails
 class _DenseResidualLN(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, res, ln_w, ln_b, eps, p, seed):
+    def forward(ctx, x, w, b, res, ln_w, ln_b, eps, p, seed, row_mul=1):
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         y, _ = _dense_fwd(x2, w, b)
         rows, H = y.shape
@@ -387,9 +399,10 @@ class _DenseResidualLN(torch.autograd.Function):
         out = torch.empty_like(y)
         mean = torch.empty(rows, dtype=torch.float32, device=y.device)
         rstd = torch.empty_like(mean)
-        _C.ln_fwd(y, res.reshape(rows, H), ln_w, ln_b, z, out, mean, rstd, float(eps), float(p), _s64(seed))
+        _C.ln_fwd(y, res.reshape(rows, H).contiguous(), ln_w, ln_b, z, out, mean, rstd, float(eps), float(p),
+                  _s64(seed), int(row_mul))
         ctx.save_for_backward(x2, w, b, z, mean, rstd, ln_w, ln_b)
-        ctx.p, ctx.seed, ctx.xshape = float(p), seed, x.shape
+        ctx.p, ctx.seed, ctx.xshape, ctx.row_mul = float(p), seed, x.shape, int(row_mul)
         return out.view(res.shape)
 
     @staticmethod
@@ -400,18 +413,20 @@ class _DenseResidualLN(torch.autograd.Function):
         dy = torch.empty_like(z)
         if ctx.p > 0:
             dz = torch.empty_like(z)
-            _C.ln_bwd(dout2, z, mean, rstd, ln_w, dz, dy, None, gg.buf, gbe.buf, gb.buf, ctx.p, _s64(ctx.seed))
+            _C.ln_bwd(dout2, z, mean, rstd, ln_w, dz, dy, None, gg.buf, gbe.buf, gb.buf, ctx.p, _s64(ctx.seed),
+                      ctx.row_mul)
         else:
             _C.ln_bwd(dout2, z, mean, rstd, ln_w, None, dy, None, gg.buf, gbe.buf, gb.buf, 0.0, 0)
             dz = dy
         gln_w, gln_b = gg.done(), gbe.done()
         dx = _dense_dgrad(dy, w, bf16_only=False).view(ctx.xshape) if ctx.needs_input_grad[0] else None
         _dense_wgrad_(gw, dy, x2, bf16_only=False)
-        return dx, gw.done(), gb.done(), dz.view(dout.shape), gln_w, gln_b, None, None, None
+        return dx, gw.done(), gb.done(), dz.view(dout.shape), gln_w, gln_b, None, None, None, None
 
 
-def dense_residual_ln(x, w, b, residual, ln_w, ln_b, eps, p, seed):
-    return _DenseResidualLN.apply(x, w, b, residual, ln_w, ln_b, eps, p, seed)
+def dense_residual_ln(x, w, b, residual, ln_w, ln_b, eps, p, seed, row_mul=1):
+    """``row_mul``: row r of the output is row ``r * row_mul`` of the dropout site (ops/rng.py keep_mask)."""
+    return _DenseResidualLN.apply(x, w, b, residual, ln_w, ln_b, eps, p, seed, row_mul)
 
 
 class _LayerNorm(torch.autograd.Function):
@@ -821,16 +836,20 @@ def _q8_kw(q8):
     return {"q8": q, "q8_amax": st[0:1], "q8_sinv": sinv, "q8_track": st[1:2], "q8fmt": fmt}
 
 
-def gemm_fwd(x, w, epi, bias=None, aux=None, out2=None, p=0.0, seed=0, xq=None, q8_for=None, q8_only=False):
+def gemm_fwd(x, w, epi, bias=None, aux=None, out2=None, p=0.0, seed=0, xq=None, q8_for=None, q8_only=False,
+             row_mul=1):
     """y[T, N] = x[T, K] · w[N, K]ᵀ with epilogue (gemm2 8-phase kernel; 128-tile kernel for odd shapes;
     gemm8 fp8 kernel when fp8 is on and the weight has an fp8 copy). ``xq``: x's fp8 copy (q, sinv) already
     written by its producer. ``q8_for``: the weight of the fp8 GEMM that consumes the output (``out2`` for the
     two-output GELU epilogue): on the fp8 path the epilogue writes that GEMM's fp8 input copy too. ``q8_only``: the
     caller's consumers of ``out2`` all take that fp8 copy, so its bf16 values are not stored when the copy is written
-    (returned ``y`` then carries ``_hsd_q8_only = True``; ``out2``'s contents are undefined)."""
+    (returned ``y`` then carries ``_hsd_q8_only = True``; ``out2``'s contents are undefined). ``row_mul``
+    (EPI_BIAS_DROP_RES, bf16 kernels only): output row r is row ``r * row_mul`` of the dropout site."""
     y = torch.empty((x.shape[0], w.shape[0]), dtype=x.dtype, device=x.device)
     wq = _fp8_w(w, "_hsd_q")
     if wq is not None and _C.gemm8_supported(epi, x.shape[0], w.shape[0], x.shape[1]):
+        if row_mul != 1:
+            raise ValueError("gemm_fwd: the fp8 kernels take no dropout row multiplier")
         qx, sx = xq if xq is not None else quant_fp8(x, FP8_E4M3, getattr(w, "_hsd_fp8_x", None))
         q8 = _q8_out(y, q8_for, "_hsd_fp8_x", "_hsd_q", FP8_E4M3) \
             if q8_for is not None and epi in (EPI_BIAS_GELU, EPI_BIAS_GELU_D) and out2 is not None else None
@@ -843,9 +862,10 @@ def gemm_fwd(x, w, epi, bias=None, aux=None, out2=None, p=0.0, seed=0, xq=None, 
             y._hsd_q8_only = True
         return y
     if _nt_ok(x.shape[0], w.shape[0], x.shape[1], epi):
-        _C.gemm2(x, w, y, 0, 0, epi, bias, aux, out2, float(p), _s64(seed), 0, None, None)  # 0: auto split-K
+        _C.gemm2(x, w, y, 0, 0, epi, bias, aux, out2, float(p), _s64(seed), 0, None, None,  # 0: auto split-K
+                 row_mul=int(row_mul))
     else:
-        _C.gemm(x, w, y, 0, 0, epi, bias, aux, out2, float(p), _s64(seed), 1)
+        _C.gemm(x, w, y, 0, 0, epi, bias, aux, out2, float(p), _s64(seed), 1, int(row_mul))
     return y
 
 
@@ -971,7 +991,7 @@ def gemm_wgrad_(g: "_Grad", dy, x, dyq=None, xq=None):
     if _wgrad8_ok(dyq, xq, N, K, T):
         _wgrad8(g.buf, dyq, xq, N, K, T)
         return
-    ok, sp, ws = _C.gemm2_wgrad_plan(N, K, T)
+    ok, sp, ws = _wgrad_plan(N, K, T)
     if ok:
         _C.gemm2(dy, x, g.buf, 1, 1, EPI_F32_SLAB, None, None, None, 0.0, 0, sp, _workspace(ws, dy.device), None)
     else:
@@ -997,19 +1017,23 @@ def _ln_fwd(z, w, b, eps, q8_for=None):
     return out, mean, rstd
 
 
-def _ln_bwd(dout2, z, mean, rstd, ln_w, dz, dy, g_lnw, g_lnb, g_b, p, seed, consumer_w, q8_only=False):
+def _ln_bwd(dout2, z, mean, rstd, ln_w, dz, dy, g_lnw, g_lnb, g_b, p, seed, consumer_w, q8_only=False, row_mul=1):
     """LN backward into dy (and dz with dropout); returns dy's fp8 copy (q, sinv) when ``consumer_w``'s dgrad runs
     fp8 on a calibrated site (quantised in the same pass), else None. ``q8_only`` (dropout on, so dz is its own
-    buffer): every consumer of dy takes that fp8 copy, and dy's bf16 values are not stored."""
+    buffer): every consumer of dy takes that fp8 copy, and dy's bf16 values are not stored. ``row_mul``: row r of z is
+    row ``r * row_mul`` of the dropout site (bf16 kernel only)."""
     st = _site_ready(consumer_w, "_hsd_fp8_g", "_hsd_qt")
     rows, H = z.shape
     if st is not None and H <= 1024 and _C.gemm8_supported(EPI_STORE, rows, consumer_w.shape[1], H):
+        if row_mul != 1:
+            raise ValueError("_ln_bwd: the fp8 kernel takes no dropout row multiplier")
         q = torch.empty((rows, H), dtype=torch.uint8, device=z.device)
         sinv = torch.empty(1, dtype=torch.float32, device=z.device)
         _C.ln_bwd_q8(dout2, z, mean, rstd, ln_w, dz, dy, g_lnw.buf, g_lnb.buf, g_b.buf, p, _s64(seed) if p > 0 else 0,
                      q, st[0:1], sinv, st[1:2], _FP8["grad_fmt"], q8_only=bool(q8_only and p > 0 and dz is not None))
         return q, sinv
-    _C.ln_bwd(dout2, z, mean, rstd, ln_w, dz, dy, None, g_lnw.buf, g_lnb.buf, g_b.buf, p, _s64(seed) if p > 0 else 0)
+    _C.ln_bwd(dout2, z, mean, rstd, ln_w, dz, dy, None, g_lnw.buf, g_lnb.buf, g_b.buf, p, _s64(seed) if p > 0 else 0,
+              int(row_mul))
     return None
 
 
@@ -1120,13 +1144,89 @@ def attn_block(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, B, S, 
                             p_h, seed_h, q8_next)
 
 
+class _AttnBlockCls(torch.autograd.Function):
+    """:class:`_AttnBlock` of the LAST encoder layer of a sequence-classification model, whose head reads only the
+    first-token row of each sequence: the QKV projection runs over all T = B·S rows (K and V are needed at every
+    position), everything after the attention scores on the B first-token rows. Returns ``[B, H]``.
+
+    Forward: QKV GEMM -> one-query attention (attention_cls.hip) -> out-projection with the dropout + residual
+    epilogue (residual = the first-token rows of ``h`` read in place, row stride S·H) -> LN, on B rows. Backward:
+    LN-bwd -> Wo wgrad / dgrad on B rows -> one-query attention backward, which writes the full dqkv (zeros in the dQ
+    rows that are not first tokens) and the QKV bias gradient -> Wqkv wgrad over T rows -> dgrad with a plain store ->
+    the first-token rows' residual gradient added in place. Hidden-dropout row b is row b·S of the full path's
+    ``[T, H]`` site (``row_mul = S``), so the masks are the ones :class:`_AttnBlock` draws for those rows."""
+
+    @staticmethod
+    def forward(ctx, h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, B, S, heads, p_a, seed_a, p_h,
+                seed_h):
+        h2d = h.reshape(-1, h.shape[-1])
+        H = out_w.shape[0]
+        qkv = gemm_fwd(h2d, qkv_w, EPI_BIAS, bias=qkv_b)
+        ctx0 = torch.empty((B, H), dtype=h.dtype, device=h.device)
+        lse = torch.empty(B * heads, dtype=torch.float32, device=h.device)
+        mb = mask_bias.contiguous().float() if mask_bias is not None else None
+        _C.attn_cls_fwd(qkv, mb, ctx0, lse, B, S, heads, float(p_a), _s64(seed_a))
+        x0 = h2d.view(B, S * H)[:, :H]  # the first-token rows, read in place
+        z = gemm_fwd(ctx0, out_w, EPI_BIAS_DROP_RES, bias=out_b, aux=x0, p=p_h, seed=seed_h, row_mul=S)
+        out, mean, rstd = _ln_fwd(z, ln_w, ln_b, eps)
+        ctx.save_for_backward(h2d, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, qkv, ctx0, lse, z, mean, rstd,
+                              mb if mb is not None else lse)
+        ctx.cfg = (B, S, heads, float(p_a), seed_a, float(p_h), seed_h, mb is not None)
+        ctx.hshape = h.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (h2d, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, qkv, ctx0, lse, z, mean, rstd, mb) = ctx.saved_tensors
+        B, S, heads, p_a, seed_a, p_h, seed_h, has_mask = ctx.cfg
+        dout2 = dout.reshape(z.shape).contiguous()
+        g_lnw, g_lnb, g_ow, g_ob = _Grad(ln_w), _Grad(ln_b), _Grad(out_w), _Grad(out_b)
+        dy = torch.empty_like(z)
+        dz = torch.empty_like(z) if p_h > 0 else None
+        _ln_bwd(dout2, z, mean, rstd, ln_w, dz, dy, g_lnw, g_lnb, g_ob, p_h, seed_h, None, row_mul=S)
+        if dz is None:
+            dz = dy
+        r_lnw, r_lnb, r_ob = g_lnw.done(), g_lnb.done(), g_ob.done()
+        r_ow = wgrad_done(g_ow, dy, ctx0)
+        dctx = gemm_dgrad(dy, out_w)
+        dqkv = torch.empty_like(qkv)
+        g_qw, g_qb = _Grad(qkv_w), _Grad(qkv_b)
+        # every dqkv element is written (zeros in the dQ rows of the other tokens); the QKV bias gradient comes out
+        # of the same kernel
+        _C.attn_cls_bwd(qkv, mb if has_mask else None, dctx, lse, dqkv, B, S, heads, p_a, _s64(seed_a), g_qb.buf)
+        r_qb = g_qb.done()
+        r_qw = wgrad_done(g_qw, dqkv, h2d)
+        dh = None
+        if ctx.needs_input_grad[0]:
+            # the residual gradient is zero off the first-token rows: plain store, then those B rows += dz
+            dh = gemm_dgrad(dqkv, qkv_w, EPI_STORE)
+            _C.add_rows_strided(dh, dz, S)
+            dh = dh.view(ctx.hshape)
+        return (dh, r_qw, r_qb, r_ow, r_ob, r_lnw, r_lnb, None, None, None, None, None, None, None, None, None)
+
+
+def attn_block_cls_ok(h, qkv_w, B, S, heads) -> bool:
+    """Whether :func:`attn_block_cls` takes this call: bf16, head dim 64, even S, fp8 off, and a batch that is a
+    multiple of 8 (the row granularity of the GEMM that takes row counts the 256-row kernels do not tile)."""
+    return (h.dtype == torch.bfloat16 and qkv_w.shape[0] == 3 * heads * 64 and S % 2 == 0 and B % 8 == 0
+            and not _FP8["on"] and bool(_C.attn_cls_supported(S)) and (S * qkv_w.shape[1]) % 8 == 0)
+
+
+def attn_block_cls(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, B, S, heads, p_a, seed_a, p_h, seed_h):
+    """The attention sub-block of the last layer on the first-token rows: ``h [B·S, H]`` -> ``[B, H]``."""
+    if not attn_block_cls_ok(h, qkv_w, B, S, heads):
+        raise ValueError("attn_block_cls: unsupported shape / dtype (attn_block_cls_ok)")
+    return _AttnBlockCls.apply(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, B, S, heads, p_a, seed_a,
+                               p_h, seed_h)
+
+
 class _FFNBlock(torch.autograd.Function):
     """h2 = LN(dropout(gelu(h W1ᵀ + b1) W2ᵀ + b2) + h). Forward: 2 GEMMs (bias+GELU epilogue writing
     pre-activation and activation; bias+dropout+residual epilogue) + LN. Backward: LN-bwd (+dropout,
     + b2 grad) -> W2 wgrad -> dgrad with gelu' epilogue -> b1 colsum -> W1 wgrad -> dgrad + residual."""
 
     @staticmethod
-    def forward(ctx, h, w1, b1, w2, b2, ln_w, ln_b, eps, p, seed, q8_next=None):
+    def forward(ctx, h, w1, b1, w2, b2, ln_w, ln_b, eps, p, seed, q8_next=None, drop_row_mul=1):
         h2d = h.reshape(-1, h.shape[-1])
         xq = _take_q8(h2d)
         act = torch.empty((h2d.shape[0], w1.shape[0]), dtype=h.dtype, device=h.device)
@@ -1147,10 +1247,11 @@ class _FFNBlock(torch.autograd.Function):
         act_missing = getattr(pre, "_hsd_q8_only", False)
         if act_missing and actq is None:
             raise RuntimeError("FFN forward: the activation's fp8 copy was not handed over")
-        z = gemm_fwd(act, w2, EPI_BIAS_DROP_RES, bias=b2, aux=h2d, p=p, seed=seed, xq=actq)
+        z = gemm_fwd(act, w2, EPI_BIAS_DROP_RES, bias=b2, aux=h2d, p=p, seed=seed, xq=actq, row_mul=drop_row_mul)
         out, mean, rstd = _ln_fwd(z, ln_w, ln_b, eps, q8_for=q8_next)
         ctx.save_for_backward(h2d, w1, b1, w2, b2, ln_w, ln_b, pre, act, z, mean, rstd)
         ctx.cfg = (float(p), seed, keep_grad)
+        ctx.drop_row_mul = int(drop_row_mul)
         ctx.act_missing = act_missing
         ctx.q8 = (xq, actq) if _FP8_WGRAD else (None, None)
         return out.view(h.shape)
@@ -1173,7 +1274,8 @@ class _FFNBlock(torch.autograd.Function):
         # backward stores only dy's fp8 copy
         dy_q8 = bool(_Q8_ONLY and _FP8["on"] and _FP8_WGRAD and actq is not None and _C.gemm8_wgrad_supported(H, I, T)
                      and _fp8_dgrad_ok(w2, EPI_MUL if keep_grad else EPI_DGELU, T))
-        dyq = _ln_bwd(dout2, z, mean, rstd, ln_w, dz, dy, g_lnw, g_lnb, g_b2, p, seed, w2, q8_only=dy_q8)
+        dyq = _ln_bwd(dout2, z, mean, rstd, ln_w, dz, dy, g_lnw, g_lnb, g_b2, p, seed, w2, q8_only=dy_q8,
+                      row_mul=ctx.drop_row_mul)
         if dz is None:
             dz = dy
         r_lnw, r_lnb, r_b2 = g_lnw.done(), g_lnb.done(), g_b2.done()
@@ -1194,12 +1296,14 @@ class _FFNBlock(torch.autograd.Function):
         r_w1 = wgrad_done(g_w1, da, h2d, daq, hq)
         dh = gemm_dgrad(da, w1, EPI_RES, aux=dz, dyq=daq) if ctx.needs_input_grad[0] else None
         return (dh.view(dout.shape) if dh is not None else None, r_w1, r_b1, r_w2, r_b2, r_lnw, r_lnb,
-                None, None, None, None)
+                None, None, None, None, None)
 
 
-def ffn_block(h, w1, b1, w2, b2, ln_w, ln_b, eps, p, seed, q8_next=None):
-    """``q8_next``: the next layer's QKV weight (its fp8 input copy is written by this block's LayerNorm)."""
-    return _FFNBlock.apply(h, w1, b1, w2, b2, ln_w, ln_b, eps, p, seed, q8_next)
+def ffn_block(h, w1, b1, w2, b2, ln_w, ln_b, eps, p, seed, q8_next=None, drop_row_mul=1):
+    """``q8_next``: the next layer's QKV weight (its fp8 input copy is written by this block's LayerNorm).
+    ``drop_row_mul``: row r of ``h`` is row ``r * drop_row_mul`` of the block's dropout site (the first-token rows of
+    the last layer, :func:`attn_block_cls`)."""
+    return _FFNBlock.apply(h, w1, b1, w2, b2, ln_w, ln_b, eps, p, seed, q8_next, drop_row_mul)
 
 
 # ------------------------------------------------------------------------------------------ attention mask

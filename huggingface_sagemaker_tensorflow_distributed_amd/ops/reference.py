@@ -16,10 +16,10 @@ import torch.nn.functional as F
 from .rng import keep_mask
 
 
-def dropout(x: torch.Tensor, p: float, seed: int, training: bool = True) -> torch.Tensor:
+def dropout(x: torch.Tensor, p: float, seed: int, training: bool = True, row_mul: int = 1) -> torch.Tensor:
     if not training or p <= 0.0:
         return x
-    m = keep_mask(seed, x.shape, p, device=x.device)
+    m = keep_mask(seed, x.shape, p, device=x.device, row_mul=row_mul)
     return x * m.to(x.dtype) * (1.0 / (1.0 - p))
 
 
@@ -45,13 +45,13 @@ def linear_gelu(x, w, b):
     return gelu(F.linear(x, w, b))
 
 
-def linear_dropout_residual(x, w, b, residual, p: float, seed: int, training: bool):
+def linear_dropout_residual(x, w, b, residual, p: float, seed: int, training: bool, row_mul: int = 1):
     """``dropout(x Wᵀ + b) + residual`` rounded ONCE to the output dtype (fp32 product and sum), as the HIP epilogues
     compute it (gemm_common.h / gemm.hip: bf16(fma(y, keep · scale, residual)) with y = bf16(x Wᵀ + b))."""
     y = F.linear(x, w, b)
     if not training or p <= 0.0:
         return y + residual
-    k = keep_mask(seed, y.shape, p, device=y.device).to(torch.float32) * (1.0 / (1.0 - p))
+    k = keep_mask(seed, y.shape, p, device=y.device, row_mul=row_mul).to(torch.float32) * (1.0 / (1.0 - p))
     return torch.addcmul(residual.float(), y.float(), k).to(y.dtype)
 
 
@@ -84,6 +84,24 @@ def attention(qkv: torch.Tensor, mask_bias: Optional[torch.Tensor], batch: int, 
     pr = dropout(pr, p, seed, training)
     o = torch.matmul(pr, v)  # [B,h,S,d]
     return o.permute(0, 2, 1, 3).reshape(batch * seq, H).to(qkv.dtype)
+
+
+def attention_cls(qkv: torch.Tensor, mask_bias: Optional[torch.Tensor], batch: int, seq: int, heads: int,
+                  p: float, seed: int, training: bool) -> torch.Tensor:
+    """:func:`attention` for the first query row of each sequence only: ``[B*S, 3H]`` -> ``[B, H]``. The same op
+    sequence on one query, and the dropout bits :func:`attention` draws for that row: row ``(b*heads + h)*S``."""
+    H3 = qkv.shape[-1]
+    H = H3 // 3
+    d = H // heads
+    x = qkv.view(batch, seq, 3, heads, d).permute(2, 0, 3, 1, 4).float()  # [3,B,h,S,d]
+    q, k, v = x[0][:, :, :1], x[1], x[2]
+    s = torch.matmul(q, k.transpose(-1, -2)) * (1.0 / math.sqrt(d))  # [B,h,1,S]
+    if mask_bias is not None:
+        s = s + mask_bias.view(batch, 1, 1, seq).float()
+    pr = torch.softmax(s, dim=-1)
+    pr = dropout(pr, p, seed, training, row_mul=seq)
+    o = torch.matmul(pr, v)  # [B,h,1,d]
+    return o.permute(0, 2, 1, 3).reshape(batch, H).to(qkv.dtype)
 
 
 def attention_varlen(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int, heads: int, p: float, seed: int,

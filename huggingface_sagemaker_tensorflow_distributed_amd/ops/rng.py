@@ -101,9 +101,10 @@ def pair_bits(key: int, rows: torch.Tensor, cps: torch.Tensor) -> torch.Tensor:
     return drop_fin(mix32((rows & M32) ^ key) ^ drop_col(cps & M32))
 
 
-def keep_mask(seed: int, shape, p: float, device=None) -> torch.Tensor:
+def keep_mask(seed: int, shape, p: float, device=None, row_mul: int = 1) -> torch.Tensor:
     """Boolean keep mask of a dropout site of ``shape`` (a tuple / torch.Size; the last dimension is the row width W)
-    with 64-bit ``seed``."""
+    with 64-bit ``seed``. ``row_mul``: row ``r`` of ``shape`` is row ``r * row_mul`` of the site (the first-token rows
+    ``[B, W]`` of a ``[B * S, W]`` site: ``row_mul = S``; ``common.h`` ``DropoutParams::row_mul``)."""
     if isinstance(shape, int):
         raise TypeError("keep_mask: pass the site's shape (its last dimension is the mask's row width), not numel")
     shape = tuple(int(d) for d in shape)
@@ -113,7 +114,7 @@ def keep_mask(seed: int, shape, p: float, device=None) -> torch.Tensor:
         numel *= d
     rows = numel // W if W else 0
     key = site_key(seed & M32, (seed >> 32) & M32)
-    r = torch.arange(rows, dtype=torch.int64, device=device).unsqueeze(1)
+    r = (torch.arange(rows, dtype=torch.int64, device=device) * int(row_mul)).unsqueeze(1)
     cp = torch.arange((W + 1) // 2, dtype=torch.int64, device=device).unsqueeze(0)
     h = pair_bits(key, r, cp)
     bits = torch.stack([h & 0xFFFF, h >> 16], dim=2).reshape(rows, -1)[:, :W]
