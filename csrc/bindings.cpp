@@ -1188,6 +1188,76 @@ void mask_bias(torch::Tensor mask, torch::Tensor out) {
                         cur_stream());
 }
 
+// mlm_mask.hip: dynamic MLM masking + ordered compaction (ops/rng.py "MLM mask"); every buffer is checked here so the
+// kernels index nothing they were not given
+static void check_i64_vec(const torch::Tensor& t, int64_t n, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kInt64 && t.numel() == n, "mlm_mask: ", what,
+              " must be a contiguous int64 GPU tensor of ", n, " elements");
+}
+static void check_i32_vec(const torch::Tensor& t, int64_t n, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kInt32 && t.numel() == n, "mlm_mask: ", what,
+              " must be a contiguous int32 GPU tensor of ", n, " elements");
+}
+
+void mlm_mask(torch::Tensor ids, c10::optional<torch::Tensor> attention_mask, c10::optional<torch::Tensor> labels_in,
+              torch::Tensor ids_out, torch::Tensor labels_out, torch::Tensor sel, torch::Tensor tgt, torch::Tensor inv,
+              torch::Tensor counts, torch::Tensor n_valid, torch::Tensor ws, int64_t seed, double p, int64_t mask_id,
+              std::vector<int64_t> special_ids, int64_t rand_lo, int64_t rand_hi, bool use_step_seed) {
+  const int64_t N = ids.numel();
+  const int64_t cap = sel.numel();
+  TORCH_CHECK(N >= 1 && N < (int64_t)1 << 31, "mlm_mask: 1 <= N < 2^31 tokens");
+  TORCH_CHECK(cap >= 1 && cap < (int64_t)1 << 31, "mlm_mask: 1 <= cap < 2^31");
+  TORCH_CHECK(p >= 0.0 && p <= 1.0, "mlm_mask: p in [0, 1]");
+  TORCH_CHECK(special_ids.size() <= 8, "mlm_mask: at most 8 special ids");
+  TORCH_CHECK(rand_lo >= 0 && rand_hi > rand_lo && rand_hi - rand_lo < (int64_t)1 << 31, "mlm_mask: rand_range");
+  check_i64_vec(ids, N, "input_ids");
+  if (attention_mask.has_value()) check_i64_vec(*attention_mask, N, "attention_mask");
+  if (labels_in.has_value()) check_i64_vec(*labels_in, N, "labels_in");
+  check_i64_vec(ids_out, N, "ids_out");
+  check_i64_vec(labels_out, N, "labels_out");
+  check_i64_vec(sel, cap, "sel");
+  check_i64_vec(tgt, cap, "tgt");
+  check_i32_vec(inv, N, "inv");
+  check_i32_vec(counts, 2, "counts");
+  check_i32_vec(ws, hsd::mlm_mask_blocks(N), "ws");
+  check_f32(n_valid, "n_valid");
+  TORCH_CHECK(n_valid.numel() == 1 && n_valid.is_contiguous(), "mlm_mask: n_valid is fp32 [1]");
+  hsd::MlmMaskParams q;
+  q.ids = ids.data_ptr<int64_t>();
+  q.attention_mask = OPT_I64(attention_mask);
+  q.labels_in = OPT_I64(labels_in);
+  q.ids_out = ids_out.data_ptr<int64_t>();
+  q.labels_out = labels_out.data_ptr<int64_t>();
+  q.sel = sel.data_ptr<int64_t>();
+  q.tgt = tgt.data_ptr<int64_t>();
+  q.inv = inv.data_ptr<int32_t>();
+  q.counts = counts.data_ptr<int32_t>();
+  q.n_valid = n_valid.data_ptr<float>();
+  q.ws = ws.data_ptr<int32_t>();
+  q.N = N;
+  q.cap = (int)cap;
+  q.seed_lo = (uint32_t)((uint64_t)seed & 0xFFFFFFFFull);
+  q.seed_hi = (uint32_t)((uint64_t)seed >> 32);
+  q.thr = (uint32_t)(p * 65536.0 + 0.5);
+  q.mask_id = mask_id;
+  q.rand_lo = rand_lo;
+  q.rand_hi = rand_hi;
+  q.n_special = (int)special_ids.size();
+  for (int k = 0; k < 8; ++k) q.special[k] = k < q.n_special ? special_ids[k] : -1;
+  q.dev_seed = nullptr;
+  hsd::launch_mlm_mask(q, use_step_seed, cur_stream());
+}
+
+void mlm_scatter_rows(torch::Tensor dx, torch::Tensor inv, torch::Tensor dh) {
+  check_bf16(dx, "dx"); check_bf16(dh, "dh");
+  TORCH_CHECK(dx.dim() == 2 && dh.dim() == 2 && dx.is_contiguous() && dh.is_contiguous() && dx.size(1) == dh.size(1) &&
+              dh.size(1) % 8 == 0, "mlm_scatter_rows: contiguous bf16 [cap, H] -> [N, H], H % 8 == 0");
+  TORCH_CHECK(dx.size(0) < (int64_t)1 << 31, "mlm_scatter_rows: cap < 2^31");
+  check_i32_vec(inv, dh.size(0), "inv");
+  hsd::launch_mlm_scatter_rows(CBF(dx), inv.data_ptr<int32_t>(), BF(dh), dh.size(0), (int)dh.size(1), (int)dx.size(0),
+                               cur_stream());
+}
+
 int64_t cls_head_blocks(int64_t R) { return hsd::cls_head_blocks((int)R); }
 
 // stream-ordered zero fill (hipMemsetAsync): gradient buffers and scatter targets without an at::native fill kernel
@@ -1414,4 +1484,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("memset0", &memset0);
   m.def("small_wgrad", &small_wgrad);
   m.def("mask_bias", &mask_bias);
+  m.def("mlm_mask", &mlm_mask);
+  m.def("mlm_scatter_rows", &mlm_scatter_rows);
+  m.def("mlm_mask_block", []() { return (int64_t)hsd::mlm_mask_block(); });
+  m.def("mlm_mask_blocks", [](int64_t N) { return (int64_t)hsd::mlm_mask_blocks(N); });
 }

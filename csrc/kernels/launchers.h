@@ -83,6 +83,37 @@ void launch_small_wgrad(const bf16_t* dy, int64_t ldy, const bf16_t* x, int64_t 
 // xent.hip: fused softmax cross-entropy (+ gradient, + argmax-correct count); stats = {Σloss, correct}
 void launch_xent(const void* logits, bool bf16, const int64_t* labels, void* dlogits, float* stats,
                  const float* n_valid, int rows, int V, int64_t ld, hipStream_t st);
+// mlm_mask.hip: dynamic MLM masking with ordered compaction into fixed-capacity buffers (ops/rng.py "MLM mask").
+// ids / attention_mask (optional) / labels_in (optional): int64 [N]; ids_out, labels_out: int64 [N]; sel, tgt: int64
+// [cap]; inv: int32 [N]; counts: int32 [2] = {n, dropped}; n_valid: fp32 [1]; ws: int32 [mlm_mask_blocks(N)].
+struct MlmMaskParams {
+  const int64_t* ids;
+  const int64_t* attention_mask;
+  const int64_t* labels_in;
+  int64_t* ids_out;
+  int64_t* labels_out;
+  int64_t* sel;
+  int64_t* tgt;
+  int* inv;
+  int* counts;
+  float* n_valid;
+  int* ws;
+  int64_t N;
+  int cap;
+  uint32_t seed_lo, seed_hi;
+  uint32_t thr;  // select iff the low 16 bits of w0 < thr
+  int64_t mask_id, rand_lo, rand_hi;
+  int64_t special[8];
+  int n_special;
+  const uint32_t* dev_seed;  // set by the launcher
+};
+int mlm_mask_block();
+int mlm_mask_blocks(int64_t N);
+// use_step_seed: XOR the process-wide device step seed (set_dropout_dev_seed) into the mask seed, as dropout does
+void launch_mlm_mask(MlmMaskParams p, bool use_step_seed, hipStream_t st);
+// dh[t][:] = inv[t] >= 0 ? dx[inv[t]][:] : 0   (bf16 [N, H], H % 8 == 0, dx [dx_rows, H]); every row written once
+void launch_mlm_scatter_rows(const bf16_t* dx, const int* inv, bf16_t* dh, int64_t N, int H, int dx_rows,
+                             hipStream_t st);
 // gradient wire casts (comm_engine 16-bit compression): to16: dst16 = src32 * scale; else dst32 = src16 * scale.
 // half: fp16, else bf16. n % 4 == 0, 16-B aligned fp32 side.
 void launch_wire_cast(const void* src, void* dst, int64_t n, bool to16, bool half, float scale, hipStream_t st);

@@ -78,6 +78,84 @@ def synthetic_mlm(num_examples: int, seq_len: int, vocab_size: int, seed: int = 
     return ArrayDataset(ids.astype(np.int32), np.ones_like(ids, dtype=np.int8), labels)
 
 
+def _ragged_lengths(rng, num_examples: int, seq_len: int, full_length: bool) -> np.ndarray:
+    if full_length:
+        return np.full(num_examples, seq_len)
+    return rng.integers(max(4, seq_len // 4), seq_len + 1, size=num_examples)  # as synthetic_classification
+
+
+def _frame(ids: np.ndarray, lengths: np.ndarray, bos_id: int, eos_id: int, pad_id: int) -> np.ndarray:
+    """<s> first, </s> last, padding after: the right-padded layout of every dataset here; returns the mask."""
+    seq_len = ids.shape[1]
+    rows = np.arange(ids.shape[0])
+    ids[:, 0] = bos_id
+    ids[rows, lengths - 1] = eos_id
+    mask = np.arange(seq_len)[None, :] < lengths[:, None]
+    ids[~mask] = pad_id
+    return mask.astype(np.int8)
+
+
+def synthetic_mlm_raw(num_examples: int, seq_len: int, vocab_size: int, seed: int = 0, bos_id: int = 0, eos_id: int = 2,
+                      pad_id: int = 1, full_length: bool = False) -> ArrayDataset:
+    """The unmasked variant of :func:`synthetic_mlm` for ``--mlm_masking dynamic``: i.i.d. uniform tokens (nothing to
+    learn: the loss stays near log V), lengths uniform in ``[S/4, S]`` so ``--pack_sequences`` has padding to drop.
+    ``labels`` is a placeholder: 0 on real tokens (the device masker reads only ``!= -100``), -100 on the padding."""
+    rng = np.random.default_rng(seed)
+    ids = rng.integers(3, vocab_size, size=(num_examples, seq_len), dtype=np.int64)
+    mask = _frame(ids, _ragged_lengths(rng, num_examples, seq_len, full_length), bos_id, eos_id, pad_id)
+    labels = np.where(mask != 0, 0, -100).astype(np.int64)
+    return ArrayDataset(ids.astype(np.int32), mask, labels)
+
+
+def bigram_successor(vocab_size: int, seed: int = 0, lo: int = 3) -> np.ndarray:
+    """``succ [V]``: a fixed random permutation of ``[lo, V)`` (identity below ``lo``), the ``synthetic-bigram``
+    corpus' transition table; a function of ``(vocab_size, lo)`` and a constant only, so the training and the
+    evaluation corpus share it whatever their seeds."""
+    del seed  # one table per vocabulary: the corpus seed picks the sequences, not the language
+    succ = np.arange(vocab_size, dtype=np.int64)
+    succ[lo:] = lo + np.random.default_rng(0x5EED_B16A).permutation(vocab_size - lo)
+    return succ
+
+
+def synthetic_bigram(num_examples: int, seq_len: int, vocab_size: int, seed: int = 0, bos_id: int = 0, eos_id: int = 2,
+                     pad_id: int = 1, follow: float = 0.9, full_length: bool = False) -> ArrayDataset:
+    """``--dataset synthetic-bigram`` (masked-lm): a corpus with something to learn. ``x[i+1] = succ[x[i]]`` with
+    probability ``follow``, uniform over ``[3, V)`` otherwise (:func:`bigram_successor`), so a masked token is
+    predictable from its neighbours and the MLM loss can fall far below log V. Unmasked, ragged lengths, placeholder
+    labels: the layout of :func:`synthetic_mlm_raw`."""
+    rng = np.random.default_rng(seed)
+    lo = 3
+    succ = bigram_successor(vocab_size, lo=lo)
+    fresh = rng.integers(lo, vocab_size, size=(num_examples, seq_len), dtype=np.int64)
+    keep = rng.random((num_examples, seq_len)) < follow
+    ids = fresh.copy()
+    for i in range(2, seq_len):  # column by column: position 0 is <s>, the chain starts fresh at 1
+        ids[:, i] = np.where(keep[:, i], succ[ids[:, i - 1]], fresh[:, i])
+    mask = _frame(ids, _ragged_lengths(rng, num_examples, seq_len, full_length), bos_id, eos_id, pad_id)
+    labels = np.where(mask != 0, 0, -100).astype(np.int64)
+    return ArrayDataset(ids.astype(np.int32), mask, labels)
+
+
+def mask_dataset_static(ds: ArrayDataset, seed: int, mlm_probability: float, mask_id: int, special_ids,
+                        rand_range) -> ArrayDataset:
+    """Mask a raw corpus ONCE with the reference masker (ops/rng.py mlm_mask_reference), one call per example with
+    the example's index in the seed: ``--mlm_masking static`` on a raw corpus (``synthetic-bigram``)."""
+    import torch
+
+    from ..ops.rng import DropoutSeeds, mlm_mask_reference
+
+    seeds = DropoutSeeds(seed)
+    ids = np.array(ds.input_ids, dtype=np.int64)
+    labels = np.full_like(ids, -100)
+    for i in range(ids.shape[0]):
+        m = mlm_mask_reference(torch.from_numpy(ids[i]), torch.from_numpy(ds.attention_mask[i].astype(np.int64)),
+                               torch.from_numpy(ds.labels[i]), seeds.mlm_eval_seed(i), mlm_probability, mask_id,
+                               special_ids, rand_range, cap=ids.shape[1])
+        ids[i] = m.input_ids.numpy()
+        labels[i] = m.labels.numpy()
+    return ArrayDataset(ids.astype(np.int32), ds.attention_mask, labels)
+
+
 # ------------------------------------------------------------------------------------------ text
 def _read_table(path: str) -> Tuple[List[str], List[int]]:
     ext = os.path.splitext(path)[1].lower()

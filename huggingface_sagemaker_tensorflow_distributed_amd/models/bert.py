@@ -256,7 +256,21 @@ class RobertaForMaskedLM(_Base):
     """RoBERTa MLM (decoder tied to the word embeddings), for the roberta-large pretraining config."""
 
     base_prefix = "roberta"
-    graph_safe = False  # the masked-token gather has a data-dependent size (no HIP-graph capture)
+
+    # --mlm_masking: "static" = the batch arrives masked (labels -100 off the masked positions) and the head gathers
+    # the masked rows with a data-dependent size; "dynamic" = the batch arrives raw, forward() draws a fresh
+    # 80 / 10 / 10 mask on the device every call (ops.mlm_mask) and the head runs on a fixed number of rows
+    mlm_masking = "static"
+    mlm_probability = 0.15
+    mlm_eval_index = 0  # the evaluation loop's batch index (Trainer.evaluate): eval masks depend on nothing else
+
+    @property
+    def graph_safe(self) -> bool:
+        """Static masking: the masked-token gather has a data-dependent size (no HIP-graph capture). Dynamic masking
+        reads no device value on the host."""
+        return self.mlm_masking == "dynamic"
+
+    eval_graph_safe = False  # dynamic eval masks take a host seed per batch, which a replayed graph would freeze
 
     # The decoder's vocabulary dimension (tied word embeddings, lm_head.bias) is padded to a multiple of this many
     # rows: 50265 -> 50432 for RoBERTa, so every GEMM of the head (logits forward, its dgrad and the tied-embedding
@@ -295,9 +309,57 @@ class RobertaForMaskedLM(_Base):
         yield "lm_head.layer_norm.bias", "lm_ln_bias", None, 1
         yield "lm_head.bias", "lm_bias", None, 1
 
+    def set_mlm_masking(self, mode: str, probability: float = 0.15) -> None:
+        if mode not in ("static", "dynamic"):
+            raise ValueError(f"mlm_masking {mode!r}")
+        if not 0.0 < float(probability) <= 1.0:
+            raise ValueError(f"mlm_probability {probability!r}")
+        self.mlm_masking, self.mlm_probability = mode, float(probability)
+
+    @property
+    def mask_token_id(self) -> int:
+        # RoBERTa's <mask> is the last id of its 50,265-token vocabulary; smaller test vocabularies fold it the way
+        # data/datasets.py synthetic_mlm does
+        return 50264 % self.vocab
+
+    def mlm_special_ids(self):
+        c = self.cfg
+        ids = [c.pad_token_id, c.bos_token_id, c.eos_token_id, self.mask_token_id]
+        return sorted({int(i) for i in ids if i is not None})
+
+    def mlm_rand_range(self):
+        """Random replacements are drawn from the ids above pad / bos / eos."""
+        c = self.cfg
+        lo = 1 + max(int(i) for i in (c.pad_token_id, c.bos_token_id, c.eos_token_id) if i is not None)
+        return (min(lo, self.vocab - 1), self.vocab)
+
+    def mask_batch(self, input_ids, attention_mask, labels, cap=None):
+        """The dynamic mask of one batch (padded ``[B, S]`` or packed ``[1, T]`` ids; ``labels``: -100 marks rows that
+        must stay unmasked). Training draws ``rng.mlm_seed()`` (a new one per call since ``rng.new_step``) and folds
+        the device step seed in; evaluation draws ``rng.mlm_eval_seed(mlm_eval_index)``."""
+        seed = self.rng.mlm_seed() if self.training else self.rng.mlm_eval_seed(self.mlm_eval_index)
+        m = ops.mlm_mask(input_ids, attention_mask, labels, seed, self.mlm_probability, self.mask_token_id,
+                         self.mlm_special_ids(), self.mlm_rand_range(), cap=cap, use_step_seed=self.training)
+        if self.training:
+            # selections dropped for want of head capacity, summed on the device; read where the trainer logs
+            tot = self.__dict__.get("_mlm_dropped")
+            if tot is None or tot.device != m.counts.device:
+                tot = self.__dict__["_mlm_dropped"] = torch.zeros((), dtype=torch.int64, device=m.counts.device)
+            tot.add_(m.counts[1])
+        return m
+
+    def mlm_dropped(self) -> int:
+        """Selections dropped so far because a batch selected more than ``cap`` positions (reads the device)."""
+        tot = self.__dict__.get("_mlm_dropped")
+        return int(tot) if tot is not None else 0
+
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, *, cu_seqlens=None,
                 max_seqlen=None, position_ids=None):
         c = self.cfg
+        mask = None
+        if labels is not None and self.mlm_masking == "dynamic":
+            mask = self.mask_batch(input_ids, attention_mask, labels)
+            input_ids = mask.input_ids
         h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, self.training, cu_seqlens=cu_seqlens,
                          max_seqlen=max_seqlen, position_ids=position_ids)
         if cu_seqlens is not None:
@@ -305,6 +367,10 @@ class RobertaForMaskedLM(_Base):
         B, S, H = h.shape
         x = h.view(B * S, H)
         wemb = self.encoder.embeddings.word_embeddings
+        if mask is not None:
+            # fixed-capacity head: the rows the device compacted, no host read (graph-safe)
+            return ops.mlm_head_fixed(x, mask, self.lm_dense_weight, self.lm_dense_bias, self.lm_ln_weight,
+                                      self.lm_ln_bias, c.layer_norm_eps, wemb, self.lm_bias, self.vocab)
         if labels is not None:
             # only masked positions feed the (large-vocab) decoder: dense + GELU -> LN -> tied decoder -> CE
             loss, logits = ops.mlm_head(x, labels.view(-1), self.lm_dense_weight, self.lm_dense_bias, self.lm_ln_weight,

@@ -270,5 +270,54 @@ def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
     return _ref.mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab)
 
 
+def mlm_mask(input_ids, attention_mask, labels_in, seed, p, mask_id, special_ids, rand_range, cap=None,
+             use_step_seed=True):
+    """Dynamic MLM masking (``--mlm_masking dynamic``; definition: ops/rng.py "MLM mask"): a fresh 80 / 10 / 10 draw
+    over the maskable tokens of the flat id buffer, compacted in order into fixed-capacity buffers. Returns an
+    :class:`ops.rng.MlmMask` (``input_ids``, ``labels``, ``sel``, ``tgt``, ``inv``, ``counts``, ``n_valid``, ``cap``).
+
+    GPU tensors: the HIP kernels (two launches, no host sync; ``use_step_seed`` folds the device step seed of a
+    graph-enabled trainer in, as the dropout kernels do). CPU tensors, and ``HSD_OPS=torch``: the torch reference."""
+    if input_ids.is_cuda and not _FORCE_TORCH:
+        return _hipmod().mlm_mask(input_ids, attention_mask, labels_in, seed, p, mask_id, special_ids, rand_range,
+                                  cap, use_step_seed)
+    from .rng import mlm_mask_reference
+
+    return mlm_mask_reference(input_ids, attention_mask, labels_in, seed, p, mask_id, special_ids, rand_range, cap)
+
+
+def mlm_head_fixed(h2d, mask, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
+    """Masked-LM head on the fixed-capacity rows of an :func:`mlm_mask` result -> (loss, logits [cap, vocab]).
+
+    The loss is ``Σ CE / max(n, 1)`` computed on the device (0 when nothing was selected) and carries the fused
+    {mean loss, hits, rows, loss sum} on ``loss._hsd_stats`` / the hits on ``loss._hsd_correct``: nothing in here reads a
+    device value on the host. GPU bf16 tensors that :func:`hip.mlm_head_ok` accepts run the HIP head (the static
+    head's kernels on ``cap`` rows, a row-scatter kernel for the hidden-state gradient); everything else the same
+    ``(sel, tgt)`` through the composed ops."""
+    sel, tgt, n_valid = mask.sel, mask.tgt, mask.n_valid
+    if _hip(h2d) and h2d.dtype == torch.bfloat16 and _hipmod().mlm_head_ok(h2d, w1, wemb):
+        loss, logits, stats = _hipmod().mlm_head_fixed(h2d, sel, tgt, mask.inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb,
+                                                       bias, vocab)
+        loss._hsd_correct = stats[1]
+        loss._hsd_stats = stats
+        return loss, logits
+    x = h2d.index_select(0, sel)
+    if _hip(h2d) or _hip32(h2d):
+        x = layer_norm(linear_gelu(x, w1, b1), ln_w, ln_b, eps)
+        logits = linear(x, wemb[:vocab], bias[:vocab])
+    else:
+        x = _ref.layer_norm(_ref.linear_gelu(x, w1, b1), ln_w, ln_b, eps)
+        logits = torch.nn.functional.linear(x, wemb[:vocab], bias[:vocab])
+    lsum = torch.nn.functional.cross_entropy(logits.float(), tgt, ignore_index=-100, reduction="sum")
+    nv = n_valid[0].clamp(min=1.0)
+    loss = lsum / nv
+    with torch.no_grad():
+        hits = ((logits.argmax(dim=-1) == tgt) & tgt.ne(-100)).sum().to(torch.float32)
+        stats = torch.stack([loss.detach().float(), hits, n_valid[0], lsum.detach().float()])
+    loss._hsd_correct = stats[1]
+    loss._hsd_stats = stats
+    return loss, logits
+
+
 def accuracy_count(logits, labels):
     return _ref.accuracy_count(logits, labels)

@@ -1473,6 +1473,106 @@ def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
     return _MlmHead.apply(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab)
 
 
+def mlm_mask(input_ids, attention_mask, labels_in, seed, p, mask_id, special_ids, rand_range, cap=None,
+             use_step_seed=True):
+    """The MLM mask of ops/rng.py on the device (csrc/kernels/mlm_mask.hip): two launches, no host sync, every
+    buffer sized from the shape alone. ``use_step_seed``: XOR the process-wide device step seed in (training);
+    evaluation passes False so its masks do not depend on the last training step."""
+    from .rng import MlmMask, mlm_capacity
+
+    ids = input_ids.contiguous().view(-1)
+    if ids.dtype != torch.int64:
+        ids = ids.long()
+    N = ids.numel()
+    cap = mlm_capacity(N, p) if cap is None else int(cap)
+    dev = ids.device
+
+    def flat(t):
+        if t is None:
+            return None
+        t = t.contiguous().view(-1)
+        return t if t.dtype == torch.int64 else t.long()
+
+    ids_out = torch.empty_like(ids)
+    labels_out = torch.empty_like(ids)
+    sel = torch.empty(cap, dtype=torch.int64, device=dev)
+    tgt = torch.empty(cap, dtype=torch.int64, device=dev)
+    inv = torch.empty(N, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    n_valid = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = torch.empty(_C.mlm_mask_blocks(N), dtype=torch.int32, device=dev)
+    _C.mlm_mask(ids, flat(attention_mask), flat(labels_in), ids_out, labels_out, sel, tgt, inv, counts, n_valid, ws,
+                _s64(seed), float(p), int(mask_id), [int(s) for s in special_ids], int(rand_range[0]),
+                int(rand_range[1]), bool(use_step_seed))
+    return MlmMask(ids_out.view(input_ids.shape), labels_out.view(input_ids.shape), sel, tgt, inv, counts, n_valid, cap)
+
+
+class _MlmHeadFixed(torch.autograd.Function):
+    """:class:`_MlmHead` on a fixed number of rows (``--mlm_masking dynamic``): the masked rows arrive as the
+    device-side compaction of ``mlm_mask`` -- ``sel`` / ``tgt`` of ``cap`` rows (a multiple of 64; ``sel = 0``,
+    ``tgt = -100`` beyond the ``n`` selected), ``inv`` and the device scalar ``n_valid`` -- so nothing is read back to
+    the host and the head can be captured into a HIP graph. The same GEMM, LayerNorm and CE chain as the static head on
+    ``cap`` rows; the rows beyond ``n`` carry ignored labels, so the CE kernel gives them exact zero gradients.
+    Backward: as the static head down to dx, then ``dh[t] = inv[t] >= 0 ? dx[inv[t]] : 0`` in one pass (every row
+    written once: no memset, no index_copy_, which would let the unused rows' ``sel = 0`` overwrite row 0).
+
+    Returns (loss, logits [cap, vocab], stats); stats = fp32 {mean loss, hits, rows, loss sum} on the device, the
+    metric meter's fused protocol (train/trainer.py _Meter)."""
+
+    @staticmethod
+    def forward(ctx, h2d, sel, tgt, inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
+        T, H = h2d.shape
+        x = h2d.index_select(0, sel)
+        act = torch.empty((sel.shape[0], H), dtype=h2d.dtype, device=h2d.device)
+        pre = gemm_fwd(x, w1, EPI_BIAS_GELU, bias=b1, out2=act)
+        y, mean, rstd = _ln_fwd(act, ln_w, ln_b, eps)
+        logits = gemm_fwd(y, wemb, EPI_BIAS, bias=bias)
+        raw = torch.zeros(2, dtype=torch.float32, device=h2d.device)
+        dlogits = torch.empty_like(logits)
+        _C.xent(logits, tgt, dlogits, raw, n_valid, vocab)
+        loss = raw[0] / n_valid[0].clamp(min=1.0)
+        stats = torch.stack([loss, raw[1], n_valid[0], raw[0]])
+        ctx.save_for_backward(x, inv, w1, b1, pre, act, y, mean, rstd, ln_w, ln_b, wemb, bias, dlogits)
+        ctx.cfg = (T, H)
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)
+        return loss, logits[:, :vocab], stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits, _dstats):
+        x, inv, w1, b1, pre, act, y, mean, rstd, ln_w, ln_b, wemb, bias, dlogits = ctx.saved_tensors
+        T, H = ctx.cfg
+        g_wemb, g_w1, g_b1, g_lnw, g_lnb, g_bias = _Grad(wemb), _Grad(w1), _Grad(b1), _Grad(ln_w), _Grad(ln_b), _Grad(bias)
+        if dloss is None:
+            dloss = torch.zeros((), dtype=torch.float32, device=x.device)
+        dl = dloss.reshape(1).to(torch.float32)
+        cs = torch.zeros(dlogits.shape[1], dtype=torch.float32, device=x.device)
+        _C.colsum(dlogits, cs)
+        g_bias.buf.add_(cs * dl)
+        gemm_wgrad_(g_wemb, dlogits, (y * dl.to(y.dtype)).contiguous())
+        r_wemb = g_wemb.done()
+        dy = torch.empty_like(y)
+        _C.gemm2(dlogits, wemb, dy, 0, 1, EPI_STORE, None, None, None, 0.0, 0, 0, None, None)
+        dy.mul_(dl.to(dy.dtype))
+        dact = torch.empty_like(act)
+        _C.ln_bwd(dy, act, mean, rstd, ln_w, None, dact, None, g_lnw.buf, g_lnb.buf, None, 0.0, 0)
+        dpre = torch.empty_like(pre)
+        _C.gelu_bwd_colsum(dact, pre, dpre, g_b1.buf)
+        gemm_wgrad_(g_w1, dpre, x)
+        dh = None
+        if ctx.needs_input_grad[0]:
+            dx = gemm_dgrad(dpre, w1)
+            dh = torch.empty((T, H), dtype=dx.dtype, device=dx.device)
+            _C.mlm_scatter_rows(dx, inv, dh)
+        return (dh, None, None, None, None, g_w1.done(), g_b1.done(), g_lnw.done(), g_lnb.done(), None, r_wemb,
+                g_bias.done(), None)
+
+
+def mlm_head_fixed(h2d, sel, tgt, inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
+    """(loss, logits [cap, vocab], stats) of the fixed-capacity masked-LM head."""
+    return _MlmHeadFixed.apply(h2d, sel, tgt, inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab)
+
+
 # ------------------------------------------------------------------------------------------ loss
 class _CrossEntropy(torch.autograd.Function):
     """Mean softmax cross-entropy over non-ignored rows (-100) with the gradient produced by the same

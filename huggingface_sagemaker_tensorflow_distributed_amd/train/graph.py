@@ -17,7 +17,9 @@ What makes a replay a *fresh* step:
 * gradients: the flat ``main_grad`` buffer is zeroed before the replay (kernels accumulate into it).
 
 Limits: fixed batch shape per captured graph (a new shape captures a new graph), models without data-dependent
-shapes (the MLM head's masked-token gather syncs the host: eager only). Data-parallel steps are captured whole only
+shapes (the static MLM head's masked-token gather syncs the host: eager only; ``--mlm_masking dynamic`` masks on the
+device into fixed-capacity buffers and is captured, its mask seed baked in and varied by the device step seed like the
+dropout seeds). Data-parallel steps are captured whole only
 on request (HSD_GRAPH_DP=1, :class:`CapturedTrainStep` with the native RCCL engine's bucket all-reduces inside the
 graph); by default they keep the eager path.
 """

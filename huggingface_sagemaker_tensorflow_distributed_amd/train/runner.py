@@ -45,11 +45,34 @@ def _datasets(args, cfg, tokenizer, max_len: int):
     n_train = args.num_train_examples
     n_eval = args.num_eval_examples
     if getattr(args, "task", "sequence-classification") == "masked-lm":
-        if args.dataset != "synthetic":
-            raise ValueError("--task masked-lm trains on --dataset synthetic (no text corpus offline)")
-        tr = hdata.synthetic_mlm(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed)
-        te = hdata.synthetic_mlm(n_eval or 512, max_len, cfg.vocab_size, seed=args.seed + 1)
+        if args.dataset not in ("synthetic", "synthetic-bigram"):
+            raise ValueError("--task masked-lm trains on --dataset synthetic or synthetic-bigram (no text corpus "
+                             "offline)")
+        p = float(getattr(args, "mlm_probability", 0.15))
+        dynamic = getattr(args, "mlm_masking", "static") == "dynamic"
+        ids = {"bos_id": cfg.bos_token_id if cfg.bos_token_id is not None else 0,
+               "eos_id": cfg.eos_token_id if cfg.eos_token_id is not None else 2}
+        if args.dataset == "synthetic" and not dynamic:
+            # the corpus masked once as it is built: i.i.d. tokens, all full length
+            tr = hdata.synthetic_mlm(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed, mlm_probability=p, **ids)
+            te = hdata.synthetic_mlm(n_eval or 512, max_len, cfg.vocab_size, seed=args.seed + 1, mlm_probability=p,
+                                     **ids)
+            return tr, te
+        make = hdata.synthetic_bigram if args.dataset == "synthetic-bigram" else hdata.synthetic_mlm_raw
+        tr = make(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed, pad_id=cfg.pad_token_id, **ids)
+        te = make(n_eval or 512, max_len, cfg.vocab_size, seed=args.seed + 1, pad_id=cfg.pad_token_id, **ids)
+        if not dynamic:
+            # a raw corpus under static masking: masked once, here, with the reference masker
+            mask_id = 50264 % cfg.vocab_size
+            special = sorted({int(cfg.pad_token_id), int(ids["bos_id"]), int(ids["eos_id"]), mask_id})
+            # the model's own rule (RobertaForMaskedLM.mlm_rand_range): replacements from above pad / bos / eos
+            rr = (min(1 + max(int(cfg.pad_token_id), int(ids["bos_id"]), int(ids["eos_id"])), cfg.vocab_size - 1),
+                  cfg.vocab_size)
+            tr = hdata.mask_dataset_static(tr, args.seed, p, mask_id, special, rr)
+            te = hdata.mask_dataset_static(te, args.seed + 1, p, mask_id, special, rr)
         return tr, te
+    if args.dataset == "synthetic-bigram":
+        raise ValueError("--dataset synthetic-bigram is a masked-lm corpus (--task masked-lm)")
     if args.dataset == "synthetic":
         tr = hdata.synthetic_classification(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed,
                                             num_labels=cfg.num_labels)
@@ -72,11 +95,20 @@ def _provenance(args, model, rank: int, n_train: int, n_eval: int, batch_plan=No
     the reference's exact format, so the data / weights they came from go to ``run_provenance.json`` beside
     them and to a WARNING in the log."""
     weights = getattr(model, "weights_source", "random-init")
-    synthetic = args.dataset == "synthetic"
+    synthetic = args.dataset in ("synthetic", "synthetic-bigram")
     info = {"dataset": args.dataset, "synthetic_data": synthetic, "weights": weights,
             "model_name_or_path": args.model_name_or_path, "num_train_examples": n_train,
             "num_eval_examples": n_eval, "train_batch_size": args.train_batch_size,
             "pack_sequences": bool(getattr(args, "pack_sequences", False))}
+    if getattr(args, "task", "sequence-classification") == "masked-lm":
+        dynamic = getattr(args, "mlm_masking", "static") == "dynamic"
+        info["mlm_masking"] = "dynamic" if dynamic else "static"
+        info["mlm_probability"] = float(getattr(args, "mlm_probability", 0.15))
+        info["corpus"] = ("synthetic-bigram (first-order chain, ragged lengths)" if args.dataset == "synthetic-bigram"
+                          else "synthetic i.i.d. tokens, " + ("raw, ragged lengths" if dynamic
+                                                              else "masked when built, full length"))
+        logger.info("masked-lm corpus: %s; --mlm_masking %s, --mlm_probability %g", info["corpus"],
+                    info["mlm_masking"], info["mlm_probability"])
     if batch_plan is not None:
         info["auto_batch"] = batch_plan.as_dict()
     if synthetic or weights == "random-init":
@@ -113,6 +145,10 @@ def build(args, mode: str):
     model.to(dev)
     model.rng.base_seed = args.seed
     model.rng.rank = rank
+    if task == "masked-lm":
+        # dynamic: the model masks each batch on the device and its head has a fixed row count (--dtype fp8 takes
+        # the same fp8 head GEMMs as the static head: both call the one gemm_fwd / gemm_dgrad / gemm_wgrad_ chain)
+        model.set_mlm_masking(getattr(args, "mlm_masking", "static"), getattr(args, "mlm_probability", 0.15))
     # --dtype fp8: bf16 activations / master-weight copies plus fp8 (e4m3) weight copies and per-tensor
     # quantised fp8 forward + dgrad GEMMs on the HIP path (ops/hip.py set_fp8); CPU runs stay bf16.
     if dtype_name == "fp32" and on_gpu:

@@ -443,6 +443,11 @@ class Trainer:
                     logger.info("epoch %d step %d/%d - loss: %.4f - sparse_categorical_accuracy: %.4f - %.1f ms/step%s",
                                 epoch + 1, step + 1, nsteps, r["loss"], r["sparse_categorical_accuracy"],
                                 (time.time() - t0) * 1e3 / (step + 1), gn)
+                    # --mlm_masking dynamic: selections beyond the head's fixed capacity (a device read, here only)
+                    dropped = self.model.mlm_dropped() if hasattr(self.model, "mlm_dropped") else 0
+                    if dropped:
+                        logger.warning("--mlm_masking dynamic: %d selected positions so far exceeded the head's "
+                                       "capacity and were left unmasked (ops/rng.py mlm_capacity)", dropped)
                 for cb in callbacks:
                     cb.on_batch_end(self, step)
             for _ in it:  # drain the prefetch thread
@@ -461,6 +466,8 @@ class Trainer:
         HSD_EVAL_GRAPH_MAX_TOKENS (16,384) tokens on the GPU, where one forward is a few hundred short launches."""
         flag = self.eval_hip_graph
         if self.device.type != "cuda" or not getattr(self.model, "graph_safe", True) or not ops.hip_active(self.device):
+            return False
+        if not getattr(self.model, "eval_graph_safe", True):
             return False
         if flag != "auto":
             return bool(flag)
@@ -498,6 +505,8 @@ class Trainer:
                 continue  # drain
             if b.get("num_valid", 1) == 0:
                 continue  # a shard's tail made only of padding rows
+            if hasattr(self.model, "mlm_eval_index"):
+                self.model.mlm_eval_index = i  # --mlm_masking dynamic: the eval mask seed is the batch's index
             loss, logits, static = self._eval_forward(b)
             meter.update(loss, logits, b["labels"], static=static)
             if self.rank == 0 and self.log_every and (i + 1) % (self.log_every * 20) == 0:

@@ -75,7 +75,8 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
     g.add_argument("--max_seq_length", type=int, default=None,
                    help="pad/truncate length (default: tokenizer.model_max_length, 512 for BERT)")
     g.add_argument("--dataset", type=str, default="synthetic",
-                   help="imdb | sst2 | synthetic | path to a local dataset directory/file")
+                   help="imdb | sst2 | synthetic | synthetic-bigram (masked-lm only: a learnable first-order corpus) | "
+                        "path to a local dataset directory/file")
     g.add_argument("--dataset_dir", type=str, default=None, help="local directory holding imdb/sst2 data")
     g.add_argument("--num_train_examples", type=int, default=None, help="synthetic/limit train size")
     g.add_argument("--num_eval_examples", type=int, default=None, help="synthetic/limit eval size")
@@ -136,6 +137,13 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
     g.add_argument("--num_labels", type=int, default=2)
     g.add_argument("--task", choices=["sequence-classification", "masked-lm"], default="sequence-classification",
                    help="masked-lm: RoBERTa MLM pretraining (BASELINE.json config 5)")
+    g.add_argument("--mlm_masking", choices=["static", "dynamic"], default="static",
+                   help="masked-lm: static = the corpus is masked once when it is built (every selected token becomes "
+                        "<mask>); dynamic = RoBERTa's recipe, a fresh draw every step on the device (80 %% <mask>, 10 %% "
+                        "random token, 10 %% unchanged) and a fixed-capacity head without a host sync, which "
+                        "--hip_graph accepts (README '--mlm_masking dynamic')")
+    g.add_argument("--mlm_probability", type=float, default=0.15,
+                   help="masked-lm: share of the maskable tokens selected for prediction (both masking modes)")
     g.add_argument("--auto_batch_max_tokens", type=int, default=131072,
                    help="--train_batch_size auto: cap per-GPU tokens (0 = fill the memory budget)")
     g.add_argument("--auto_batch_headroom", type=float, default=0.9,
