@@ -1260,6 +1260,67 @@ void mlm_scatter_rows(torch::Tensor dx, torch::Tensor inv, torch::Tensor dh) {
 
 int64_t cls_head_blocks(int64_t R) { return hsd::cls_head_blocks((int)R); }
 
+// fused token-classification head (token_head.hip). h [R][H] bf16 contiguous, W [C][H], b [C] bf16, labels int64 [R]
+// (or none: logits only, stats untouched); logits [R][C] bf16; partials fp32 [token_head_fwd_blocks(R)][4]; stats
+// fp32 [4]
+static void token_head_check(const torch::Tensor& h, const torch::Tensor& W, const torch::Tensor& logits) {
+  TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() && h.scalar_type() == torch::kBFloat16, "token_head h");
+  const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
+  TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 16 && H % 8 == 0 && H >= 8 && H <= 1024 && C >= 2 && C <= 16,
+              "token_head: 1 <= rows < 2^31, H % 8 == 0, H <= 1024, 2 <= classes <= 16");
+  TORCH_CHECK(W.is_contiguous() && W.dim() == 2 && W.size(1) == H && W.scalar_type() == torch::kBFloat16,
+              "token_head W");
+  TORCH_CHECK(logits.is_contiguous() && logits.dim() == 2 && logits.size(0) == R && logits.size(1) == C &&
+              logits.scalar_type() == torch::kBFloat16, "token_head logits");
+}
+
+void token_head_fwd(torch::Tensor h, torch::Tensor W, torch::Tensor b, c10::optional<torch::Tensor> labels,
+                    torch::Tensor logits, torch::Tensor partials, torch::Tensor stats, double p, int64_t seed) {
+  token_head_check(h, W, logits);
+  const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
+  TORCH_CHECK(b.is_contiguous() && b.numel() == C && b.scalar_type() == torch::kBFloat16, "token_head b");
+  check_f32(partials, "partials");
+  check_f32(stats, "stats");
+  TORCH_CHECK(partials.numel() >= 4 * (int64_t)hsd::token_head_fwd_blocks((int)R) && stats.numel() >= 4,
+              "token_head stats");
+  const int64_t* lab = nullptr;
+  if (labels.has_value()) {
+    TORCH_CHECK(labels->scalar_type() == torch::kInt64 && labels->is_contiguous() && labels->numel() == R, "labels");
+    lab = labels->data_ptr<int64_t>();
+  }
+  hsd::launch_token_head_fwd(CBF(h), CBF(W), CBF(b), lab, BF(logits), partials.data_ptr<float>(),
+                             stats.data_ptr<float>(), (int)R, (int)H, (int)C, p, (uint64_t)seed, cur_stream());
+}
+
+// dh [R][H] bf16 (or none: parameter gradients only); part fp32, >= token_head_bwd_blocks(R) · (C·H + C) elements;
+// dW fp32 [C·H] and db fp32 [C] are ADDED to
+void token_head_bwd(torch::Tensor h, torch::Tensor W, torch::Tensor logits, torch::Tensor labels, torch::Tensor stats,
+                    torch::Tensor dloss, c10::optional<torch::Tensor> dh, torch::Tensor part, torch::Tensor dW,
+                    torch::Tensor db, double p, int64_t seed) {
+  token_head_check(h, W, logits);
+  const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
+  TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.is_contiguous() && labels.numel() == R, "labels");
+  check_f32(stats, "stats");
+  check_f32(dloss, "dloss");
+  check_f32(part, "part");
+  check_f32(dW, "dW");
+  check_f32(db, "db");
+  TORCH_CHECK(stats.numel() >= 4 && dloss.numel() >= 1, "token_head stats / dloss");
+  TORCH_CHECK(part.numel() >= (int64_t)hsd::token_head_bwd_blocks((int)R) * (C * H + C), "token_head workspace");
+  TORCH_CHECK(dW.numel() == C * H && db.numel() == C, "token_head grads");
+  hsd::bf16_t* dhp = nullptr;
+  if (dh.has_value()) {
+    TORCH_CHECK(dh->is_contiguous() && dh->sizes() == h.sizes() && dh->scalar_type() == torch::kBFloat16, "dh");
+    dhp = BF(*dh);
+  }
+  hsd::launch_token_head_bwd(CBF(h), CBF(W), CBF(logits), labels.data_ptr<int64_t>(), stats.data_ptr<float>(),
+                             dloss.data_ptr<float>(), dhp, part.data_ptr<float>(), dW.data_ptr<float>(),
+                             db.data_ptr<float>(), (int)R, (int)H, (int)C, p, (uint64_t)seed, cur_stream());
+}
+
+int64_t token_head_fwd_blocks(int64_t R) { return hsd::token_head_fwd_blocks((int)R); }
+int64_t token_head_bwd_blocks(int64_t R) { return hsd::token_head_bwd_blocks((int)R); }
+
 // stream-ordered zero fill (hipMemsetAsync): gradient buffers and scatter targets without an at::native fill kernel
 void memset0(torch::Tensor x) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "memset0: contiguous GPU tensor");
@@ -1481,6 +1542,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cls_head_fwd", &cls_head_fwd);
   m.def("cls_head_bwd", &cls_head_bwd);
   m.def("cls_head_blocks", &cls_head_blocks);
+  m.def("token_head_fwd", &token_head_fwd);
+  m.def("token_head_bwd", &token_head_bwd);
+  m.def("token_head_fwd_blocks", &token_head_fwd_blocks);
+  m.def("token_head_bwd_blocks", &token_head_bwd_blocks);
   m.def("memset0", &memset0);
   m.def("small_wgrad", &small_wgrad);
   m.def("mask_bias", &mask_bias);

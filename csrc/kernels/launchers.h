@@ -127,6 +127,17 @@ void launch_cls_head_fwd(const bf16_t* pre, int64_t ld_pre, const bf16_t* W2, co
 void launch_cls_head_bwd(const bf16_t* t_in, const bf16_t* W2, const bf16_t* logits, const int64_t* labels,
                          const float* stats, const float* dloss, bf16_t* dpre, float* dW2, float* db2, int R, int H,
                          int C, int act, double p, uint64_t seed, hipStream_t st);
+// token_head.hip: fused token-classification head over every row (dropout, classifier, CE, accuracy); H % 8 == 0,
+// H <= 1024, 2 <= C <= 16. labels may be null (logits only: stats untouched). The backward writes
+// token_head_bwd_blocks(R) fp32 partial slabs of C·H + C into `part` and adds them into dW / db; dh may be null.
+int token_head_fwd_blocks(int R);
+int token_head_bwd_blocks(int R);
+void launch_token_head_fwd(const bf16_t* h, const bf16_t* W, const bf16_t* b, const int64_t* labels, bf16_t* logits,
+                           float* partials, float* stats, int R, int H, int C, double p, uint64_t seed,
+                           hipStream_t st);
+void launch_token_head_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* logits, const int64_t* labels,
+                           const float* stats, const float* dloss, bf16_t* dh, float* part, float* dW, float* db,
+                           int R, int H, int C, double p, uint64_t seed, hipStream_t st);
 // attention.hip
 bool attn_streaming(int S);
 // kmask (optional, streaming S > 128 kernels: attn_keep_mask_supported): the forward writes its dropout keep bits

@@ -1,9 +1,11 @@
-from .datasets import (ArrayDataset, bigram_successor, load_text_split, mask_dataset_static, synthetic_bigram,
-                       synthetic_classification, synthetic_mlm, synthetic_mlm_raw, tokenize_dataset)
+from .datasets import (ArrayDataset, bigram_successor, conll_tag_list, load_text_split, mask_dataset_static,
+                       read_conll, synthetic_bigram, synthetic_classification, synthetic_mlm, synthetic_mlm_raw,
+                       synthetic_token_classification, tag_table, tokenize_conll, tokenize_dataset)
 from .loader import BatchLoader
 from .packing import pack_batch, position_rule, unpack_rows
 from .tokenization import Tokenizer, load_tokenizer
 
 __all__ = ["ArrayDataset", "synthetic_classification", "synthetic_mlm", "synthetic_mlm_raw", "synthetic_bigram",
            "bigram_successor", "mask_dataset_static", "load_text_split", "tokenize_dataset",
+           "synthetic_token_classification", "tag_table", "read_conll", "conll_tag_list", "tokenize_conll",
            "BatchLoader", "Tokenizer", "load_tokenizer", "pack_batch", "position_rule", "unpack_rows"]

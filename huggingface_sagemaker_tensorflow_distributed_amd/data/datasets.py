@@ -136,6 +136,114 @@ def synthetic_bigram(num_examples: int, seq_len: int, vocab_size: int, seed: int
     return ArrayDataset(ids.astype(np.int32), mask, labels)
 
 
+def tag_table(vocab_size: int, num_labels: int) -> np.ndarray:
+    """``table [V]`` of the synthetic tagging corpus: a fixed random map token id -> ``[0, L)``, a function of
+    ``(vocab_size, num_labels)`` and a constant only, so the train and eval splits share one language."""
+    return np.random.default_rng([0x7A65, int(vocab_size), int(num_labels)]).integers(
+        0, num_labels, size=vocab_size, dtype=np.int64)
+
+
+def synthetic_token_classification(num_examples: int, seq_len: int, vocab_size: int, seed: int = 0,
+                                   num_labels: int = 9, full_length: bool = False, ignore_fraction: float = 0.25,
+                                   cls_id: int = 101, sep_id: int = 102, pad_id: int = 0) -> ArrayDataset:
+    """``--task token-classification --dataset synthetic``: a learnable tagging corpus in the ``[CLS] … [SEP]`` layout
+    of :func:`synthetic_classification`, lengths ragged in ``[S/4, S]``. ``tag[i] = (table[x[i]] + table[x[i-1]]) % L``
+    (:func:`tag_table`; ``x[i-1]`` of the first real token is ``[CLS]``), so a token's tag depends on its left
+    neighbour. ``labels [N, S]``: -100 on ``[CLS]``, ``[SEP]``, the padding and a seeded ``ignore_fraction`` of the
+    real tokens (they stand in for word-continuation pieces: ignored rows are scattered, not only at the tail)."""
+    rng = np.random.default_rng(seed)
+    lo = 1000 if vocab_size > 4000 else 4
+    ids = rng.integers(lo, vocab_size, size=(num_examples, seq_len), dtype=np.int64)
+    lengths = _ragged_lengths(rng, num_examples, seq_len, full_length)
+    drop = rng.random((num_examples, seq_len)) < ignore_fraction
+    mask = _frame(ids, lengths, cls_id % vocab_size, sep_id % vocab_size, pad_id)
+    table = tag_table(vocab_size, num_labels)
+    tags = np.zeros_like(ids)
+    tags[:, 1:] = (table[ids[:, 1:]] + table[ids[:, :-1]]) % num_labels
+    pos = np.arange(seq_len)[None, :]
+    real = (pos >= 1) & (pos < (lengths[:, None] - 1))
+    labels = np.where(real & ~drop, tags, -100).astype(np.int64)
+    return ArrayDataset(ids.astype(np.int32), mask, labels)
+
+
+# ------------------------------------------------------------------------------------------ CoNLL column files
+def read_conll(path: str) -> Tuple[List[List[str]], List[List[str]]]:
+    """CoNLL column format: one token per line, first column the word, last column the tag; a blank line ends a
+    sentence; ``-DOCSTART-`` lines are skipped. Returns (sentences of words, sentences of tags)."""
+    words: List[List[str]] = []
+    tags: List[List[str]] = []
+    w: List[str] = []
+    t: List[str] = []
+    with open(path, encoding="utf-8") as f:
+        for line in f:
+            cols = line.split()
+            if not cols:
+                if w:
+                    words.append(w)
+                    tags.append(t)
+                    w, t = [], []
+                continue
+            if cols[0] == "-DOCSTART-":
+                continue
+            if len(cols) < 2:
+                raise ValueError(f"{path}: a token line needs a word and a tag, got {line!r}")
+            w.append(cols[0])
+            t.append(cols[-1])
+    if w:
+        words.append(w)
+        tags.append(t)
+    return words, tags
+
+
+def conll_split_path(dataset_dir: str, split: str) -> str:
+    names = ["train.txt"] if split == "train" else ["test.txt", "validation.txt", "dev.txt"]
+    for n in names:
+        p = os.path.join(dataset_dir or "", n)
+        if os.path.isfile(p):
+            return p
+    raise FileNotFoundError(f"--dataset conll: none of {names} in --dataset_dir {dataset_dir!r}")
+
+
+def conll_tag_list(dataset_dir: str) -> List[str]:
+    """``labels.txt`` (one tag per line) if present, else the sorted tags of the train split."""
+    p = os.path.join(dataset_dir or "", "labels.txt")
+    if os.path.isfile(p):
+        with open(p, encoding="utf-8") as f:
+            tags = [l.strip() for l in f if l.strip()]
+    else:
+        tags = sorted({t for sent in read_conll(conll_split_path(dataset_dir, "train"))[1] for t in sent})
+    if len(tags) < 2:
+        raise ValueError(f"--dataset conll: {len(tags)} tag(s) in {dataset_dir!r}")
+    return tags
+
+
+def tokenize_conll(tokenizer, words: List[List[str]], tags: List[List[str]], tag_list: List[str],
+                   max_length: int, chunk: int = 1000) -> ArrayDataset:
+    """Pre-tokenised sentences -> ``ArrayDataset`` with ``labels [N, S]``: a word's first piece carries its tag; its
+    other pieces, the special tokens and the padding carry -100. Truncated and padded to ``max_length``."""
+    tag_id = {t: i for i, t in enumerate(tag_list)}
+    ids, mask, labels = [], [], []
+    for i in range(0, len(words), chunk):
+        enc = tokenizer.encode_words(words[i:i + chunk], max_length)
+        ids.append(enc["input_ids"])
+        mask.append(enc["attention_mask"])
+        wid = enc["word_ids"]  # [n, S] int64, -1 on special tokens and padding
+        lab = np.full(wid.shape, -100, dtype=np.int64)
+        for r in range(wid.shape[0]):
+            sent = tags[i + r]
+            prev = -1
+            for c in range(wid.shape[1]):
+                k = int(wid[r, c])
+                if k >= 0 and k != prev:
+                    if sent[k] not in tag_id:
+                        raise ValueError(f"tag {sent[k]!r} is not in the tag list {tag_list}")
+                    lab[r, c] = tag_id[sent[k]]
+                if k >= 0:
+                    prev = k
+        labels.append(lab)
+    return ArrayDataset(np.concatenate(ids), np.concatenate(mask), np.concatenate(labels))
+
+
 def mask_dataset_static(ds: ArrayDataset, seed: int, mlm_probability: float, mask_id: int, special_ids,
                         rand_range) -> ArrayDataset:
     """Mask a raw corpus ONCE with the reference masker (ops/rng.py mlm_mask_reference), one call per example with

@@ -98,6 +98,18 @@ class Tokenizer:
         mask = np.asarray([e.attention_mask for e in enc], dtype=np.int8)
         return {"input_ids": ids, "attention_mask": mask}
 
+    def encode_words(self, sentences: Sequence[Sequence[str]], max_length: int) -> Dict[str, np.ndarray]:
+        """Pre-tokenised sentences (lists of words, ``is_pretokenized=True``), truncated and padded to ``max_length``
+        like :meth:`encode_batch`. ``word_ids [n, S]``: the index of the word a piece belongs to
+        (``Encoding.word_ids``), -1 on the special tokens and the padding."""
+        self.backend.enable_truncation(max_length)
+        self.backend.enable_padding(length=max_length, pad_id=self.pad_token_id)
+        enc = self.backend.encode_batch([list(s) for s in sentences], is_pretokenized=True)
+        ids = np.asarray([e.ids for e in enc], dtype=np.int32)
+        mask = np.asarray([e.attention_mask for e in enc], dtype=np.int8)
+        wid = np.asarray([[-1 if w is None else w for w in e.word_ids] for e in enc], dtype=np.int64)
+        return {"input_ids": ids, "attention_mask": mask, "word_ids": wid}
+
     def save_pretrained(self, save_directory: str) -> List[str]:
         os.makedirs(save_directory, exist_ok=True)
         tj = os.path.join(save_directory, "tokenizer.json")

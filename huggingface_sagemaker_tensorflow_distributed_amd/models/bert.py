@@ -252,6 +252,52 @@ class TransformerForSequenceClassification(_Base):
         return out
 
 
+class TransformerForTokenClassification(_Base):
+    """BertForTokenClassification / RobertaForTokenClassification / DistilBertForTokenClassification:
+    ``logits = classifier(dropout(sequence_output))`` over every row (no pooler, no dense layer), mean CE over the
+    rows whose label is not -100 (NER, POS tagging, chunking).
+
+    Inputs: padded ``[B, S]`` ids with ``[B, S]`` labels (logits ``[B, S, L]``), or a packed ``[1, T]`` buffer with
+    ``[T]`` labels (data/packing.py; logits ``[T, L]``). The head (``ops.token_head``) draws one dropout seed after
+    the encoder's; its site is the flat ``[rows, H]`` buffer. Nothing reads a device value on the host, so the
+    whole step captures into a graph (``graph_safe``)."""
+
+    graph_safe = True
+
+    def __init__(self, cfg: ModelConfig):
+        super().__init__(cfg)
+        self.base_prefix = {"bert": "bert", "roberta": "roberta", "distilbert": "distilbert"}[cfg.model_type]
+        self.classifier_weight, self.classifier_bias = _param(cfg.num_labels, cfg.hidden_size), _param(cfg.num_labels)
+
+    def architecture(self) -> str:
+        return {"bert": "BertForTokenClassification", "roberta": "RobertaForTokenClassification",
+                "distilbert": "DistilBertForTokenClassification"}[self.cfg.model_type]
+
+    def _head_hf_names(self):
+        yield "classifier.weight", "classifier_weight", None, 1
+        yield "classifier.bias", "classifier_bias", None, 1
+
+    def head_dropout(self) -> float:
+        c = self.cfg
+        if c.model_type == "distilbert":
+            return c.hidden_dropout_prob  # HF DistilBertForTokenClassification: nn.Dropout(config.dropout)
+        return c.classifier_dropout if c.classifier_dropout is not None else c.hidden_dropout_prob
+
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, *, cu_seqlens=None,
+                max_seqlen=None, position_ids=None):
+        h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, self.training, cu_seqlens=cu_seqlens,
+                         max_seqlen=max_seqlen, position_ids=position_ids, first_token_only=False)
+        H = h.shape[-1]
+        p = self.head_dropout() if self.training else 0.0
+        seed = self.rng.next() if p else 0
+        out = ops.token_head(h.reshape(-1, H), self.classifier_weight, self.classifier_bias, labels, p, seed)
+        shape = tuple(h.shape[:-1]) + (self.cfg.num_labels,)  # [B, S, L] padded, [T, L] packed
+        if labels is None:
+            return out.view(shape)
+        loss, logits = out
+        return loss, logits.view(shape)
+
+
 class RobertaForMaskedLM(_Base):
     """RoBERTa MLM (decoder tied to the word embeddings), for the roberta-large pretraining config."""
 
@@ -389,6 +435,8 @@ def build_model(cfg: ModelConfig, task: str = "sequence-classification", seed: O
         if cfg.model_type != "roberta":
             raise ValueError("masked-lm is provided for roberta configs")
         m = RobertaForMaskedLM(cfg)
+    elif task in ("token-classification", "token-cls"):
+        m = TransformerForTokenClassification(cfg)
     else:
         raise ValueError(task)
     g = None

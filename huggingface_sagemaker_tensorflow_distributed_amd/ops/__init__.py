@@ -9,7 +9,8 @@
 
 ``HSD_OPS=torch`` forces the reference path on GPU (only for A/B measurements of the kernels); ``HSD_FP32_OPS=torch``
 does so for fp32 tensors only. ``HSD_CLS_ROWS_ONLY=0`` keeps the last encoder layer of a sequence-classification
-model on all rows (:func:`attn_block_cls`; tests and same-process A/Bs).
+model on all rows (:func:`attn_block_cls`; tests and same-process A/Bs). ``HSD_TOKEN_HEAD=composed`` runs the
+token-classification head (:func:`token_head`) as composed ops instead of its fused kernels (A/B measurements).
 """
 from __future__ import annotations
 
@@ -24,6 +25,9 @@ _FORCE_TORCH = os.environ.get("HSD_OPS", "").lower() == "torch"
 _FP32_TORCH = os.environ.get("HSD_FP32_OPS", "").lower() == "torch"
 # the last encoder layer of a sequence-classification model on its first-token rows only (attn_block_cls)
 CLS_ROWS_ONLY = os.environ.get("HSD_CLS_ROWS_ONLY", "1").strip().lower() not in ("0", "off", "false")
+# HSD_TOKEN_HEAD=composed: the token-classification head as dropout -> linear -> cross_entropy instead of the fused
+# kernels of csrc/kernels/token_head.hip (A/B measurements)
+TOKEN_HEAD_FUSED = os.environ.get("HSD_TOKEN_HEAD", "fused").strip().lower() != "composed"
 
 
 def _hip(x: torch.Tensor) -> bool:
@@ -249,6 +253,48 @@ def cls_head(h, w1, b1, w2, b2, labels, act: str, p_in: float, seed_in: int, p: 
     if labels is None:
         return logits
     return cross_entropy(logits, labels), logits
+
+
+def token_head(h2d, w, b, labels, p: float, seed: int):
+    """Token-classification head on every row of ``h2d`` [R, H]: ``logits = dropout(h) Wᵀ + b`` [R, C] and, with
+    ``labels`` [R], the CE over the rows whose label is not -100 divided by ``max(n_valid, 1)`` (0 when every row is
+    ignored). Returns ``logits`` without labels, else ``(loss, logits)`` with the fused {mean loss, hits, n_valid,
+    loss sum} on ``loss._hsd_stats`` and the hits on ``loss._hsd_correct`` (every path: nothing reads a device value
+    on the host).
+
+    bf16 GPU tensors within ``hip.token_head_ok`` (H % 8 == 0, H <= 1024, 2 <= C <= 16) run the fused kernels of
+    csrc/kernels/token_head.hip, unless ``HSD_TOKEN_HEAD=composed``. Everything else (CPU tensors, fp32 GPU tensors,
+    ``HSD_OPS=torch``, other shapes) runs the composed ``dropout -> linear -> cross_entropy`` with the same seed and
+    so the same mask; the all-torch form of it is ``reference.token_head``, the kernels' oracle."""
+    lab = labels.reshape(-1) if labels is not None else None
+    needs_grad = torch.is_grad_enabled() and (h2d.requires_grad or w.requires_grad or b.requires_grad)
+    if _hip(h2d) and TOKEN_HEAD_FUSED and _hipmod().token_head_ok(h2d, w) and not (lab is None and needs_grad):
+        if lab is None:  # inference: the fused forward alone (differentiable logits take the composed ops below)
+            return _hipmod().token_head_logits(h2d, w, b, p, seed)
+        loss, logits, stats = _hipmod().token_head(h2d, w, b, lab, p, seed)
+        loss._hsd_correct = stats[1]
+        loss._hsd_stats = stats
+        return loss, logits
+    if _hip(h2d) or (_hip32(h2d) and w.shape[0] % 4 == 0):  # (the fp32 GEMM epilogue takes whole groups of 4 columns)
+        logits = linear(dropout(h2d, p, seed), w, b)
+        if lab is None:
+            return logits
+        lsum = torch.nn.functional.cross_entropy(logits.float(), lab.long(), ignore_index=-100, reduction="sum")
+        with torch.no_grad():
+            ok = lab.ne(-100)
+            n = ok.sum().to(torch.float32)
+            hits = ((logits.argmax(dim=-1) == lab) & ok).sum().to(torch.float32)
+        loss = lsum / n.clamp(min=1.0)
+        with torch.no_grad():
+            stats = torch.stack([loss.detach().float(), hits, n, lsum.detach().float()])
+    else:
+        out = _ref.token_head(h2d, w, b, lab, p, seed, True)
+        if lab is None:
+            return out
+        loss, logits, stats = out
+    loss._hsd_correct = stats[1]
+    loss._hsd_stats = stats
+    return loss, logits
 
 
 def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):

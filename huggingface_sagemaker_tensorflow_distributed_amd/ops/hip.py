@@ -1388,6 +1388,72 @@ def cls_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed):
     return _ClsHead.apply(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed)
 
 
+# ------------------------------------------------------------------------------------------ token-classification head
+def token_head_ok(h2d, w) -> bool:
+    """What csrc/kernels/token_head.hip takes: bf16 rows [R, H] with H % 8 == 0, H <= 1024, and 2 <= C <= 16."""
+    if h2d.dim() != 2 or w.dim() != 2:
+        return False
+    R, H = h2d.shape
+    return (h2d.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and 1 <= R < (1 << 31) - 16 and H % 8 == 0
+            and 8 <= H <= 1024 and 2 <= w.shape[0] <= 16 and w.shape[1] == H)
+
+
+class _TokenHead(torch.autograd.Function):
+    """Every row of h -> fused dropout / classifier / CE / accuracy (token_head.hip: one kernel + the stats reducer).
+    Backward: one fused kernel (CE grad, dh with the dropout mask, per-block fp32 dW / db slabs in the shared
+    workspace) + the slab reducer that adds into main_grad."""
+
+    @staticmethod
+    def forward(ctx, h2d, w, b, labels, p, seed):
+        R, H = h2d.shape
+        C = w.shape[0]
+        x = h2d.contiguous()
+        wc, bc = w.contiguous(), b.contiguous()
+        logits = torch.empty((R, C), dtype=x.dtype, device=x.device)
+        partials = torch.empty(_C.token_head_fwd_blocks(R) * 4, dtype=torch.float32, device=x.device)
+        stats = torch.empty(4, dtype=torch.float32, device=x.device)
+        lab = labels.contiguous().long()
+        _C.token_head_fwd(x, wc, bc, lab, logits, partials, stats, float(p), _s64(seed))
+        ctx.save_for_backward(x, w, b, logits, lab, stats)
+        ctx.cfg = (float(p), seed)
+        ctx.mark_non_differentiable(logits, stats)
+        ctx.set_materialize_grads(False)
+        return stats[0], logits, stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits, _dstats):
+        x, w, b, logits, lab, stats = ctx.saved_tensors
+        p, seed = ctx.cfg
+        R, H = x.shape
+        C = w.shape[0]
+        g_w, g_b = _Grad(w), _Grad(b)
+        if dloss is None:
+            dloss = torch.zeros((), dtype=torch.float32, device=x.device)
+        dl = dloss.reshape(1).to(torch.float32).contiguous()
+        dh = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        part = _workspace(_C.token_head_bwd_blocks(R) * (C * H + C), x.device)
+        _C.token_head_bwd(x, w.contiguous(), logits, lab, stats, dl, dh, part, g_w.buf.view(-1), g_b.buf.view(-1),
+                          p, _s64(seed))
+        return dh, g_w.done(), g_b.done(), None, None, None
+
+
+def token_head(h2d, w, b, labels, p, seed):
+    """(loss, logits, stats) of the fused token-classification head (labels [R] required); stats = fp32
+    {mean loss, argmax hits, rows scored, loss sum}."""
+    return _TokenHead.apply(h2d, w, b, labels, p, seed)
+
+
+def token_head_logits(h2d, w, b, p, seed):
+    """The fused head's logits alone (inference: no labels, no autograd)."""
+    x = h2d.contiguous()
+    logits = torch.empty((x.shape[0], w.shape[0]), dtype=x.dtype, device=x.device)
+    partials = torch.empty(_C.token_head_fwd_blocks(x.shape[0]) * 4, dtype=torch.float32, device=x.device)
+    stats = torch.empty(4, dtype=torch.float32, device=x.device)
+    _C.token_head_fwd(x.detach(), w.detach().contiguous(), b.detach().contiguous(), None, logits, partials, stats,
+                      float(p), _s64(seed))
+    return logits
+
+
 # ------------------------------------------------------------------------------------------ masked-LM head
 def mlm_head_ok(h2d, w1, wemb) -> bool:
     T, H = h2d.shape

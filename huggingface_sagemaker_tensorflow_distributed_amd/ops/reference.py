@@ -156,6 +156,27 @@ def cls_head(x, w1, b1, w2, b2, act: str, p_in: float, seed_in: int, p: float, s
     return F.linear(h, w2, b2)
 
 
+def token_head(h2d, w, b, labels, p: float, seed: int, training: bool = True):
+    """Token-classification head on every row of ``h2d`` [R, H] (HF ``*ForTokenClassification``):
+    ``logits = dropout(h) Wᵀ + b`` [R, C]; the dropout site is the flat ``[R, H]`` buffer. With ``labels`` [R]
+    returns ``(loss, logits, stats)``: ``loss`` = CE summed over the rows whose label is not -100, divided by
+    ``max(n_valid, 1)`` (0, not NaN, when every row is ignored), and ``stats`` = fp32 {mean loss, first-maximum argmax
+    hits, n_valid, loss sum}. Without labels: the logits."""
+    logits = F.linear(dropout(h2d, p, seed, training), w, b)
+    if labels is None:
+        return logits
+    lab = labels.reshape(-1).long()
+    lsum = F.cross_entropy(logits.float(), lab, ignore_index=-100, reduction="sum")
+    with torch.no_grad():
+        ok = lab.ne(-100)
+        n = ok.sum().to(torch.float32)
+        hits = ((logits.argmax(dim=-1) == lab) & ok).sum().to(torch.float32)
+    loss = lsum / n.clamp(min=1.0)
+    with torch.no_grad():
+        stats = torch.stack([loss.detach().float(), hits, n, lsum.detach().float()])
+    return loss, logits, stats
+
+
 def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps: float, wemb, bias, vocab: int):
     """RoBERTa LM head on the masked positions (labels != -100) of ``h2d`` [T, H]: ``LN(gelu(x W1ᵀ + b1))`` ->
     tied decoder (``wemb[:vocab]``, ``bias[:vocab]``) -> mean CE. Returns (loss, logits [n_masked, vocab])."""

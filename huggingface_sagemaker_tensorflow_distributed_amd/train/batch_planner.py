@@ -89,6 +89,11 @@ def _probe_peak(model, store, cfg, batch: int, seq_len: int, device) -> int:
     if model.__class__.__name__ == "RobertaForMaskedLM":
         labels = torch.full((batch, seq_len), -100, dtype=torch.long, device=device)
         labels[:, ::7] = ids[:, ::7]
+    elif model.__class__.__name__ == "TransformerForTokenClassification":
+        # per-token labels [B, S], every fourth one ignored (word-continuation pieces)
+        labels = torch.randint(0, max(2, cfg.num_labels), (batch, seq_len), generator=g)
+        labels[:, ::4] = -100
+        labels = labels.to(device)
     torch.cuda.synchronize(device)
     torch.cuda.empty_cache()
     torch.cuda.reset_peak_memory_stats(device)

@@ -71,6 +71,30 @@ def _datasets(args, cfg, tokenizer, max_len: int):
             tr = hdata.mask_dataset_static(tr, args.seed, p, mask_id, special, rr)
             te = hdata.mask_dataset_static(te, args.seed + 1, p, mask_id, special, rr)
         return tr, te
+    if getattr(args, "task", "sequence-classification") == "token-classification":
+        if args.dataset == "synthetic":
+            kw = {"num_labels": cfg.num_labels, "pad_id": cfg.pad_token_id}
+            if cfg.model_type == "roberta":
+                kw.update(cls_id=cfg.bos_token_id if cfg.bos_token_id is not None else 0,
+                          sep_id=cfg.eos_token_id if cfg.eos_token_id is not None else 2)
+            tr = hdata.synthetic_token_classification(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed, **kw)
+            te = hdata.synthetic_token_classification(n_eval or 512, max_len, cfg.vocab_size, seed=args.seed + 1, **kw)
+            return tr, te
+        if args.dataset == "conll":
+            tags = _conll_tags(args)
+            out = []
+            for split, n in (("train", n_train), ("test", n_eval)):
+                from ..data.datasets import conll_split_path
+
+                words, wtags = hdata.read_conll(conll_split_path(args.dataset_dir, split))
+                if n:
+                    words, wtags = words[:n], wtags[:n]
+                out.append(hdata.tokenize_conll(tokenizer, words, wtags, tags, max_len))
+            return out[0], out[1]
+        raise ValueError(f"--task token-classification trains on --dataset synthetic or conll (per-token labels); "
+                         f"--dataset {args.dataset} holds one label per text")
+    if args.dataset == "conll":
+        raise ValueError("--dataset conll holds per-token tags (--task token-classification)")
     if args.dataset == "synthetic-bigram":
         raise ValueError("--dataset synthetic-bigram is a masked-lm corpus (--task masked-lm)")
     if args.dataset == "synthetic":
@@ -88,6 +112,18 @@ def _datasets(args, cfg, tokenizer, max_len: int):
         texts, labels = texts[:n_eval], labels[:n_eval]
     te = hdata.tokenize_dataset(tokenizer, texts, labels, max_len)
     return tr, te
+
+
+def _conll_tags(args) -> Optional[List[str]]:
+    """The tag list of ``--task token-classification --dataset conll`` (read once, kept on ``args``)."""
+    if getattr(args, "task", "") != "token-classification" or args.dataset != "conll":
+        return None
+    tags = getattr(args, "_conll_tags", None)
+    if tags is None:
+        if not args.dataset_dir:
+            raise ValueError("--dataset conll needs --dataset_dir (train.txt and test.txt in CoNLL column format)")
+        tags = args._conll_tags = hdata.conll_tag_list(args.dataset_dir)
+    return tags
 
 
 def _provenance(args, model, rank: int, n_train: int, n_eval: int, batch_plan=None) -> dict:
@@ -109,6 +145,14 @@ def _provenance(args, model, rank: int, n_train: int, n_eval: int, batch_plan=No
                                                               else "masked when built, full length"))
         logger.info("masked-lm corpus: %s; --mlm_masking %s, --mlm_probability %g", info["corpus"],
                     info["mlm_masking"], info["mlm_probability"])
+    if getattr(args, "task", "sequence-classification") == "token-classification":
+        info["task"] = "token-classification"
+        info["num_labels"] = int(model.cfg.num_labels)
+        info["corpus"] = ("CoNLL column files in " + str(args.dataset_dir) if args.dataset == "conll" else
+                          "synthetic tagging corpus (tag = f(token, left neighbour), ragged lengths, ~25 % of the "
+                          "real tokens ignored)")
+        info["metric"] = "loss and accuracy over the labelled tokens (not entity-level F1)"
+        logger.info("token-classification corpus: %s; %d labels", info["corpus"], info["num_labels"])
     if batch_plan is not None:
         info["auto_batch"] = batch_plan.as_dict()
     if synthetic or weights == "random-init":
@@ -140,8 +184,18 @@ def build(args, mode: str):
     torch.manual_seed(args.seed)
 
     task = getattr(args, "task", "sequence-classification")
+    if task == "token-classification" and args.dataset not in ("synthetic", "conll"):
+        raise ValueError(f"--task token-classification trains on --dataset synthetic or conll (per-token labels); "
+                         f"--dataset {args.dataset} holds one label per text")
+    tags = _conll_tags(args)
+    if tags is not None:
+        if args.num_labels != len(tags):
+            logger.info("--dataset conll: %d tags %s; --num_labels %d -> %d", len(tags), tags, args.num_labels, len(tags))
+        args.num_labels = len(tags)
     model = from_pretrained(args.model_name_or_path or "bert-base-uncased", task=task, num_labels=args.num_labels,
                             seed=args.seed)
+    if tags is not None:
+        model.cfg.id2label = {str(i): t for i, t in enumerate(tags)}  # config.json id2label / label2id
     model.to(dev)
     model.rng.base_seed = args.seed
     model.rng.rank = rank

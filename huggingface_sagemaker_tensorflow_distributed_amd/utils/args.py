@@ -76,8 +76,10 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
                    help="pad/truncate length (default: tokenizer.model_max_length, 512 for BERT)")
     g.add_argument("--dataset", type=str, default="synthetic",
                    help="imdb | sst2 | synthetic | synthetic-bigram (masked-lm only: a learnable first-order corpus) | "
-                        "path to a local dataset directory/file")
-    g.add_argument("--dataset_dir", type=str, default=None, help="local directory holding imdb/sst2 data")
+                        "conll (token-classification only: train.txt / test.txt in CoNLL column format under "
+                        "--dataset_dir) | path to a local dataset directory/file")
+    g.add_argument("--dataset_dir", type=str, default=None,
+                   help="local directory holding imdb/sst2 data, or the CoNLL files of --dataset conll")
     g.add_argument("--num_train_examples", type=int, default=None, help="synthetic/limit train size")
     g.add_argument("--num_eval_examples", type=int, default=None, help="synthetic/limit eval size")
     g.add_argument("--max_steps", type=int, default=None, help="stop each epoch after this many steps")
@@ -135,8 +137,11 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
     g.add_argument("--log_every", type=int, default=50)
     g.add_argument("--device", type=str, default=None, help="cuda | cpu (default: cuda if available)")
     g.add_argument("--num_labels", type=int, default=2)
-    g.add_argument("--task", choices=["sequence-classification", "masked-lm"], default="sequence-classification",
-                   help="masked-lm: RoBERTa MLM pretraining (BASELINE.json config 5)")
+    g.add_argument("--task", choices=["sequence-classification", "masked-lm", "token-classification"],
+                   default="sequence-classification",
+                   help="masked-lm: RoBERTa MLM pretraining (BASELINE.json config 5); token-classification: one label "
+                        "per token (NER / POS tagging; --dataset synthetic or conll, --num_labels follows the tag list "
+                        "of a CoNLL directory)")
     g.add_argument("--mlm_masking", choices=["static", "dynamic"], default="static",
                    help="masked-lm: static = the corpus is masked once when it is built (every selected token becomes "
                         "<mask>); dynamic = RoBERTa's recipe, a fresh draw every step on the device (80 %% <mask>, 10 %% "
