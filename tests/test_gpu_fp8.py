@@ -82,6 +82,33 @@ def test_gemm8_matches_fp32_reference(gpu, M, N, K, epi, fa):
     err = (y.float() - ref).abs()
     tol = 2e-2 * ref.abs().max() + 1e-2 * ref.abs()
     assert (err <= tol).float().mean() > 0.999, float(err.max())
+    if epi == 8:
+        return
+    # every element, against fp64, within the bf16 kernels' bound (test_gpu_gemm._check: one bf16 ulp of each rounded
+    # intermediate + 2^-16 of the accumulation magnitude). fp8 products are exact in fp32, the dequantisation scale adds
+    # one fp32 rounding to the sum, and the epilogue is the bf16 kernels' own epilogue_bf16, so their bound applies
+    from test_gpu_gemm import _check
+
+    dx, dw = _deq(qx, sx, fa).double(), _deq(qw, sw, 0).double()
+    a64 = dx @ dw.t()
+    am = dx.abs() @ dw.abs().t()
+    del dx, dw
+    rb = lambda t: t.float().bfloat16().double()  # noqa: E731
+    b64, x64 = bias.double(), aux.double()
+    if epi == 0:
+        _check(y, a64, acc=2 * am)
+    elif epi == 1:
+        _check(y, a64 + b64, acc=2 * am)
+    elif epi == 3:
+        yb = rb(a64 + b64)
+        r64 = yb + x64
+        _check(y, r64, mag=2 * yb.abs() + x64.abs() + r64.abs(), acc=2 * am)
+    elif epi == 4:
+        r64 = rb(a64) + x64
+        _check(y, r64, mag=a64.abs() + x64.abs() + r64.abs(), acc=2 * am)
+    else:  # 9
+        r64 = rb(a64) * x64
+        _check(y, r64, mag=2 * a64.abs() * x64.abs() + r64.abs(), acc=2 * am)
 
 
 def test_store_fp8_weight_copies(gpu):
