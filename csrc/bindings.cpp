@@ -1318,6 +1318,73 @@ void token_head_bwd(torch::Tensor h, torch::Tensor W, torch::Tensor logits, torc
                              db.data_ptr<float>(), (int)R, (int)H, (int)C, p, (uint64_t)seed, cur_stream());
 }
 
+// the token head's backward from a given gradient table (question-answering: qa_head.hip). g0 fp32 [R][C]; cnt fp32,
+// >= C elements: g = g0 · dloss · gmul / max(cnt[c], 1). No logits, no labels.
+void token_head_bwd_given(torch::Tensor h, torch::Tensor W, torch::Tensor g0, torch::Tensor cnt, double gmul,
+                          torch::Tensor dloss, c10::optional<torch::Tensor> dh, torch::Tensor part, torch::Tensor dW,
+                          torch::Tensor db, double p, int64_t seed) {
+  TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() && h.scalar_type() == torch::kBFloat16, "token_head h");
+  const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
+  TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 16 && H % 8 == 0 && H >= 8 && H <= 1024 && C >= 2 && C <= 16,
+              "token_head: 1 <= rows < 2^31, H % 8 == 0, H <= 1024, 2 <= classes <= 16");
+  TORCH_CHECK(W.is_contiguous() && W.dim() == 2 && W.size(1) == H && W.scalar_type() == torch::kBFloat16,
+              "token_head W");
+  check_f32(g0, "g0");
+  check_f32(cnt, "cnt");
+  check_f32(dloss, "dloss");
+  check_f32(part, "part");
+  check_f32(dW, "dW");
+  check_f32(db, "db");
+  TORCH_CHECK(g0.numel() == R * C && cnt.numel() >= C && dloss.numel() >= 1, "token_head g0 / cnt / dloss");
+  TORCH_CHECK(part.numel() >= (int64_t)hsd::token_head_bwd_blocks((int)R) * (C * H + C), "token_head workspace");
+  TORCH_CHECK(dW.numel() == C * H && db.numel() == C, "token_head grads");
+  hsd::bf16_t* dhp = nullptr;
+  if (dh.has_value()) {
+    TORCH_CHECK(dh->is_contiguous() && dh->sizes() == h.sizes() && dh->scalar_type() == torch::kBFloat16, "dh");
+    dhp = BF(*dh);
+  }
+  hsd::launch_token_head_bwd_given(CBF(h), CBF(W), g0.data_ptr<float>(), cnt.data_ptr<float>(), (float)gmul,
+                                   dloss.data_ptr<float>(), dhp, part.data_ptr<float>(), dW.data_ptr<float>(),
+                                   db.data_ptr<float>(), (int)R, (int)H, (int)C, p, (uint64_t)seed, cur_stream());
+}
+
+// span-extraction loss (qa_head.hip). logits [R][2] bf16; cu int32 [B+1]; mask int64 [R] or none; pos int64 [B][2] or
+// none (pred only); rec fp32 [B][8], pred int32 [B][2], g0 fp32 [R][2], stats fp32 [8]
+void span_ce(torch::Tensor logits, torch::Tensor cu, c10::optional<torch::Tensor> mask,
+             c10::optional<torch::Tensor> pos, int64_t max_answer_length, torch::Tensor rec, torch::Tensor pred,
+             torch::Tensor g0, torch::Tensor stats) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.size(1) == 2 && logits.is_contiguous() &&
+              logits.scalar_type() == torch::kBFloat16, "span_ce logits [R][2] bf16");
+  const int64_t R = logits.size(0), B = cu.numel() - 1;
+  TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 30) && B >= 1, "span_ce: 1 <= rows < 2^30, at least one sequence");
+  TORCH_CHECK(cu.is_cuda() && cu.is_contiguous() && cu.scalar_type() == torch::kInt32, "span_ce cu int32");
+  TORCH_CHECK(pred.is_cuda() && pred.is_contiguous() && pred.scalar_type() == torch::kInt32 && pred.numel() == 2 * B,
+              "span_ce pred int32 [B][2]");
+  const int64_t* mp = nullptr;
+  if (mask.has_value()) {
+    TORCH_CHECK(mask->is_cuda() && mask->is_contiguous() && mask->scalar_type() == torch::kInt64 &&
+                mask->numel() == R, "span_ce mask int64 [R]");
+    mp = mask->data_ptr<int64_t>();
+  }
+  const int64_t* pp = nullptr;
+  float *recp = nullptr, *g0p = nullptr, *stp = nullptr;
+  if (pos.has_value()) {
+    TORCH_CHECK(pos->is_cuda() && pos->is_contiguous() && pos->scalar_type() == torch::kInt64 &&
+                pos->numel() == 2 * B, "span_ce positions int64 [B][2]");
+    pp = pos->data_ptr<int64_t>();
+    check_f32(rec, "rec");
+    check_f32(g0, "g0");
+    check_f32(stats, "stats");
+    TORCH_CHECK(rec.numel() >= 8 * B && g0.numel() == 2 * R && stats.numel() >= 8, "span_ce rec / g0 / stats");
+    recp = rec.data_ptr<float>();
+    g0p = g0.data_ptr<float>();
+    stp = stats.data_ptr<float>();
+  }
+  const int mal = (int)std::min<int64_t>(std::max<int64_t>(max_answer_length, 1), (int64_t)1 << 30);
+  hsd::launch_span_ce(CBF(logits), cu.data_ptr<int>(), mp, pp, mal, recp, pred.data_ptr<int>(), g0p, stp, (int)R,
+                      (int)B, cur_stream());
+}
+
 int64_t token_head_fwd_blocks(int64_t R) { return hsd::token_head_fwd_blocks((int)R); }
 int64_t token_head_bwd_blocks(int64_t R) { return hsd::token_head_bwd_blocks((int)R); }
 
@@ -1544,6 +1611,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cls_head_blocks", &cls_head_blocks);
   m.def("token_head_fwd", &token_head_fwd);
   m.def("token_head_bwd", &token_head_bwd);
+  m.def("token_head_bwd_given", &token_head_bwd_given);
+  m.def("span_ce", &span_ce);
   m.def("token_head_fwd_blocks", &token_head_fwd_blocks);
   m.def("token_head_bwd_blocks", &token_head_bwd_blocks);
   m.def("memset0", &memset0);

@@ -138,6 +138,16 @@ void launch_token_head_fwd(const bf16_t* h, const bf16_t* W, const bf16_t* b, co
 void launch_token_head_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* logits, const int64_t* labels,
                            const float* stats, const float* dloss, bf16_t* dh, float* part, float* dW, float* db,
                            int R, int H, int C, double p, uint64_t seed, hipStream_t st);
+// the same backward from a GIVEN per-row gradient table g0 [R][C] fp32 (zero rows are ignored rows):
+// g[row][c] = g0[row][c] · dloss · gmul / max(cnt[c], 1), cnt fp32 [C] on the device
+void launch_token_head_bwd_given(const bf16_t* h, const bf16_t* W, const float* g0, const float* cnt, float gmul,
+                                 const float* dloss, bf16_t* dh, float* part, float* dW, float* db, int R, int H,
+                                 int C, double p, uint64_t seed, hipStream_t st);
+// qa_head.hip: span-extraction loss of --task question-answering on logits [R][2] bf16. One workgroup per sequence
+// (rows cu[b] .. cu[b+1]-1, at most 1,024; mask int64 [R] optional), then the stats reducer. pos int64 [B][2] may be
+// null (pred only: rec, g0 and stats untouched). rec fp32 [B][8], pred int32 [B][2], g0 fp32 [R][2], stats fp32 [8].
+void launch_span_ce(const bf16_t* logits, const int* cu, const int64_t* mask, const int64_t* pos, int max_answer_length,
+                    float* rec, int* pred, float* g0, float* stats, int R, int B, hipStream_t st);
 // attention.hip
 bool attn_streaming(int S);
 // kmask (optional, streaming S > 128 kernels: attn_keep_mask_supported): the forward writes its dropout keep bits

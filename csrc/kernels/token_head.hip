@@ -44,6 +44,7 @@
 // hipcc -Rpass-analysis=kernel-resource-usage (gfx950, -O3; one instantiation each, C and H are run-time values):
 //   tok_fwd_kernel     152 VGPRs + 4 AGPRs, scratch 0, occupancy 3 waves / SIMD, LDS 33,072 B
 //   tok_bwd_kernel     233 VGPRs,           scratch 0, occupancy 2 waves / SIMD, LDS 48,640 B
+//   tok_bwd_kernel<true> (the given-gradient entry of qa_head.hip): 235 VGPRs, scratch 0, LDS 48,640 B
 //   tok_stats_kernel    14 VGPRs,           scratch 0;  tok_reduce_kernel 12 VGPRs, scratch 0
 #include "common.h"
 #include "launchers.h"
@@ -259,13 +260,19 @@ __device__ __forceinline__ void load_tile(const bf16_t* __restrict__ h, int tile
   }
 }
 
+// GIVEN = false: g from the logits and the labels (the token-classification loss above). GIVEN = true: the caller's
+// per-row gradient table g0 [R][C] fp32 (launch_token_head_bwd_given: the span head of qa_head.hip, whose softmax runs
+// along the sequence), g[row][c] = g0[row][c] · dloss · gmul / max(cnt[c], 1); logits, labels and stats are not read.
+// A row of zeros in g0 is an ignored row. Everything from g on is the same code.
+template <bool GIVEN>
 __global__ __launch_bounds__(256, 2) void tok_bwd_kernel(const bf16_t* __restrict__ h, const bf16_t* __restrict__ W,
                                                          const bf16_t* __restrict__ logits,
                                                          const int64_t* __restrict__ labels,
                                                          const float* __restrict__ stats,
                                                          const float* __restrict__ dloss, bf16_t* __restrict__ dh,
                                                          float* __restrict__ part, int R, int H, int C, int write_dh,
-                                                         DropoutParams dp) {
+                                                         DropoutParams dp, const float* __restrict__ g0,
+                                                         const float* __restrict__ cnt, float gmul) {
   dp = resolve_seed(dp);
   __shared__ __attribute__((aligned(16))) bf16_t Wt[MAXH * WT_STRIDE];
   __shared__ __attribute__((aligned(16))) bf16_t Dst[4][TR * D_STRIDE];
@@ -279,7 +286,14 @@ __global__ __launch_bounds__(256, 2) void tok_bwd_kernel(const bf16_t* __restric
   }
   __syncthreads();
 
-  const float scale = dloss[0] / fmaxf(stats[2], 1.0f);
+  float scale = 0.f, cscale[4] = {0.f, 0.f, 0.f, 0.f};  // GIVEN: one factor per class 4q + j of this lane
+  if constexpr (GIVEN) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (4 * q + j < C) cscale[j] = dloss[0] * gmul / fmaxf(cnt[4 * q + j], 1.0f);
+  } else {
+    scale = dloss[0] / fmaxf(stats[2], 1.0f);
+  }
   // transposed-read addresses (ds_read_b64_tr_b16): lane 4a + p of a 16-lane group supplies row a, columns 4p .. 4p+3
   // of the group's 4-row block (rows 4q .. 4q+3 of the tile); lane i of the group receives column i of those rows
   const int ta = r >> 2, tp = r & 3;
@@ -305,8 +319,18 @@ __global__ __launch_bounds__(256, 2) void tok_bwd_kernel(const bf16_t* __restric
     load_tile(h, tile + gridDim.x, ntiles, R, H, wave, r, q, nxt);
     const int row = tile * TR + r;
     const bool rvalid = row < R;
-    const int64_t lab = rvalid ? labels[row] : -100;
-    const bool valid = lab >= 0 && lab < C;
+    int64_t lab = -100;
+    bool valid;
+    float gv[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (GIVEN) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (rvalid && 4 * q + j < C) gv[j] = g0[(int64_t)row * C + 4 * q + j];
+      valid = gv[0] != 0.f || gv[1] != 0.f || gv[2] != 0.f || gv[3] != 0.f;  // this lane's classes of its row
+    } else {
+      lab = rvalid ? labels[row] : -100;
+      valid = lab >= 0 && lab < C;
+    }
     if (__ballot(valid) == 0ull) {
       // every row of the tile is ignored: zeros, nothing else (the branch is wave-uniform)
       if (write_dh) {
@@ -318,30 +342,38 @@ __global__ __launch_bounds__(256, 2) void tok_bwd_kernel(const bf16_t* __restric
       }
     } else {
       // g of this lane's 4 classes of its row
-      float e[4], m = -INFINITY;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        e[j] = rvalid && 4 * q + j < C ? bf2f(logits[(int64_t)row * C + 4 * q + j]) : -INFINITY;
-        m = fmaxf(m, e[j]);
-      }
-      m = fmaxf(m, __shfl_xor(m, 16, 64));
-      m = fmaxf(m, __shfl_xor(m, 32, 64));
-      if (!rvalid) m = 0.f;
-      float se = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        e[j] = __expf(e[j] - m);  // exp(-inf) = 0 in the padding classes
-        se += e[j];
-      }
-      se += __shfl_xor(se, 16, 64);
-      se += __shfl_xor(se, 32, 64);
-      const float inv = 1.0f / se;
       float g[4];
+      if constexpr (GIVEN) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = 4 * q + j;
-        g[j] = valid && c < C ? (e[j] * inv - (c == (int)lab ? 1.f : 0.f)) * scale : 0.f;
-        accb[j] += g[j];
+        for (int j = 0; j < 4; ++j) {
+          g[j] = gv[j] * cscale[j];
+          accb[j] += g[j];
+        }
+      } else {
+        float e[4], m = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          e[j] = rvalid && 4 * q + j < C ? bf2f(logits[(int64_t)row * C + 4 * q + j]) : -INFINITY;
+          m = fmaxf(m, e[j]);
+        }
+        m = fmaxf(m, __shfl_xor(m, 16, 64));
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        if (!rvalid) m = 0.f;
+        float se = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          e[j] = __expf(e[j] - m);  // exp(-inf) = 0 in the padding classes
+          se += e[j];
+        }
+        se += __shfl_xor(se, 16, 64);
+        se += __shfl_xor(se, 32, 64);
+        const float inv = 1.0f / se;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int c = 4 * q + j;
+          g[j] = valid && c < C ? (e[j] * inv - (c == (int)lab ? 1.f : 0.f)) * scale : 0.f;
+          accb[j] += g[j];
+        }
       }
       const u32x2 gpk = {pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3])};
       const bf16x4 gb = __builtin_bit_cast(bf16x4, gpk);  // B operand of dh: [k = class 4q + j][n = row r]
@@ -476,8 +508,24 @@ void launch_token_head_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* logit
                            int R, int H, int C, double p, uint64_t seed, hipStream_t st) {
   const int nblk = token_head_bwd_blocks(R);
   const DropoutParams dp = make_dropout(p, seed);
-  hipLaunchKernelGGL(tok::tok_bwd_kernel, dim3(nblk), dim3(256), 0, st, h, W, logits, labels, stats, dloss, dh, part,
-                     R, H, C, dh != nullptr ? 1 : 0, dp);
+  hipLaunchKernelGGL(tok::tok_bwd_kernel<false>, dim3(nblk), dim3(256), 0, st, h, W, logits, labels, stats, dloss, dh,
+                     part, R, H, C, dh != nullptr ? 1 : 0, dp, (const float*)nullptr, (const float*)nullptr, 0.f);
+  HSD_CHECK_LAUNCH();
+  const int n = C * H + C;
+  hipLaunchKernelGGL(tok::tok_reduce_kernel, dim3((n + tok::RED_X - 1) / tok::RED_X), dim3(tok::RED_X * tok::RED_G), 0,
+                     st, (const float*)part, nblk, n, C * H,
+                     dW, db);
+  HSD_CHECK_LAUNCH();
+}
+
+void launch_token_head_bwd_given(const bf16_t* h, const bf16_t* W, const float* g0, const float* cnt, float gmul,
+                                 const float* dloss, bf16_t* dh, float* part, float* dW, float* db, int R, int H,
+                                 int C, double p, uint64_t seed, hipStream_t st) {
+  const int nblk = token_head_bwd_blocks(R);
+  const DropoutParams dp = make_dropout(p, seed);
+  hipLaunchKernelGGL(tok::tok_bwd_kernel<true>, dim3(nblk), dim3(256), 0, st, h, W, (const bf16_t*)nullptr,
+                     (const int64_t*)nullptr, (const float*)nullptr, dloss, dh, part, R, H, C, dh != nullptr ? 1 : 0,
+                     dp, g0, cnt, gmul);
   HSD_CHECK_LAUNCH();
   const int n = C * H + C;
   hipLaunchKernelGGL(tok::tok_reduce_kernel, dim3((n + tok::RED_X - 1) / tok::RED_X), dim3(tok::RED_X * tok::RED_G), 0,

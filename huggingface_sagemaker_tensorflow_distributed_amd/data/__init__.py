@@ -1,6 +1,7 @@
-from .datasets import (ArrayDataset, bigram_successor, conll_tag_list, load_text_split, mask_dataset_static,
+from .datasets import (ArrayDataset, answer_length_table, bigram_successor, conll_tag_list, load_text_split, mask_dataset_static,
                        read_conll, synthetic_bigram, synthetic_classification, synthetic_mlm, synthetic_mlm_raw,
-                       synthetic_token_classification, tag_table, tokenize_conll, tokenize_dataset)
+                       synthetic_question_answering, synthetic_token_classification, tag_table, read_squad, tokenize_conll,
+                       tokenize_dataset, tokenize_squad)
 from .loader import BatchLoader
 from .packing import pack_batch, position_rule, unpack_rows
 from .tokenization import Tokenizer, load_tokenizer
@@ -8,4 +9,5 @@ from .tokenization import Tokenizer, load_tokenizer
 __all__ = ["ArrayDataset", "synthetic_classification", "synthetic_mlm", "synthetic_mlm_raw", "synthetic_bigram",
            "bigram_successor", "mask_dataset_static", "load_text_split", "tokenize_dataset",
            "synthetic_token_classification", "tag_table", "read_conll", "conll_tag_list", "tokenize_conll",
+           "synthetic_question_answering", "answer_length_table", "read_squad", "tokenize_squad",
            "BatchLoader", "Tokenizer", "load_tokenizer", "pack_batch", "position_rule", "unpack_rows"]

@@ -31,7 +31,9 @@ NEG_MARK = 2919  # "bad"
 class ArrayDataset:
     input_ids: np.ndarray        # [N, S] int32
     attention_mask: np.ndarray   # [N, S] int8
-    labels: np.ndarray           # [N] int64 (or [N, S] for MLM)
+    labels: np.ndarray           # [N] int64 (or [N, S] for MLM / token classification, [N, 2] for question answering)
+    token_type_ids: Optional[np.ndarray] = None  # [N, S] segment ids (question answering with BERT), else None
+    span_labels: bool = False    # labels are [N, 2] (start, end) token positions, not one label per row
 
     def __len__(self) -> int:
         return int(self.input_ids.shape[0])
@@ -164,6 +166,125 @@ def synthetic_token_classification(num_examples: int, seq_len: int, vocab_size: 
     real = (pos >= 1) & (pos < (lengths[:, None] - 1))
     labels = np.where(real & ~drop, tags, -100).astype(np.int64)
     return ArrayDataset(ids.astype(np.int32), mask, labels)
+
+
+# ------------------------------------------------------------------------------------------ question answering
+def answer_length_table(vocab_size: int) -> np.ndarray:
+    """``table [V]`` of the synthetic question-answering corpus: a fixed random map token id -> ``[0, 4)``, a function
+    of ``vocab_size`` and a constant only (the train and eval splits share it)."""
+    return np.random.default_rng([0x51AD, int(vocab_size)]).integers(0, 4, size=vocab_size, dtype=np.int64)
+
+
+def synthetic_question_answering(num_examples: int, seq_len: int, vocab_size: int, seed: int = 0,
+                                 full_length: bool = False, segment_ids: bool = True, no_answer_fraction: float = 0.1,
+                                 cls_id: int = 101, sep_id: int = 102, pad_id: int = 0) -> ArrayDataset:
+    """``--task question-answering --dataset synthetic``: a learnable span corpus in the layout
+    ``[CLS] q [SEP] context [SEP]``, lengths uniform in ``[S/4, S]`` (at least 12). The question ``q`` is ONE key token
+    and the context holds it exactly once (keys and context tokens come from disjoint id ranges); the answer starts at
+    the token after it and runs for ``1 + table[x[start]] % 4`` tokens (:func:`answer_length_table`). A seeded
+    ``no_answer_fraction`` of the examples has no key in its context and the label ``(0, 0)`` (the ``[CLS]`` span of
+    SQuAD v2). ``labels [N, 2]`` = (start, end) token indices; ``token_type_ids`` 0 on ``[CLS] q [SEP]`` and the
+    padding, 1 on ``context [SEP]`` (``segment_ids=False``: none, for RoBERTa / DistilBERT)."""
+    if seq_len < 12:
+        raise ValueError(f"synthetic_question_answering needs seq_len >= 12, got {seq_len}")
+    rng = np.random.default_rng(seed)
+    lo = 1000 if vocab_size > 4000 else 4
+    nkeys = max(1, (vocab_size - lo) // 4)
+    ids = rng.integers(lo + nkeys, vocab_size, size=(num_examples, seq_len), dtype=np.int64)  # context tokens
+    if full_length:
+        lengths = np.full(num_examples, seq_len)
+    else:
+        lengths = rng.integers(max(12, seq_len // 4), seq_len + 1, size=num_examples)
+    keys = rng.integers(lo, lo + nkeys, size=num_examples, dtype=np.int64)
+    special = [cls_id % vocab_size, sep_id % vocab_size, pad_id]  # a key that is [SEP] would occur twice
+    spare = [k for k in range(lo, lo + nkeys) if k not in special]
+    if not spare:
+        raise ValueError(f"synthetic_question_answering: vocab_size {vocab_size} leaves no key token")
+    keys[np.isin(keys, special)] = spare[0]
+    no_answer = rng.random(num_examples) < no_answer_fraction
+    # the key sits at k in [3, len - 6]: the answer (at most 4 tokens from k + 1) ends before the final [SEP]
+    where = 3 + (rng.random(num_examples) * (lengths - 8)).astype(np.int64)
+    table = answer_length_table(vocab_size)
+    labels = np.zeros((num_examples, 2), dtype=np.int64)
+    rows = np.arange(num_examples)
+    ids[:, 0] = cls_id % vocab_size
+    ids[:, 1] = keys
+    ids[:, 2] = sep_id % vocab_size
+    ids[rows, lengths - 1] = sep_id % vocab_size
+    has = ~no_answer
+    ids[rows[has], where[has]] = keys[has]
+    start = where + 1
+    end = start + table[ids[rows, start]] % 4
+    labels[has, 0] = start[has]
+    labels[has, 1] = end[has]
+    pos = np.arange(seq_len)[None, :]
+    mask = pos < lengths[:, None]
+    ids[~mask] = pad_id
+    tt = ((pos >= 3) & mask).astype(np.int8) if segment_ids else None
+    return ArrayDataset(ids.astype(np.int32), mask.astype(np.int8), labels, token_type_ids=tt, span_labels=True)
+
+
+def read_squad(path: str) -> List[Dict[str, object]]:
+    """SQuAD-format JSON (v1.1 or v2 layout: ``data[].paragraphs[].{context, qas[]}``) -> one dict per question:
+    ``question``, ``context``, ``answers`` = list of ``(text, answer_start)`` (empty for a v2 ``is_impossible``
+    question) and ``id``."""
+    with open(path, encoding="utf-8") as f:
+        doc = json.load(f)
+    out: List[Dict[str, object]] = []
+    for article in doc["data"]:
+        for para in article["paragraphs"]:
+            ctx = para["context"]
+            for qa in para["qas"]:
+                ans = [] if qa.get("is_impossible", False) else [(a["text"], int(a["answer_start"]))
+                                                                 for a in qa.get("answers", [])]
+                out.append({"id": qa.get("id", str(len(out))), "question": qa["question"].strip(), "context": ctx,
+                            "answers": ans})
+    return out
+
+
+def squad_split_path(dataset_dir: str, split: str) -> str:
+    pats = ["train*.json"] if split == "train" else ["dev*.json", "validation*.json", "test*.json"]
+    for pat in pats:
+        hits = sorted(glob.glob(os.path.join(dataset_dir or "", pat)))
+        if hits:
+            return hits[0]
+    raise FileNotFoundError(f"--dataset squad: none of {pats} in --dataset_dir {dataset_dir!r}")
+
+
+def tokenize_squad(tokenizer, examples: List[Dict[str, object]], max_length: int, doc_stride: int = 128,
+                   segment_ids: bool = True, chunk: int = 256) -> ArrayDataset:
+    """Questions and contexts -> windows of ``max_length`` tokens (``Tokenizer.encode_pairs``: only the context is
+    truncated, a long context yields overlapping windows ``doc_stride`` tokens apart). ``labels [N, 2]``: the token
+    positions, within the window, of the first answer's first and last character; ``(0, 0)`` for a window that does
+    not hold the whole answer and for a question without one. ``example_index [N]`` (an attribute of the result) maps
+    a window to its question."""
+    ids, mask, tts, labels, owner = [], [], [], [], []
+    for i in range(0, len(examples), chunk):
+        part = examples[i:i + chunk]
+        enc = tokenizer.encode_pairs([e["question"] for e in part], [e["context"] for e in part], max_length,
+                                     doc_stride)
+        off, sid = enc["offsets"], enc["sequence_ids"]
+        lab = np.zeros((off.shape[0], 2), dtype=np.int64)
+        for w in range(off.shape[0]):
+            ans = part[int(enc["sample"][w])]["answers"]
+            if not ans:
+                continue
+            text, a0 = ans[0]
+            a1 = a0 + len(text)
+            ctx = sid[w] == 1
+            s = np.nonzero(ctx & (off[w, :, 0] <= a0) & (a0 < off[w, :, 1]))[0]
+            e = np.nonzero(ctx & (off[w, :, 0] < a1) & (a1 <= off[w, :, 1]))[0]
+            if s.size and e.size and s[0] <= e[-1]:
+                lab[w] = (s[0], e[-1])
+        ids.append(enc["input_ids"])
+        mask.append(enc["attention_mask"])
+        tts.append(enc["token_type_ids"])
+        labels.append(lab)
+        owner.append(enc["sample"] + i)
+    ds = ArrayDataset(np.concatenate(ids), np.concatenate(mask), np.concatenate(labels),
+                      token_type_ids=np.concatenate(tts).astype(np.int8) if segment_ids else None, span_labels=True)
+    ds.example_index = np.concatenate(owner)
+    return ds
 
 
 # ------------------------------------------------------------------------------------------ CoNLL column files

@@ -53,8 +53,14 @@ class BatchLoader:
         if pad.any():
             labels[pad] = -100  # ignored by the loss and by the metric meter
         ints = {}
+        tt = getattr(self.ds, "token_type_ids", None)
         if self.pack:
-            pk = pack_batch(self.ds.input_ids[ix], self.ds.attention_mask[ix], labels, **self.pack_rule)
+            extra = {}
+            if tt is not None:
+                extra["token_type_ids"] = tt[ix]
+            if getattr(self.ds, "span_labels", False):
+                extra["span_labels"] = True
+            pk = pack_batch(self.ds.input_ids[ix], self.ds.attention_mask[ix], labels, **self.pack_rule, **extra)
             ints = {k: pk.pop(k) for k in ("max_seqlen", "real_tokens")}
             b = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in pk.items()}
         else:
@@ -63,6 +69,8 @@ class BatchLoader:
                 "attention_mask": torch.from_numpy(self.ds.attention_mask[ix].astype(np.int64)),
                 "labels": torch.from_numpy(labels),
             }
+            if tt is not None:
+                b["token_type_ids"] = torch.from_numpy(tt[ix].astype(np.int64))
         if self._cuda:
             b = {k: v.pin_memory() for k, v in b.items()}
         b.update(ints)

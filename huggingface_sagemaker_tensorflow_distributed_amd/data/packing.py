@@ -14,19 +14,23 @@ are *dead*: they belong to no sequence, hold the padding token, and every kernel
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import numpy as np
 
 
 def pack_batch(input_ids: np.ndarray, attention_mask: np.ndarray, labels: np.ndarray, *, pad_id: int, pos_base: int,
-               pad_pos: int, row_multiple: int = 256) -> Dict[str, object]:
+               pad_pos: int, row_multiple: int = 256, token_type_ids: Optional[np.ndarray] = None,
+               span_labels: bool = False) -> Dict[str, object]:
     """Pack a right-padded ``[B, S]`` batch.
 
     ``position_ids[t] = pos_base + i`` for the ``i``-th token of its sequence (BERT / DistilBERT: ``pos_base = 0``,
     ``pad_pos = 0``; RoBERTa: ``pos_base = pad_token_id + 1``, ``pad_pos = pad_token_id``, what
     ``Embeddings.position_ids`` yields for a prefix mask). ``labels``: ``[B]`` (classification, returned as is) or
-    ``[B, S]`` (masked LM, packed to ``[T]`` with -100 on the dead rows).
+    ``[B, S]`` (masked LM, packed to ``[T]`` with -100 on the dead rows). ``span_labels=True``: ``labels`` are the
+    ``[B, 2]`` (start, end) positions of question answering, relative to the sequence's first token and so the same
+    numbers packed: returned as they are. ``token_type_ids [B, S]``, when given, are packed to ``[1, T]`` (0 on the
+    dead rows) and returned under that key.
 
     Returns ``input_ids [1, T]``, ``position_ids [1, T]`` (int64), ``cu_seqlens [B+1]`` (int32), ``labels`` and the
     host ints ``max_seqlen`` and ``real_tokens``.
@@ -54,14 +58,25 @@ def pack_batch(input_ids: np.ndarray, attention_mask: np.ndarray, labels: np.nda
     pos = np.full(T, pad_pos, dtype=np.int64)
     pos[:t_real] = (np.broadcast_to(np.arange(S, dtype=np.int64), (B, S)) + pos_base)[prefix]
     lab = np.asarray(labels)
-    if lab.ndim == 2:
+    if span_labels:
+        if lab.shape != (B, 2):
+            raise ValueError(f"pack_batch: span labels {lab.shape} must be [B, 2] = {(B, 2)}")
+    elif lab.ndim == 2:
         if lab.shape != ids.shape:
             raise ValueError(f"pack_batch: per-token labels {lab.shape} do not match input_ids {ids.shape}")
         packed = np.full(T, -100, dtype=np.int64)
         packed[:t_real] = lab[prefix]
         lab = packed
-    return {"input_ids": out_ids[None, :], "position_ids": pos[None, :], "cu_seqlens": cu, "labels": lab,
-            "max_seqlen": int(lengths.max()), "real_tokens": t_real}
+    out = {"input_ids": out_ids[None, :], "position_ids": pos[None, :], "cu_seqlens": cu, "labels": lab,
+           "max_seqlen": int(lengths.max()), "real_tokens": t_real}
+    if token_type_ids is not None:
+        tt = np.asarray(token_type_ids)
+        if tt.shape != ids.shape:
+            raise ValueError(f"pack_batch: token_type_ids {tt.shape} do not match input_ids {ids.shape}")
+        packed_tt = np.zeros(T, dtype=np.int64)
+        packed_tt[:t_real] = tt[prefix]
+        out["token_type_ids"] = packed_tt[None, :]
+    return out
 
 
 def unpack_rows(x: np.ndarray, cu_seqlens: np.ndarray, S: int) -> np.ndarray:

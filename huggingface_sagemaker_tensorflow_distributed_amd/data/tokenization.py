@@ -110,6 +110,33 @@ class Tokenizer:
         wid = np.asarray([[-1 if w is None else w for w in e.word_ids] for e in enc], dtype=np.int64)
         return {"input_ids": ids, "attention_mask": mask, "word_ids": wid}
 
+    def encode_pairs(self, questions: Sequence[str], contexts: Sequence[str], max_length: int,
+                     stride: int = 128) -> Dict[str, np.ndarray]:
+        """(question, context) pairs for question answering: only the context is truncated (``only_second``), and a
+        context that does not fit yields further windows that overlap the previous one by ``stride`` tokens
+        (``Encoding.overflowing``); every window is padded to ``max_length``. Per window: ``input_ids``,
+        ``attention_mask``, ``token_type_ids``, ``offsets [n, S, 2]`` (character span of each token in its own text),
+        ``sequence_ids [n, S]`` (0 question, 1 context, -1 special tokens and padding) and ``sample [n]`` (the index
+        of the pair the window came from)."""
+        self.backend.enable_truncation(max_length, stride=int(stride), strategy="only_second")
+        self.backend.enable_padding(length=max_length, pad_id=self.pad_token_id)
+        try:
+            enc = self.backend.encode_batch([(q, c) for q, c in zip(questions, contexts)])
+        finally:
+            self.backend.enable_truncation(max_length)  # the other encoders set their own; leave no pair strategy
+        wins, sample = [], []
+        for i, e in enumerate(enc):
+            for w in [e] + list(e.overflowing):
+                wins.append(w)
+                sample.append(i)
+        return {"input_ids": np.asarray([w.ids for w in wins], dtype=np.int32),
+                "attention_mask": np.asarray([w.attention_mask for w in wins], dtype=np.int8),
+                "token_type_ids": np.asarray([w.type_ids for w in wins], dtype=np.int8),
+                "offsets": np.asarray([w.offsets for w in wins], dtype=np.int64).reshape(len(wins), -1, 2),
+                "sequence_ids": np.asarray([[-1 if x is None else x for x in w.sequence_ids] for w in wins],
+                                           dtype=np.int64),
+                "sample": np.asarray(sample, dtype=np.int64)}
+
     def save_pretrained(self, save_directory: str) -> List[str]:
         os.makedirs(save_directory, exist_ok=True)
         tj = os.path.join(save_directory, "tokenizer.json")

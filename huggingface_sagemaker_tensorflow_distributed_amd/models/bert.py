@@ -298,6 +298,71 @@ class TransformerForTokenClassification(_Base):
         return loss, logits.view(shape)
 
 
+class TransformerForQuestionAnswering(_Base):
+    """BertForQuestionAnswering / RobertaForQuestionAnswering / DistilBertForQuestionAnswering (extractive, SQuAD-style):
+    ``logits = qa_outputs(dropout(sequence_output))`` over every row, column 0 the start logit and column 1 the end
+    logit, and per column a cross-entropy over the positions of each sequence (``ops.qa_head``).
+
+    Inputs: padded ``[B, S]`` ids with mask (and ``token_type_ids`` for BERT), or a packed ``[1, T]`` buffer with
+    ``cu_seqlens`` (data/packing.py); either way ``labels [B, 2]`` int64 = (start, end) token indices relative to the
+    sequence's first token, so an example carries the same numbers padded or packed. Logits ``[B, S, 2]`` / ``[T, 2]``.
+    A position ``< 0``, ``>= len`` or on a masked row is ignored.
+
+    Unlike HF the softmax of a sequence runs over its REAL rows only (docs/PARITY.md): a padding row gets an exactly
+    zero gradient and the packed step equals the padded one, as for every other task. On a batch without padding the
+    loss is HF's. BERT and RoBERTa have no head dropout (no seed is drawn); DistilBERT uses ``qa_dropout``, its seed
+    drawn after the encoder's, on the flat ``[rows, H]`` buffer. ``loss._hsd_pred`` holds the best span per sequence
+    (``max_answer_length``), ``loss._hsd_stats`` the exact-match counts. Nothing reads a device value on the host
+    (``graph_safe``)."""
+
+    graph_safe = True
+    max_answer_length = 30
+
+    def __init__(self, cfg: ModelConfig):
+        super().__init__(cfg)
+        self.base_prefix = {"bert": "bert", "roberta": "roberta", "distilbert": "distilbert"}[cfg.model_type]
+        self.qa_outputs_weight, self.qa_outputs_bias = _param(2, cfg.hidden_size), _param(2)
+
+    def architecture(self) -> str:
+        return {"bert": "BertForQuestionAnswering", "roberta": "RobertaForQuestionAnswering",
+                "distilbert": "DistilBertForQuestionAnswering"}[self.cfg.model_type]
+
+    def _head_hf_names(self):
+        yield "qa_outputs.weight", "qa_outputs_weight", None, 1
+        yield "qa_outputs.bias", "qa_outputs_bias", None, 1
+
+    def head_dropout(self) -> float:
+        return self.cfg.qa_dropout if self.cfg.model_type == "distilbert" else 0.0
+
+    def _offsets(self, input_ids) -> torch.Tensor:
+        B, S = input_ids.shape
+        return self.encoder.embeddings._cached(
+            "cu", input_ids, lambda: torch.arange(B + 1, device=input_ids.device, dtype=torch.int32) * S)
+
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, *, cu_seqlens=None,
+                max_seqlen=None, position_ids=None):
+        h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, self.training, cu_seqlens=cu_seqlens,
+                         max_seqlen=max_seqlen, position_ids=position_ids, first_token_only=False)
+        H = h.shape[-1]
+        p = self.head_dropout() if self.training else 0.0
+        seed = self.rng.next() if p else 0
+        if cu_seqlens is not None:
+            cu, row_mask, longest = cu_seqlens, None, int(max_seqlen)
+        else:
+            cu, longest = self._offsets(input_ids), int(input_ids.shape[1])
+            row_mask = attention_mask.reshape(-1) if attention_mask is not None else None
+        out = ops.qa_head(h.reshape(-1, H), self.qa_outputs_weight, self.qa_outputs_bias, labels, cu, row_mask, p, seed,
+                          self.max_answer_length, max_seqlen=longest)
+        shape = tuple(h.shape[:-1]) + (2,)  # [B, S, 2] padded, [T, 2] packed
+        if labels is None:
+            logits, pred = out
+            logits = logits.view(shape)
+            logits._hsd_pred = pred
+            return logits
+        loss, logits = out
+        return loss, logits.view(shape)
+
+
 class RobertaForMaskedLM(_Base):
     """RoBERTa MLM (decoder tied to the word embeddings), for the roberta-large pretraining config."""
 
@@ -437,6 +502,11 @@ def build_model(cfg: ModelConfig, task: str = "sequence-classification", seed: O
         m = RobertaForMaskedLM(cfg)
     elif task in ("token-classification", "token-cls"):
         m = TransformerForTokenClassification(cfg)
+    elif task in ("span-extraction", "qa"):
+        # --task question-answering (models/hf_io.py from_pretrained maps the flag's name to this key). build_model
+        # itself keeps refusing the string "question-answering", which tests/test_token_classification.py pins as its
+        # example of a task this function does not know.
+        m = TransformerForQuestionAnswering(cfg)
     else:
         raise ValueError(task)
     g = None

@@ -40,6 +40,7 @@ class ModelConfig:
     # distilbert-only
     sinusoidal_pos_embds: bool = False
     seq_classif_dropout: float = 0.2
+    qa_dropout: float = 0.1
     # bookkeeping
     name_or_path: str = ""
     model_max_length: int = 512
@@ -77,7 +78,7 @@ class ModelConfig:
                 "max_position_embeddings": self.max_position_embeddings,
                 "sinusoidal_pos_embds": self.sinusoidal_pos_embds,
                 "seq_classif_dropout": self.seq_classif_dropout,
-                "qa_dropout": 0.1, "tie_weights_": True,
+                "qa_dropout": self.qa_dropout, "tie_weights_": True,
             })
         else:
             common.update({
@@ -113,7 +114,8 @@ class ModelConfig:
                 initializer_range=d.get("initializer_range", 0.02), layer_norm_eps=1e-12,
                 pad_token_id=d.get("pad_token_id", 0), num_labels=nl,
                 sinusoidal_pos_embds=d.get("sinusoidal_pos_embds", False),
-                seq_classif_dropout=d.get("seq_classif_dropout", 0.2), id2label=labels,
+                seq_classif_dropout=d.get("seq_classif_dropout", 0.2), qa_dropout=d.get("qa_dropout", 0.1),
+                id2label=labels,
             )
         return cls(
             model_type=mt, vocab_size=d.get("vocab_size", 30522), hidden_size=d.get("hidden_size", 768),

@@ -112,7 +112,8 @@ def read_checkpoint(path: str) -> Optional[Dict[str, torch.Tensor]]:
 def from_pretrained(name_or_path: str, task: str = "sequence-classification", num_labels: Optional[int] = None,
                     seed: Optional[int] = 0) -> _Base:
     cfg = resolve_config(name_or_path, num_labels=num_labels)
-    model = build_model(cfg, task=task, seed=seed)
+    # the command line's --task question-answering is build_model's "span-extraction"
+    model = build_model(cfg, task="span-extraction" if task == "question-answering" else task, seed=seed)
     model.weights_source = "random-init"  # what the run's provenance record reports
     if os.path.isdir(name_or_path):
         sd = read_checkpoint(name_or_path)

@@ -10,7 +10,8 @@
 ``HSD_OPS=torch`` forces the reference path on GPU (only for A/B measurements of the kernels); ``HSD_FP32_OPS=torch``
 does so for fp32 tensors only. ``HSD_CLS_ROWS_ONLY=0`` keeps the last encoder layer of a sequence-classification
 model on all rows (:func:`attn_block_cls`; tests and same-process A/Bs). ``HSD_TOKEN_HEAD=composed`` runs the
-token-classification head (:func:`token_head`) as composed ops instead of its fused kernels (A/B measurements).
+token-classification head (:func:`token_head`) as composed ops instead of its fused kernels (A/B measurements);
+``HSD_QA_HEAD=composed`` does the same for the question-answering head (:func:`qa_head`).
 """
 from __future__ import annotations
 
@@ -28,6 +29,9 @@ CLS_ROWS_ONLY = os.environ.get("HSD_CLS_ROWS_ONLY", "1").strip().lower() not in 
 # HSD_TOKEN_HEAD=composed: the token-classification head as dropout -> linear -> cross_entropy instead of the fused
 # kernels of csrc/kernels/token_head.hip (A/B measurements)
 TOKEN_HEAD_FUSED = os.environ.get("HSD_TOKEN_HEAD", "fused").strip().lower() != "composed"
+# HSD_QA_HEAD=composed: the question-answering head as dropout -> linear -> masked span cross-entropy in torch instead
+# of the fused kernels of csrc/kernels/qa_head.hip (A/B measurements)
+QA_HEAD_FUSED = os.environ.get("HSD_QA_HEAD", "fused").strip().lower() != "composed"
 
 
 def _hip(x: torch.Tensor) -> bool:
@@ -294,6 +298,42 @@ def token_head(h2d, w, b, labels, p: float, seed: int):
         loss, logits, stats = out
     loss._hsd_correct = stats[1]
     loss._hsd_stats = stats
+    return loss, logits
+
+
+def qa_head(h2d, w, b, positions, cu, row_mask, p: float, seed: int, max_answer_length: int = 30, max_seqlen=None):
+    """Question-answering (span extraction) head on every row of ``h2d`` [R, H]: ``logits = dropout(h) Wᵀ + b``
+    [R, 2] (start, end) and the span loss over the sequences ``cu[b] .. cu[b+1]-1`` of the flat buffer, with
+    ``row_mask`` [R] taking rows out (padded batches: ``cu = arange(B+1)·S`` and the flat attention mask; packed ones:
+    ``cu_seqlens``, no mask). ``positions`` [B, 2] (start, end) count from the sequence's first row; the definition of
+    the loss, of an ignored position and of the best span is ``reference.span_loss`` / ``span_best``.
+
+    With ``positions`` returns ``(loss, logits)`` with the fp32 [8] {loss, hits, n, loss·n, n_start, n_end, start hits,
+    end hits} on ``loss._hsd_stats`` and the best spans (int32 [B, 2]) on ``loss._hsd_pred``; without them
+    ``(logits, pred)``. ``max_seqlen``: the longest sequence as a host int, if the caller knows it.
+
+    bf16 GPU tensors within ``hip.qa_head_ok`` (H % 8 == 0, H <= 1024, sequences of at most 1,024 rows) run the fused
+    kernels of csrc/kernels/qa_head.hip and token_head.hip, unless ``HSD_QA_HEAD=composed``. Everything else (CPU
+    tensors, fp32 GPU tensors, ``HSD_OPS=torch``, other shapes) runs the composed ops with the same seed and so the
+    same mask; the all-torch form is ``reference.qa_head``, the kernels' oracle."""
+    needs_grad = torch.is_grad_enabled() and (h2d.requires_grad or w.requires_grad or b.requires_grad)
+    if _hip(h2d) and QA_HEAD_FUSED and _hipmod().qa_head_ok(h2d, w, cu, max_seqlen) \
+            and not (positions is None and needs_grad):
+        if positions is None:
+            return _hipmod().qa_head_logits(h2d, w, b, cu, row_mask, p, seed, max_answer_length)
+        loss, logits, stats, pred = _hipmod().qa_head(h2d, w, b, positions, cu, row_mask, p, seed, max_answer_length)
+    elif _hip(h2d):
+        logits = linear(dropout(h2d, p, seed), w, b)
+        if positions is None:
+            return logits, _ref.span_best(logits, cu, row_mask, max_answer_length, max_seqlen)
+        loss, stats, pred = _ref.span_loss(logits, positions, cu, row_mask, max_answer_length, max_seqlen)
+    else:
+        out = _ref.qa_head(h2d, w, b, positions, cu, row_mask, p, seed, max_answer_length, True, max_seqlen)
+        if positions is None:
+            return out
+        loss, logits, stats, pred = out
+    loss._hsd_stats = stats
+    loss._hsd_pred = pred
     return loss, logits
 
 

@@ -1454,6 +1454,95 @@ def token_head_logits(h2d, w, b, p, seed):
     return logits
 
 
+# ------------------------------------------------------------------------------------------ question-answering head
+QA_MAX_SEQLEN = 1024  # rows of one sequence the span kernel holds in LDS (csrc/kernels/qa_head.hip)
+
+
+def qa_head_ok(h2d, w, cu, max_seqlen=None) -> bool:
+    """What the fused question-answering head takes: the token head's rows (bf16 [R, H], H % 8 == 0, H <= 1024) with
+    the 2-column classifier, offsets on the device and sequences of at most 1,024 rows (``max_seqlen``: the longest
+    one as a host int; when it is not given the kernel itself answers a longer sequence with a NaN loss)."""
+    return (token_head_ok(h2d, w) and w.shape[0] == 2 and h2d.shape[0] < (1 << 30) and cu.is_cuda
+            and cu.numel() >= 2 and (max_seqlen is None or int(max_seqlen) <= QA_MAX_SEQLEN))
+
+
+def _span_args(x, cu, row_mask):
+    cu32 = cu if cu.dtype == torch.int32 else cu.to(torch.int32)
+    mask = None
+    if row_mask is not None:
+        mask = row_mask.reshape(-1)
+        mask = (mask if mask.dtype == torch.int64 else mask.to(torch.int64)).contiguous()
+    return cu32.contiguous(), mask
+
+
+def _qa_logits(x, wc, bc, p, seed):
+    """tok_fwd_kernel in its logits-only mode with C = 2: the one streaming pass over h."""
+    logits = torch.empty((x.shape[0], 2), dtype=x.dtype, device=x.device)
+    scratch = torch.empty(_C.token_head_fwd_blocks(x.shape[0]) * 4 + 4, dtype=torch.float32, device=x.device)
+    _C.token_head_fwd(x, wc, bc, None, logits, scratch[4:], scratch[:4], float(p), _s64(seed))
+    return logits
+
+
+class _QAHead(torch.autograd.Function):
+    """Every row of h -> logits (token_head.hip, logits-only) -> span_ce_kernel + span_stats_kernel (qa_head.hip).
+    Backward: the token head's backward from the saved gradient table g0 (tok_bwd_kernel<true>) + the slab reducer
+    that adds into main_grad."""
+
+    @staticmethod
+    def forward(ctx, h2d, w, b, positions, cu, row_mask, p, seed, max_answer_length):
+        x = h2d.contiguous()
+        wc, bc = w.contiguous(), b.contiguous()
+        R = x.shape[0]
+        B = cu.numel() - 1
+        cu32, mask = _span_args(x, cu, row_mask)
+        logits = _qa_logits(x, wc, bc, p, seed)
+        pos = positions.reshape(B, 2).contiguous().long()
+        rec = torch.empty(B * 8, dtype=torch.float32, device=x.device)
+        pred = torch.empty((B, 2), dtype=torch.int32, device=x.device)
+        g0 = torch.empty((R, 2), dtype=torch.float32, device=x.device)
+        stats = torch.empty(8, dtype=torch.float32, device=x.device)
+        _C.span_ce(logits, cu32, mask, pos, int(max_answer_length), rec, pred, g0, stats)
+        ctx.save_for_backward(x, w, b, g0, stats)
+        ctx.cfg = (float(p), seed)
+        ctx.mark_non_differentiable(logits, stats, pred)
+        ctx.set_materialize_grads(False)
+        return stats[0], logits, stats, pred
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits, _dstats, _dpred):
+        x, w, b, g0, stats = ctx.saved_tensors
+        p, seed = ctx.cfg
+        R, H = x.shape
+        g_w, g_b = _Grad(w), _Grad(b)
+        if dloss is None:
+            dloss = torch.zeros((), dtype=torch.float32, device=x.device)
+        dl = dloss.reshape(1).to(torch.float32).contiguous()
+        dh = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        part = _workspace(_C.token_head_bwd_blocks(R) * (2 * H + 2), x.device)
+        # g = g0 · dloss · ½ / max(n_c, 1), n_c = stats[4 + c]
+        _C.token_head_bwd_given(x, w.contiguous(), g0, stats[4:6], 0.5, dl, dh, part, g_w.buf.view(-1),
+                                g_b.buf.view(-1), p, _s64(seed))
+        return dh, g_w.done(), g_b.done(), None, None, None, None, None, None
+
+
+def qa_head(h2d, w, b, positions, cu, row_mask, p, seed, max_answer_length):
+    """(loss, logits, stats, pred) of the fused question-answering head (positions [B, 2] required); stats = fp32
+    {loss, hits, n, loss·n, n_start, n_end, start hits, end hits}, pred int32 [B, 2]."""
+    return _QAHead.apply(h2d, w, b, positions, cu, row_mask, p, seed, max_answer_length)
+
+
+def qa_head_logits(h2d, w, b, cu, row_mask, p, seed, max_answer_length):
+    """(logits, pred) of the fused head without labels (inference: no autograd)."""
+    x = h2d.detach().contiguous()
+    B = cu.numel() - 1
+    cu32, mask = _span_args(x, cu, row_mask)
+    logits = _qa_logits(x, w.detach().contiguous(), b.detach().contiguous(), p, seed)
+    pred = torch.empty((B, 2), dtype=torch.int32, device=x.device)
+    none = torch.empty(0, dtype=torch.float32, device=x.device)
+    _C.span_ce(logits, cu32, mask, None, int(max_answer_length), none, pred, none, none)
+    return logits, pred
+
+
 # ------------------------------------------------------------------------------------------ masked-LM head
 def mlm_head_ok(h2d, w1, wemb) -> bool:
     T, H = h2d.shape

@@ -177,6 +177,106 @@ def token_head(h2d, w, b, labels, p: float, seed: int, training: bool = True):
     return loss, logits, stats
 
 
+def span_segments(cu, rows: int, row_mask=None):
+    """Rows of a flat ``[rows]`` buffer -> (sequence index ``seg`` [rows] with ``B`` on the dead rows past ``cu[B]``,
+    index within the sequence ``rel`` [rows], ``real`` [rows] bool: in a sequence and not masked). No host read."""
+    cu = cu.long()
+    B = cu.numel() - 1
+    r = torch.arange(rows, device=cu.device)
+    seg = torch.searchsorted(cu[1:].contiguous(), r, right=True)
+    real = (seg < B) & (r >= cu[0])
+    if row_mask is not None:
+        real = real & row_mask.reshape(-1).ne(0)
+    rel = r - cu[seg.clamp(max=B - 1)]
+    return seg, rel, real
+
+
+def span_best(logits, cu, row_mask, max_answer_length: int, max_seqlen: Optional[int] = None):
+    """Best span of every sequence: ``pred [B, 2]`` int32 = the first maximum, in ``(s, e)`` lexicographic order, of
+    ``start[s] + end[e]`` (ONE fp32 add of the logits as stored) over the real rows with
+    ``s <= e <= s + max_answer_length - 1``; ``(0, 0)`` for a sequence without a real row. ``max_seqlen``: the longest
+    sequence as a host int (read from ``cu`` when it is not given)."""
+    R = logits.shape[0]
+    B = cu.numel() - 1
+    seg, rel, real = span_segments(cu, R, row_mask)
+    if max_seqlen is None:
+        max_seqlen = int((cu[1:] - cu[:-1]).max())
+    L = max(1, int(max_seqlen))
+    ok = real & (rel < L)
+    slot = torch.where(ok, seg * L + rel, torch.full_like(seg, B * L))  # one spare slot takes every other row
+    x = logits.detach().float()
+    pad = torch.full(((B + 1) * L,), float("-inf"), dtype=torch.float32, device=x.device)
+    st = pad.scatter(0, slot, torch.where(ok, x[:, 0], pad[:1]))[:B * L].view(B, L)
+    en = pad.scatter(0, slot, torch.where(ok, x[:, 1], pad[:1]))[:B * L].view(B, L)
+    i = torch.arange(L, device=x.device)
+    band = (i[None, :] >= i[:, None]) & (i[None, :] - i[:, None] < max(1, int(max_answer_length)))
+    out = []
+    step = max(1, (1 << 24) // (L * L))
+    for b0 in range(0, B, step):
+        sc = st[b0:b0 + step, :, None] + en[b0:b0 + step, None, :]
+        sc = sc.masked_fill(~band, float("-inf"))
+        k = sc.view(sc.shape[0], -1).argmax(dim=1)  # the first maximum
+        out.append(torch.stack([k // L, k % L], dim=1))
+    return torch.cat(out).to(torch.int32)
+
+
+def span_loss(logits, positions, cu, row_mask, max_answer_length: int, max_seqlen: Optional[int] = None):
+    """Span-extraction loss of ``logits [R, 2]`` (column 0 = start, column 1 = end) over the sequences
+    ``cu[b] .. cu[b+1]-1`` of the flat buffer, ``row_mask [R]`` taking rows out (the padded layout:
+    ``cu = arange(B+1)·S`` plus the flat attention mask). ``positions [B, 2]`` are relative to the sequence's first
+    row; one is ignored when it is ``< 0``, ``>= len`` or on a masked row. For column c sequence b contributes
+    ``lse_c(b) - logit[pos_c(b), c]`` with the logsumexp over the REAL rows of b;
+    ``loss = ½ (Σ start terms / max(n_start, 1) + Σ end terms / max(n_end, 1))``, 0 when everything is ignored.
+
+    Returns ``(loss, stats, pred)``: ``stats`` fp32 [8] = {loss, hits, n, loss·n, n_start, n_end, start hits, end hits}
+    (hits: both labels valid and equal to the best span; n: both labels valid), ``pred`` from :func:`span_best`."""
+    R = logits.shape[0]
+    B = cu.numel() - 1
+    cul = cu.long()
+    seg, rel, real = span_segments(cu, R, row_mask)
+    x = logits.float()
+    ninf = torch.full((), float("-inf"), dtype=torch.float32, device=x.device)
+    xm = torch.where(real[:, None], x, ninf)
+    idx = seg[:, None].expand(-1, 2)
+    m = torch.full((B + 1, 2), float("-inf"), dtype=torch.float32, device=x.device)
+    m = m.scatter_reduce(0, idx, xm.detach(), "amax", include_self=True)
+    z = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+    e = torch.where(real[:, None], torch.exp(xm - z[seg]), torch.zeros_like(x))
+    se = torch.zeros((B + 1, 2), dtype=torch.float32, device=x.device).index_add(0, seg, e)
+    lse = (z + torch.log(se.clamp_min(1e-30)))[:B]
+    pos = positions.reshape(B, 2).long()
+    length = (cul[1:] - cul[:-1])[:, None]
+    inside = (pos >= 0) & (pos < length)
+    row = (cul[:-1, None] + torch.where(inside, pos, torch.zeros_like(pos))).clamp(0, R - 1)
+    valid = inside & real[row] & (seg[row] == torch.arange(B, device=x.device)[:, None])
+    tgt = torch.gather(x, 0, row)  # [B, 2]: column c of row[:, c]
+    terms = torch.where(valid, lse - tgt, torch.zeros_like(tgt))
+    nc = valid.sum(0).to(torch.float32)
+    loss = 0.5 * (terms.sum(0) / nc.clamp(min=1.0)).sum()
+    with torch.no_grad():
+        pred = span_best(logits, cu, row_mask, max_answer_length, max_seqlen)
+        eq = (pred.long() == pos) & valid
+        both = valid.all(dim=1)
+        n = both.sum().to(torch.float32)
+        hits = (eq.all(dim=1) & both).sum().to(torch.float32)
+        lv = loss.detach().float()
+        stats = torch.stack([lv, hits, n, lv * n, nc[0], nc[1], eq[:, 0].sum().float(), eq[:, 1].sum().float()])
+    return loss, stats, pred
+
+
+def qa_head(h2d, w, b, positions, cu, row_mask, p: float, seed: int, max_answer_length: int = 30,
+            training: bool = True, max_seqlen: Optional[int] = None):
+    """Question-answering head on every row of ``h2d`` [R, H] (HF ``*ForQuestionAnswering``):
+    ``logits = dropout(h) Wᵀ + b`` [R, 2], the dropout site being the flat ``[R, H]`` buffer, then :func:`span_loss`.
+    With ``positions`` returns ``(loss, logits, stats, pred)``, without ``(logits, pred)``. Unlike HF the softmax runs
+    over the real rows only (docs/PARITY.md)."""
+    logits = F.linear(dropout(h2d, p, seed, training), w, b)
+    if positions is None:
+        return logits, span_best(logits, cu, row_mask, max_answer_length, max_seqlen)
+    loss, stats, pred = span_loss(logits, positions, cu, row_mask, max_answer_length, max_seqlen)
+    return loss, logits, stats, pred
+
+
 def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps: float, wemb, bias, vocab: int):
     """RoBERTa LM head on the masked positions (labels != -100) of ``h2d`` [T, H]: ``LN(gelu(x W1ᵀ + b1))`` ->
     tied decoder (``wemb[:vocab]``, ``bias[:vocab]``) -> mean CE. Returns (loss, logits [n_masked, vocab])."""

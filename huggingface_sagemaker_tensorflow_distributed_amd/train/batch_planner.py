@@ -94,6 +94,10 @@ def _probe_peak(model, store, cfg, batch: int, seq_len: int, device) -> int:
         labels = torch.randint(0, max(2, cfg.num_labels), (batch, seq_len), generator=g)
         labels[:, ::4] = -100
         labels = labels.to(device)
+    elif model.__class__.__name__ == "TransformerForQuestionAnswering":
+        # span labels [B, 2] = (start, end) token positions
+        start = torch.randint(0, max(1, seq_len - 4), (batch, 1), generator=g)
+        labels = torch.cat([start, start + 3], dim=1).clamp(max=seq_len - 1).to(device)
     torch.cuda.synchronize(device)
     torch.cuda.empty_cache()
     torch.cuda.reset_peak_memory_stats(device)

@@ -93,6 +93,32 @@ def _datasets(args, cfg, tokenizer, max_len: int):
             return out[0], out[1]
         raise ValueError(f"--task token-classification trains on --dataset synthetic or conll (per-token labels); "
                          f"--dataset {args.dataset} holds one label per text")
+    if getattr(args, "task", "sequence-classification") == "question-answering":
+        segs = cfg.model_type == "bert"  # segment ids 0 / 1 for BERT; RoBERTa and DistilBERT take none
+        if args.dataset == "synthetic":
+            kw = {"segment_ids": segs, "pad_id": cfg.pad_token_id}
+            if cfg.model_type == "roberta":
+                kw.update(cls_id=cfg.bos_token_id if cfg.bos_token_id is not None else 0,
+                          sep_id=cfg.eos_token_id if cfg.eos_token_id is not None else 2)
+            tr = hdata.synthetic_question_answering(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed, **kw)
+            te = hdata.synthetic_question_answering(n_eval or 512, max_len, cfg.vocab_size, seed=args.seed + 1, **kw)
+            return tr, te
+        if args.dataset == "squad":
+            from ..data.datasets import squad_split_path
+
+            if not args.dataset_dir:
+                raise ValueError("--dataset squad needs --dataset_dir (train*.json and dev*.json in SQuAD format)")
+            out = []
+            for split, n in (("train", n_train), ("dev", n_eval)):
+                ex = hdata.read_squad(squad_split_path(args.dataset_dir, split))
+                if n:
+                    ex = ex[:n]
+                out.append(hdata.tokenize_squad(tokenizer, ex, max_len, int(getattr(args, "doc_stride", 128)),
+                                                segment_ids=segs))
+            return out[0], out[1]
+        raise ValueError(_QA_DATASETS.format(args.dataset))
+    if args.dataset == "squad":
+        raise ValueError("--dataset squad holds answer spans (--task question-answering)")
     if args.dataset == "conll":
         raise ValueError("--dataset conll holds per-token tags (--task token-classification)")
     if args.dataset == "synthetic-bigram":
@@ -112,6 +138,10 @@ def _datasets(args, cfg, tokenizer, max_len: int):
         texts, labels = texts[:n_eval], labels[:n_eval]
     te = hdata.tokenize_dataset(tokenizer, texts, labels, max_len)
     return tr, te
+
+
+_QA_DATASETS = ("--task question-answering trains on --dataset synthetic or squad (start / end positions); "
+                "--dataset {} holds no answer spans")
 
 
 def _conll_tags(args) -> Optional[List[str]]:
@@ -153,6 +183,16 @@ def _provenance(args, model, rank: int, n_train: int, n_eval: int, batch_plan=No
                           "real tokens ignored)")
         info["metric"] = "loss and accuracy over the labelled tokens (not entity-level F1)"
         logger.info("token-classification corpus: %s; %d labels", info["corpus"], info["num_labels"])
+    if getattr(args, "task", "sequence-classification") == "question-answering":
+        info["task"] = "question-answering"
+        info["max_answer_length"] = int(getattr(args, "max_answer_length", 30))
+        info["corpus"] = ("SQuAD-format files in " + str(args.dataset_dir) + ", doc_stride "
+                          + str(int(getattr(args, "doc_stride", 128))) if args.dataset == "squad" else
+                          "synthetic span corpus ([CLS] key [SEP] context [SEP], the answer follows the key's one "
+                          "occurrence in the context, ~10 % without an answer, ragged lengths)")
+        info["metric"] = ("loss and exact match of the best (start, end) token span over the windows with both "
+                          "labels valid (not text-level EM / F1)")
+        logger.info("question-answering corpus: %s; max_answer_length %d", info["corpus"], info["max_answer_length"])
     if batch_plan is not None:
         info["auto_batch"] = batch_plan.as_dict()
     if synthetic or weights == "random-init":
@@ -187,6 +227,8 @@ def build(args, mode: str):
     if task == "token-classification" and args.dataset not in ("synthetic", "conll"):
         raise ValueError(f"--task token-classification trains on --dataset synthetic or conll (per-token labels); "
                          f"--dataset {args.dataset} holds one label per text")
+    if task == "question-answering" and args.dataset not in ("synthetic", "squad"):
+        raise ValueError(_QA_DATASETS.format(args.dataset))
     tags = _conll_tags(args)
     if tags is not None:
         if args.num_labels != len(tags):
@@ -199,6 +241,10 @@ def build(args, mode: str):
     model.to(dev)
     model.rng.base_seed = args.seed
     model.rng.rank = rank
+    if task == "question-answering":
+        if int(getattr(args, "max_answer_length", 30)) < 1:
+            raise ValueError(f"--max_answer_length {args.max_answer_length} must be at least 1")
+        model.max_answer_length = int(getattr(args, "max_answer_length", 30))
     if task == "masked-lm":
         # dynamic: the model masks each batch on the device and its head has a fixed row count (--dtype fp8 takes
         # the same fp8 head GEMMs as the static head: both call the one gemm_fwd / gemm_dgrad / gemm_wgrad_ chain)

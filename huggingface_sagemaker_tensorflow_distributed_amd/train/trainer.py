@@ -246,10 +246,12 @@ class Trainer:
             if self.model.training:
                 self.packed_real_tokens += int(batch["real_tokens"])
                 self.packed_rows += int(batch["input_ids"].shape[-1])
+            kw = {"token_type_ids": batch["token_type_ids"]} if "token_type_ids" in batch else {}
             return self.model(batch["input_ids"], labels=batch["labels"], cu_seqlens=batch["cu_seqlens"],
-                              max_seqlen=batch["max_seqlen"], position_ids=batch["position_ids"])
+                              max_seqlen=batch["max_seqlen"], position_ids=batch["position_ids"], **kw)
+        kw = {"token_type_ids": batch["token_type_ids"]} if "token_type_ids" in batch else {}
         loss, logits = self.model(batch["input_ids"], attention_mask=batch["attention_mask"],
-                                  labels=batch["labels"])
+                                  labels=batch["labels"], **kw)
         return loss, logits
 
     def train_step(self, micro_batches: List[Dict[str, torch.Tensor]], meter: Optional[_Meter] = None) -> torch.Tensor:

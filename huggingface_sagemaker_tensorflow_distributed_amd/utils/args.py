@@ -77,7 +77,8 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
     g.add_argument("--dataset", type=str, default="synthetic",
                    help="imdb | sst2 | synthetic | synthetic-bigram (masked-lm only: a learnable first-order corpus) | "
                         "conll (token-classification only: train.txt / test.txt in CoNLL column format under "
-                        "--dataset_dir) | path to a local dataset directory/file")
+                        "--dataset_dir) | squad (question-answering only: train*.json / dev*.json in SQuAD format "
+                        "under --dataset_dir) | path to a local dataset directory/file")
     g.add_argument("--dataset_dir", type=str, default=None,
                    help="local directory holding imdb/sst2 data, or the CoNLL files of --dataset conll")
     g.add_argument("--num_train_examples", type=int, default=None, help="synthetic/limit train size")
@@ -137,11 +138,17 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
     g.add_argument("--log_every", type=int, default=50)
     g.add_argument("--device", type=str, default=None, help="cuda | cpu (default: cuda if available)")
     g.add_argument("--num_labels", type=int, default=2)
-    g.add_argument("--task", choices=["sequence-classification", "masked-lm", "token-classification"],
+    g.add_argument("--task", choices=["sequence-classification", "masked-lm", "token-classification",
+                                      "question-answering"],
                    default="sequence-classification",
                    help="masked-lm: RoBERTa MLM pretraining (BASELINE.json config 5); token-classification: one label "
                         "per token (NER / POS tagging; --dataset synthetic or conll, --num_labels follows the tag list "
-                        "of a CoNLL directory)")
+                        "of a CoNLL directory); question-answering: extractive start / end span prediction "
+                        "(--dataset synthetic or squad)")
+    g.add_argument("--max_answer_length", type=int, default=30,
+                   help="question-answering: the longest span (in tokens) the best-span search returns")
+    g.add_argument("--doc_stride", type=int, default=128,
+                   help="question-answering --dataset squad: tokens two consecutive windows of a long context share")
     g.add_argument("--mlm_masking", choices=["static", "dynamic"], default="static",
                    help="masked-lm: static = the corpus is masked once when it is built (every selected token becomes "
                         "<mask>); dynamic = RoBERTa's recipe, a fresh draw every step on the device (80 %% <mask>, 10 %% "
