@@ -1119,6 +1119,26 @@ void xent(torch::Tensor logits, torch::Tensor labels, c10::optional<torch::Tenso
                    n_valid.data_ptr<float>(), (int)logits.size(0), (int)V, ld, cur_stream());
 }
 
+// ---- argument checks shared by the fused task heads (cls_head.hip, token_head.hip, qa_head.hip)
+// contiguous bf16 [rows][cols]
+static void check_bf16_2d(const torch::Tensor& t, int64_t rows, int64_t cols, const char* what) {
+  TORCH_CHECK(t.is_contiguous() && t.dim() == 2 && t.size(0) == rows && t.size(1) == cols &&
+              t.scalar_type() == torch::kBFloat16, what);
+}
+// contiguous bf16 vector of n elements
+static void check_bf16_vec(const torch::Tensor& t, int64_t n, const char* what) {
+  TORCH_CHECK(t.is_contiguous() && t.numel() == n && t.scalar_type() == torch::kBFloat16, what);
+}
+// labels int64 [R]
+static const int64_t* head_labels(const torch::Tensor& labels, int64_t R) {
+  TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.is_contiguous() && labels.numel() == R, "labels");
+  return labels.data_ptr<int64_t>();
+}
+// ... or none (logits only)
+static const int64_t* head_labels(const c10::optional<torch::Tensor>& labels, int64_t R) {
+  return labels.has_value() ? head_labels(*labels, R) : nullptr;
+}
+
 // fused classification head (cls_head.hip). pre [R][H] bf16 (row stride ld), W2 [C][H], b2 [C] bf16, labels int64 [R]
 // (or none: logits only); t_out [R][H], logits [R][C] bf16; partials fp32 [cls_head_blocks(R)][4]; stats fp32 [4]
 void cls_head_fwd(torch::Tensor pre, torch::Tensor W2, torch::Tensor b2, c10::optional<torch::Tensor> labels,
@@ -1128,19 +1148,14 @@ void cls_head_fwd(torch::Tensor pre, torch::Tensor W2, torch::Tensor b2, c10::op
               pre.scalar_type() == torch::kBFloat16, "cls_head pre");
   const int64_t R = pre.size(0), H = pre.size(1), C = W2.size(0);
   TORCH_CHECK(H % 8 == 0 && H <= 1024 && C >= 1 && C <= 4, "cls_head: H % 8 == 0, H <= 1024, 1 <= classes <= 4");
-  TORCH_CHECK(W2.is_contiguous() && W2.size(1) == H && W2.scalar_type() == torch::kBFloat16, "cls_head W2");
-  TORCH_CHECK(b2.is_contiguous() && b2.numel() == C && b2.scalar_type() == torch::kBFloat16, "cls_head b2");
-  TORCH_CHECK(t_out.is_contiguous() && t_out.sizes() == pre.sizes() && t_out.scalar_type() == torch::kBFloat16, "cls t");
-  TORCH_CHECK(logits.is_contiguous() && logits.size(0) == R && logits.size(1) == C &&
-              logits.scalar_type() == torch::kBFloat16, "cls_head logits");
+  check_bf16_2d(W2, C, H, "cls_head W2");
+  check_bf16_vec(b2, C, "cls_head b2");
+  check_bf16_2d(t_out, R, H, "cls t");
+  check_bf16_2d(logits, R, C, "cls_head logits");
   check_f32(partials, "partials");
   check_f32(stats, "stats");
   TORCH_CHECK(partials.numel() >= 4 * (int64_t)hsd::cls_head_blocks((int)R) && stats.numel() >= 4, "cls_head stats");
-  const int64_t* lab = nullptr;
-  if (labels.has_value()) {
-    TORCH_CHECK(labels->scalar_type() == torch::kInt64 && labels->is_contiguous() && labels->numel() == R, "labels");
-    lab = labels->data_ptr<int64_t>();
-  }
+  const int64_t* lab = head_labels(labels, R);
   TORCH_CHECK(act == 0 || act == 1, "cls_head act: 0 tanh, 1 relu");
   hsd::launch_cls_head_fwd(CBF(pre), pre.stride(0), CBF(W2), CBF(b2), lab, BF(t_out), BF(logits),
                            partials.data_ptr<float>(), stats.data_ptr<float>(), (int)R, (int)H, (int)C, (int)act, p,
@@ -1153,19 +1168,18 @@ void cls_head_bwd(torch::Tensor t, torch::Tensor W2, torch::Tensor logits, torch
   TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.is_contiguous() && t.scalar_type() == torch::kBFloat16, "cls t");
   const int64_t R = t.size(0), H = t.size(1), C = W2.size(0);
   TORCH_CHECK(H % 8 == 0 && H <= 1024 && C >= 1 && C <= 4, "cls_head shape");
-  TORCH_CHECK(W2.is_contiguous() && W2.size(1) == H && W2.scalar_type() == torch::kBFloat16, "cls_head W2");
-  TORCH_CHECK(logits.is_contiguous() && logits.size(0) == R && logits.size(1) == C &&
-              logits.scalar_type() == torch::kBFloat16, "cls_head logits");
-  TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.is_contiguous() && labels.numel() == R, "labels");
+  check_bf16_2d(W2, C, H, "cls_head W2");
+  check_bf16_2d(logits, R, C, "cls_head logits");
+  const int64_t* lab = head_labels(labels, R);
   check_f32(stats, "stats");
   check_f32(dloss, "dloss");
-  TORCH_CHECK(dpre.is_contiguous() && dpre.sizes() == t.sizes() && dpre.scalar_type() == torch::kBFloat16, "dpre");
+  check_bf16_2d(dpre, R, H, "dpre");
   check_f32(dW2, "dW2");
   check_f32(db2, "db2");
   TORCH_CHECK(dW2.numel() == C * H && db2.numel() == C, "cls_head grads");
-  hsd::launch_cls_head_bwd(CBF(t), CBF(W2), CBF(logits), labels.data_ptr<int64_t>(), stats.data_ptr<float>(),
-                           dloss.data_ptr<float>(), BF(dpre), dW2.data_ptr<float>(), db2.data_ptr<float>(), (int)R,
-                           (int)H, (int)C, (int)act, p, (uint64_t)seed, cur_stream());
+  hsd::launch_cls_head_bwd(CBF(t), CBF(W2), CBF(logits), lab, stats.data_ptr<float>(), dloss.data_ptr<float>(),
+                           BF(dpre), dW2.data_ptr<float>(), db2.data_ptr<float>(), (int)R, (int)H, (int)C, (int)act, p,
+                           (uint64_t)seed, cur_stream());
 }
 
 // C [N][K] fp32 += dy [T][N]ᵀ · x [T][K] for small T (row strides allowed; unit inner strides)
@@ -1263,59 +1277,61 @@ int64_t cls_head_blocks(int64_t R) { return hsd::cls_head_blocks((int)R); }
 // fused token-classification head (token_head.hip). h [R][H] bf16 contiguous, W [C][H], b [C] bf16, labels int64 [R]
 // (or none: logits only, stats untouched); logits [R][C] bf16; partials fp32 [token_head_fwd_blocks(R)][4]; stats
 // fp32 [4]
-static void token_head_check(const torch::Tensor& h, const torch::Tensor& W, const torch::Tensor& logits) {
+static void token_head_check(const torch::Tensor& h, const torch::Tensor& W) {
   TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() && h.scalar_type() == torch::kBFloat16, "token_head h");
   const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
   TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 16 && H % 8 == 0 && H >= 8 && H <= 1024 && C >= 2 && C <= 16,
               "token_head: 1 <= rows < 2^31, H % 8 == 0, H <= 1024, 2 <= classes <= 16");
-  TORCH_CHECK(W.is_contiguous() && W.dim() == 2 && W.size(1) == H && W.scalar_type() == torch::kBFloat16,
-              "token_head W");
-  TORCH_CHECK(logits.is_contiguous() && logits.dim() == 2 && logits.size(0) == R && logits.size(1) == C &&
-              logits.scalar_type() == torch::kBFloat16, "token_head logits");
+  check_bf16_2d(W, C, H, "token_head W");
+}
+static void token_head_check(const torch::Tensor& h, const torch::Tensor& W, const torch::Tensor& logits) {
+  token_head_check(h, W);
+  check_bf16_2d(logits, h.size(0), W.size(0), "token_head logits");
 }
 
 void token_head_fwd(torch::Tensor h, torch::Tensor W, torch::Tensor b, c10::optional<torch::Tensor> labels,
                     torch::Tensor logits, torch::Tensor partials, torch::Tensor stats, double p, int64_t seed) {
   token_head_check(h, W, logits);
   const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
-  TORCH_CHECK(b.is_contiguous() && b.numel() == C && b.scalar_type() == torch::kBFloat16, "token_head b");
+  check_bf16_vec(b, C, "token_head b");
   check_f32(partials, "partials");
   check_f32(stats, "stats");
   TORCH_CHECK(partials.numel() >= 4 * (int64_t)hsd::token_head_fwd_blocks((int)R) && stats.numel() >= 4,
               "token_head stats");
-  const int64_t* lab = nullptr;
-  if (labels.has_value()) {
-    TORCH_CHECK(labels->scalar_type() == torch::kInt64 && labels->is_contiguous() && labels->numel() == R, "labels");
-    lab = labels->data_ptr<int64_t>();
-  }
-  hsd::launch_token_head_fwd(CBF(h), CBF(W), CBF(b), lab, BF(logits), partials.data_ptr<float>(),
+  hsd::launch_token_head_fwd(CBF(h), CBF(W), CBF(b), head_labels(labels, R), BF(logits), partials.data_ptr<float>(),
                              stats.data_ptr<float>(), (int)R, (int)H, (int)C, p, (uint64_t)seed, cur_stream());
 }
 
-// dh [R][H] bf16 (or none: parameter gradients only); part fp32, >= token_head_bwd_blocks(R) · (C·H + C) elements;
-// dW fp32 [C·H] and db fp32 [C] are ADDED to
+// the outputs both backward entries share. dh [R][H] bf16 (or none: parameter gradients only; returns null); part
+// fp32, >= token_head_bwd_blocks(R) · (C·H + C) elements; dW fp32 [C·H] and db fp32 [C] are ADDED to
+static hsd::bf16_t* token_head_bwd_check(const torch::Tensor& h, const torch::Tensor& W, const torch::Tensor& dloss,
+                                         const c10::optional<torch::Tensor>& dh, const torch::Tensor& part,
+                                         const torch::Tensor& dW, const torch::Tensor& db) {
+  const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
+  check_f32(dloss, "dloss");
+  check_f32(part, "part");
+  check_f32(dW, "dW");
+  check_f32(db, "db");
+  TORCH_CHECK(dloss.numel() >= 1, "token_head dloss");
+  TORCH_CHECK(part.numel() >= (int64_t)hsd::token_head_bwd_blocks((int)R) * (C * H + C), "token_head workspace");
+  TORCH_CHECK(dW.numel() == C * H && db.numel() == C, "token_head grads");
+  if (!dh.has_value()) return nullptr;
+  check_bf16_2d(*dh, R, H, "dh");
+  return BF(*dh);
+}
+
 void token_head_bwd(torch::Tensor h, torch::Tensor W, torch::Tensor logits, torch::Tensor labels, torch::Tensor stats,
                     torch::Tensor dloss, c10::optional<torch::Tensor> dh, torch::Tensor part, torch::Tensor dW,
                     torch::Tensor db, double p, int64_t seed) {
   token_head_check(h, W, logits);
   const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
-  TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.is_contiguous() && labels.numel() == R, "labels");
+  const int64_t* lab = head_labels(labels, R);
   check_f32(stats, "stats");
-  check_f32(dloss, "dloss");
-  check_f32(part, "part");
-  check_f32(dW, "dW");
-  check_f32(db, "db");
-  TORCH_CHECK(stats.numel() >= 4 && dloss.numel() >= 1, "token_head stats / dloss");
-  TORCH_CHECK(part.numel() >= (int64_t)hsd::token_head_bwd_blocks((int)R) * (C * H + C), "token_head workspace");
-  TORCH_CHECK(dW.numel() == C * H && db.numel() == C, "token_head grads");
-  hsd::bf16_t* dhp = nullptr;
-  if (dh.has_value()) {
-    TORCH_CHECK(dh->is_contiguous() && dh->sizes() == h.sizes() && dh->scalar_type() == torch::kBFloat16, "dh");
-    dhp = BF(*dh);
-  }
-  hsd::launch_token_head_bwd(CBF(h), CBF(W), CBF(logits), labels.data_ptr<int64_t>(), stats.data_ptr<float>(),
-                             dloss.data_ptr<float>(), dhp, part.data_ptr<float>(), dW.data_ptr<float>(),
-                             db.data_ptr<float>(), (int)R, (int)H, (int)C, p, (uint64_t)seed, cur_stream());
+  TORCH_CHECK(stats.numel() >= 4, "token_head stats");
+  hsd::bf16_t* dhp = token_head_bwd_check(h, W, dloss, dh, part, dW, db);
+  hsd::launch_token_head_bwd(CBF(h), CBF(W), CBF(logits), lab, stats.data_ptr<float>(), dloss.data_ptr<float>(), dhp,
+                             part.data_ptr<float>(), dW.data_ptr<float>(), db.data_ptr<float>(), (int)R, (int)H,
+                             (int)C, p, (uint64_t)seed, cur_stream());
 }
 
 // the token head's backward from a given gradient table (question-answering: qa_head.hip). g0 fp32 [R][C]; cnt fp32,
@@ -1323,26 +1339,12 @@ void token_head_bwd(torch::Tensor h, torch::Tensor W, torch::Tensor logits, torc
 void token_head_bwd_given(torch::Tensor h, torch::Tensor W, torch::Tensor g0, torch::Tensor cnt, double gmul,
                           torch::Tensor dloss, c10::optional<torch::Tensor> dh, torch::Tensor part, torch::Tensor dW,
                           torch::Tensor db, double p, int64_t seed) {
-  TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() && h.scalar_type() == torch::kBFloat16, "token_head h");
+  token_head_check(h, W);
   const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
-  TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 16 && H % 8 == 0 && H >= 8 && H <= 1024 && C >= 2 && C <= 16,
-              "token_head: 1 <= rows < 2^31, H % 8 == 0, H <= 1024, 2 <= classes <= 16");
-  TORCH_CHECK(W.is_contiguous() && W.dim() == 2 && W.size(1) == H && W.scalar_type() == torch::kBFloat16,
-              "token_head W");
   check_f32(g0, "g0");
   check_f32(cnt, "cnt");
-  check_f32(dloss, "dloss");
-  check_f32(part, "part");
-  check_f32(dW, "dW");
-  check_f32(db, "db");
-  TORCH_CHECK(g0.numel() == R * C && cnt.numel() >= C && dloss.numel() >= 1, "token_head g0 / cnt / dloss");
-  TORCH_CHECK(part.numel() >= (int64_t)hsd::token_head_bwd_blocks((int)R) * (C * H + C), "token_head workspace");
-  TORCH_CHECK(dW.numel() == C * H && db.numel() == C, "token_head grads");
-  hsd::bf16_t* dhp = nullptr;
-  if (dh.has_value()) {
-    TORCH_CHECK(dh->is_contiguous() && dh->sizes() == h.sizes() && dh->scalar_type() == torch::kBFloat16, "dh");
-    dhp = BF(*dh);
-  }
+  TORCH_CHECK(g0.numel() == R * C && cnt.numel() >= C, "token_head g0 / cnt");
+  hsd::bf16_t* dhp = token_head_bwd_check(h, W, dloss, dh, part, dW, db);
   hsd::launch_token_head_bwd_given(CBF(h), CBF(W), g0.data_ptr<float>(), cnt.data_ptr<float>(), (float)gmul,
                                    dloss.data_ptr<float>(), dhp, part.data_ptr<float>(), dW.data_ptr<float>(),
                                    db.data_ptr<float>(), (int)R, (int)H, (int)C, p, (uint64_t)seed, cur_stream());

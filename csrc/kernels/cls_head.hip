@@ -15,49 +15,27 @@
 //                                                                  per 16-row block)
 //
 // One wave per row; lanes own 8-element (16-B) chunks of the row, chunk c = lane + 64·i. Block = 4 waves x 4 rows.
-// The forward writes per-block partial sums {loss, correct, n_valid}; cls_stats_kernel (one block) reduces them
-// into stats = {mean loss, correct, n_valid, loss sum} — no memset, no atomics, deterministic.
-#include "common.h"
+// The forward writes per-block partial sums {loss, correct, n_valid}; head_stats_kernel (head_stats.hip, one block)
+// reduces them into stats = {mean loss, correct, n_valid, loss sum} — no memset, no atomics, deterministic.
+#include "head_common.h"
 #include "launchers.h"
 
 namespace hsd {
 namespace cls {
+
+using head::keep8;
+using head::pack8;
+using head::unpack8;
 
 constexpr int ROWS_PER_WAVE = 4;
 constexpr int ROWS_PER_BLOCK = 4 * ROWS_PER_WAVE;
 constexpr int MAXC = 4;
 constexpr int MAX_CHUNKS = 2;  // H <= 1024 (8 elements x 64 lanes x 2)
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ float act_fwd(float x, int act) { return act == 0 ? tanhf(x) : fmaxf(x, 0.0f); }
 
 // act'(.) from the stored activation t: tanh' = 1 - t², relu' = [t > 0]
 __device__ __forceinline__ float act_bwd(float t, int act) { return act == 0 ? 1.0f - t * t : (t > 0.0f ? 1.0f : 0.0f); }
-
-__device__ __forceinline__ void unpack8(const u32x4& w, float (&v)[8]) {
-  v[0] = lo_bf(w.x); v[1] = hi_bf(w.x); v[2] = lo_bf(w.y); v[3] = hi_bf(w.y);
-  v[4] = lo_bf(w.z); v[5] = hi_bf(w.z); v[6] = lo_bf(w.w); v[7] = hi_bf(w.w);
-}
-
-__device__ __forceinline__ u32x4 pack8(const float (&v)[8]) {
-  return u32x4{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
-}
-
-// keep factors of the 8 elements from column h0 (h0 % 8 == 0) of row `row` ([R][H] site, mask rows of width H)
-__device__ __forceinline__ void keep8(int row, int h0, const DropoutParams& dp, float (&kf)[8]) {
-  const uint32_t x = dropout_row((uint32_t)row, dp) ^ drop_col((uint32_t)h0 >> 1);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {  // (h0 / 2) % 4 == 0: pair h0 / 2 + j = h0 / 2 ^ j
-    const uint32_t b = drop_fin(x ^ drop_col((uint32_t)j));
-    kf[2 * j] = keep_factor(b, 0, dp);
-    kf[2 * j + 1] = keep_factor(b, 1, dp);
-  }
-}
 
 template <int C>
 __global__ __launch_bounds__(256) void cls_fwd_kernel(const bf16_t* __restrict__ pre, int64_t ld_pre,
@@ -88,7 +66,7 @@ __global__ __launch_bounds__(256) void cls_fwd_kernel(const bf16_t* __restrict__
       *reinterpret_cast<u32x4*>(t_out + (int64_t)row * H + h0) = pack8(v);
       if (dp.enabled) {  // bf16(t · keep · scale)
         float kf[8];
-        keep8(row, h0, dp, kf);
+        keep8(dropout_row((uint32_t)row, dp), h0, dp, kf);
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = bf2f(f2bf(v[k] * kf[k]));
       }
@@ -131,34 +109,6 @@ __global__ __launch_bounds__(256) void cls_fwd_kernel(const bf16_t* __restrict__
   if (threadIdx.x < 3) {
     const int k = threadIdx.x;
     partials[(int64_t)blockIdx.x * 4 + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-  }
-}
-
-// stats = {loss_sum / max(n_valid, 1), correct, n_valid, loss_sum}
-__global__ __launch_bounds__(256) void cls_stats_kernel(const float* __restrict__ partials, int nblk,
-                                                        float* __restrict__ stats) {
-  __shared__ float red[4][3];
-  float s[3] = {0.f, 0.f, 0.f};
-  for (int b = threadIdx.x; b < nblk; b += blockDim.x) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s[k] += partials[(int64_t)b * 4 + k];
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) s[k] = wave_sum(s[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) red[wave][k] = s[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-    stats[0] = t[0] / fmaxf(t[2], 1.0f);
-    stats[1] = t[1];
-    stats[2] = t[2];
-    stats[3] = t[0];
   }
 }
 
@@ -228,7 +178,7 @@ __global__ __launch_bounds__(256) void cls_bwd_kernel(const bf16_t* __restrict__
         for (int k = 0; k < 8; ++k) dd[k] = fmaf(g[c], w[k], dd[k]);
       }
       float o[8], kf[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
-      if (dp.enabled) keep8(row, h0, dp, kf);
+      if (dp.enabled) keep8(dropout_row((uint32_t)row, dp), h0, dp, kf);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float keep = kf[k];
@@ -276,8 +226,7 @@ void launch_cls_head_fwd(const bf16_t* pre, int64_t ld_pre, const bf16_t* W2, co
   }
 #undef CLS_F
   HSD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(cls::cls_stats_kernel, dim3(1), dim3(256), 0, st, (const float*)partials, nblk, stats);
-  HSD_CHECK_LAUNCH();
+  launch_head_stats(partials, nblk, stats, st);
 }
 
 void launch_cls_head_bwd(const bf16_t* t_in, const bf16_t* W2, const bf16_t* logits, const int64_t* labels,

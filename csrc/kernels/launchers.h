@@ -119,6 +119,9 @@ void launch_mlm_scatter_rows(const bf16_t* dx, const int* inv, bf16_t* dh, int64
 void launch_wire_cast(const void* src, void* dst, int64_t n, bool to16, bool half, float scale, hipStream_t st);
 // desc: int64 [n][5] = {src, dst, rows, cols, first_tile}; rows, cols multiples of 4
 void launch_transpose_many(const int64_t* desc, int n, int total_tiles, hipStream_t st);
+// head_stats.hip: partials fp32 [nblk][4] = per-block {loss sum, hits, n_valid} of a classification head's forward ->
+// stats fp32 [4] = {mean loss, hits, n_valid, loss sum} (one workgroup)
+void launch_head_stats(const float* partials, int nblk, float* stats, hipStream_t st);
 // cls_head.hip: fused sequence-classification head after the dense GEMM (act, dropout, classifier, CE, accuracy)
 int cls_head_blocks(int R);
 void launch_cls_head_fwd(const bf16_t* pre, int64_t ld_pre, const bf16_t* W2, const bf16_t* b2, const int64_t* labels,

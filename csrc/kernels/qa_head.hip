@@ -39,8 +39,7 @@ constexpr int MAXL = 1024;  // rows of one sequence held in LDS
 
 // max / sum over the 256 threads of the workgroup; red holds one float per wave. Every thread gets the result.
 __device__ __forceinline__ float block_max(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  v = wave_max(v);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -49,8 +48,7 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 }
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   v = (red[0] + red[1]) + (red[2] + red[3]);

@@ -7,7 +7,8 @@
 //   forward   d       = bf16(h · keep · 1/(1-p))      the hash dropout of ops/rng.py, element (row, col) of [R, H]
 //             logits  = bf16(d·Wᵀ + b)                [R, C], 2 <= C <= 16
 //             per valid row: logsumexp(logits) - logits[label], first-maximum argmax hit (from the rounded logits)
-//             per-block partial sums -> tok_stats_kernel -> stats = {mean loss, hits, n_valid, loss sum}
+//             per-block partial sums -> head_stats_kernel (head_stats.hip) -> stats = {mean loss, hits, n_valid,
+//             loss sum}
 //   backward  g       = (softmax(logits) - onehot(label)) · dloss / max(n_valid, 1)      0 on ignored rows
 //             dh      = bf16((g·W) · keep · 1/(1-p))   every row written once, 16-byte stores
 //             dW, db  : per-block fp32 partial slabs [C][H] + [C] -> tok_reduce_kernel adds them in a fixed order
@@ -45,8 +46,8 @@
 //   tok_fwd_kernel     152 VGPRs + 4 AGPRs, scratch 0, occupancy 3 waves / SIMD, LDS 33,072 B
 //   tok_bwd_kernel     233 VGPRs,           scratch 0, occupancy 2 waves / SIMD, LDS 48,640 B
 //   tok_bwd_kernel<true> (the given-gradient entry of qa_head.hip): 235 VGPRs, scratch 0, LDS 48,640 B
-//   tok_stats_kernel    14 VGPRs,           scratch 0;  tok_reduce_kernel 12 VGPRs, scratch 0
-#include "common.h"
+//   tok_reduce_kernel   12 VGPRs,           scratch 0
+#include "head_common.h"
 #include "launchers.h"
 
 namespace hsd {
@@ -65,32 +66,9 @@ constexpr int BWD_SLICES = MAXH / 32 / 4;  // 32-column slices per wave
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ void unpack8(const u32x4& w, float (&v)[8]) {
-  v[0] = lo_bf(w.x); v[1] = hi_bf(w.x); v[2] = lo_bf(w.y); v[3] = hi_bf(w.y);
-  v[4] = lo_bf(w.z); v[5] = hi_bf(w.z); v[6] = lo_bf(w.w); v[7] = hi_bf(w.w);
-}
-
-__device__ __forceinline__ u32x4 pack8(const float (&v)[8]) {
-  return u32x4{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
-}
-
-// keep factors (0 or 1/(1-p)) of the 8 elements from column h0 (h0 % 8 == 0) of the row whose row word is rw:
-// cls_head.hip keep8 with the row hash hoisted (one per lane and tile)
-__device__ __forceinline__ void keep8(uint32_t rw, int h0, const DropoutParams& dp, float (&kf)[8]) {
-  const uint32_t x = rw ^ drop_col((uint32_t)h0 >> 1);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {  // (h0 / 2) % 4 == 0: pair h0 / 2 + j = h0 / 2 ^ j
-    const uint32_t b = drop_fin(x ^ drop_col((uint32_t)j));
-    kf[2 * j] = keep_factor(b, 0, dp);
-    kf[2 * j + 1] = keep_factor(b, 1, dp);
-  }
-}
+using head::keep8;
+using head::pack8;
+using head::unpack8;
 
 // the bf16 classifier input d = bf16(h · keep · scale) of one lane's 8 columns (h itself without dropout)
 __device__ __forceinline__ u32x4 dropped8(const u32x4& raw, uint32_t rw, int h0, const DropoutParams& dp) {
@@ -215,34 +193,6 @@ __global__ __launch_bounds__(256) void tok_fwd_kernel(const bf16_t* __restrict__
   if (threadIdx.x < 3) {
     const int k = threadIdx.x;
     partials[(int64_t)blockIdx.x * 4 + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-  }
-}
-
-// stats = {loss_sum / max(n_valid, 1), hits, n_valid, loss_sum}
-__global__ __launch_bounds__(256) void tok_stats_kernel(const float* __restrict__ partials, int nblk,
-                                                        float* __restrict__ stats) {
-  __shared__ float red[4][3];
-  float s[3] = {0.f, 0.f, 0.f};
-  for (int b = threadIdx.x; b < nblk; b += blockDim.x) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s[k] += partials[(int64_t)b * 4 + k];
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) s[k] = wave_sum(s[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) red[wave][k] = s[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-    stats[0] = t[0] / fmaxf(t[2], 1.0f);
-    stats[1] = t[1];
-    stats[2] = t[2];
-    stats[3] = t[0];
   }
 }
 
@@ -497,10 +447,7 @@ void launch_token_head_fwd(const bf16_t* h, const bf16_t* W, const bf16_t* b, co
   const DropoutParams dp = make_dropout(p, seed);
   hipLaunchKernelGGL(tok::tok_fwd_kernel, dim3(nblk), dim3(256), 0, st, h, W, b, labels, logits, partials, R, H, C, dp);
   HSD_CHECK_LAUNCH();
-  if (labels != nullptr) {
-    hipLaunchKernelGGL(tok::tok_stats_kernel, dim3(1), dim3(256), 0, st, (const float*)partials, nblk, stats);
-    HSD_CHECK_LAUNCH();
-  }
+  if (labels != nullptr) launch_head_stats(partials, nblk, stats, st);
 }
 
 void launch_token_head_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* logits, const int64_t* labels,

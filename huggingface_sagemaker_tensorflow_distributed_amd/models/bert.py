@@ -149,14 +149,27 @@ def _init_(module: nn.Module, cfg: ModelConfig, generator: Optional[torch.Genera
                 e.position_embeddings[cfg.pad_token_id].zero_()
 
 
+_FAMILY = {"bert": "Bert", "roberta": "Roberta", "distilbert": "DistilBert"}  # HF's class-name prefix per model_type
+
+
 class _Base(nn.Module):
-    base_prefix = "bert"
+    base_prefix = None  # HF's name of the base model: cfg.model_type, unless the class fixes it
+    arch_suffix = None  # HF's class name is _FAMILY[cfg.model_type] + arch_suffix
 
     def __init__(self, cfg: ModelConfig):
         super().__init__()
         self.cfg = cfg
+        if self.base_prefix is None:
+            if cfg.model_type not in _FAMILY:
+                raise KeyError(cfg.model_type)
+            self.base_prefix = cfg.model_type
         self.encoder = Encoder(cfg)
         self.rng = DropoutSeeds(0)
+
+    def _encode(self, input_ids, attention_mask, token_type_ids, cu_seqlens, max_seqlen, position_ids,
+                first_token_only=False):
+        return self.encoder(input_ids, attention_mask, token_type_ids, self.rng, self.training, cu_seqlens=cu_seqlens,
+                            max_seqlen=max_seqlen, position_ids=position_ids, first_token_only=first_token_only)
 
     # ----------------------------------------------------------------- HF name mapping
     def _embedding_hf_names(self) -> Iterator[Tuple[str, str, Optional[int], int]]:
@@ -183,7 +196,7 @@ class _Base(nn.Module):
         yield from self._head_hf_names()
 
     def architecture(self) -> str:
-        raise NotImplementedError
+        return _FAMILY[self.cfg.model_type] + self.arch_suffix
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters())
@@ -192,19 +205,16 @@ class _Base(nn.Module):
 class TransformerForSequenceClassification(_Base):
     """BertForSequenceClassification / RobertaForSequenceClassification / DistilBertForSequenceClassification."""
 
+    arch_suffix = "ForSequenceClassification"
+
     def __init__(self, cfg: ModelConfig):
         super().__init__(cfg)
         H, L = cfg.hidden_size, cfg.num_labels
-        self.base_prefix = {"bert": "bert", "roberta": "roberta", "distilbert": "distilbert"}[cfg.model_type]
         if cfg.model_type == "bert":
             self.pooler_weight, self.pooler_bias = _param(H, H), _param(H)
         else:  # roberta classifier.dense / distilbert pre_classifier
             self.head_dense_weight, self.head_dense_bias = _param(H, H), _param(H)
         self.classifier_weight, self.classifier_bias = _param(L, H), _param(L)
-
-    def architecture(self) -> str:
-        return {"bert": "BertForSequenceClassification", "roberta": "RobertaForSequenceClassification",
-                "distilbert": "DistilBertForSequenceClassification"}[self.cfg.model_type]
 
     def _head_hf_names(self):
         mt = self.cfg.model_type
@@ -228,8 +238,8 @@ class TransformerForSequenceClassification(_Base):
                 max_seqlen=None, position_ids=None):
         c = self.cfg
         training = self.training
-        h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, training, cu_seqlens=cu_seqlens,
-                         max_seqlen=max_seqlen, position_ids=position_ids, first_token_only=cu_seqlens is None)
+        h = self._encode(input_ids, attention_mask, token_type_ids, cu_seqlens, max_seqlen, position_ids,
+                         first_token_only=cu_seqlens is None)
         if cu_seqlens is not None:
             # packed [T, H]: the first-token row of sequence b is row cu_seqlens[b]
             h = h.index_select(0, cu_seqlens[:-1].long()).unsqueeze(1)  # [B, 1, H]
@@ -246,10 +256,8 @@ class TransformerForSequenceClassification(_Base):
             p = c.seq_classif_dropout if training else 0.0
             w1, b1, act, p_in, seed_in = self.head_dense_weight, self.head_dense_bias, "relu", 0.0, 0
         seed = self.rng.next() if p else 0
-        out = ops.cls_head(h, w1, b1, self.classifier_weight, self.classifier_bias, labels, act, p_in, seed_in, p, seed)
-        if labels is not None:
-            return out  # (loss, logits)
-        return out
+        # logits without labels, else (loss, logits)
+        return ops.cls_head(h, w1, b1, self.classifier_weight, self.classifier_bias, labels, act, p_in, seed_in, p, seed)
 
 
 class TransformerForTokenClassification(_Base):
@@ -263,15 +271,11 @@ class TransformerForTokenClassification(_Base):
     whole step captures into a graph (``graph_safe``)."""
 
     graph_safe = True
+    arch_suffix = "ForTokenClassification"
 
     def __init__(self, cfg: ModelConfig):
         super().__init__(cfg)
-        self.base_prefix = {"bert": "bert", "roberta": "roberta", "distilbert": "distilbert"}[cfg.model_type]
         self.classifier_weight, self.classifier_bias = _param(cfg.num_labels, cfg.hidden_size), _param(cfg.num_labels)
-
-    def architecture(self) -> str:
-        return {"bert": "BertForTokenClassification", "roberta": "RobertaForTokenClassification",
-                "distilbert": "DistilBertForTokenClassification"}[self.cfg.model_type]
 
     def _head_hf_names(self):
         yield "classifier.weight", "classifier_weight", None, 1
@@ -285,8 +289,7 @@ class TransformerForTokenClassification(_Base):
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, *, cu_seqlens=None,
                 max_seqlen=None, position_ids=None):
-        h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, self.training, cu_seqlens=cu_seqlens,
-                         max_seqlen=max_seqlen, position_ids=position_ids, first_token_only=False)
+        h = self._encode(input_ids, attention_mask, token_type_ids, cu_seqlens, max_seqlen, position_ids)
         H = h.shape[-1]
         p = self.head_dropout() if self.training else 0.0
         seed = self.rng.next() if p else 0
@@ -316,16 +319,12 @@ class TransformerForQuestionAnswering(_Base):
     (``graph_safe``)."""
 
     graph_safe = True
+    arch_suffix = "ForQuestionAnswering"
     max_answer_length = 30
 
     def __init__(self, cfg: ModelConfig):
         super().__init__(cfg)
-        self.base_prefix = {"bert": "bert", "roberta": "roberta", "distilbert": "distilbert"}[cfg.model_type]
         self.qa_outputs_weight, self.qa_outputs_bias = _param(2, cfg.hidden_size), _param(2)
-
-    def architecture(self) -> str:
-        return {"bert": "BertForQuestionAnswering", "roberta": "RobertaForQuestionAnswering",
-                "distilbert": "DistilBertForQuestionAnswering"}[self.cfg.model_type]
 
     def _head_hf_names(self):
         yield "qa_outputs.weight", "qa_outputs_weight", None, 1
@@ -341,8 +340,7 @@ class TransformerForQuestionAnswering(_Base):
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, *, cu_seqlens=None,
                 max_seqlen=None, position_ids=None):
-        h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, self.training, cu_seqlens=cu_seqlens,
-                         max_seqlen=max_seqlen, position_ids=position_ids, first_token_only=False)
+        h = self._encode(input_ids, attention_mask, token_type_ids, cu_seqlens, max_seqlen, position_ids)
         H = h.shape[-1]
         p = self.head_dropout() if self.training else 0.0
         seed = self.rng.next() if p else 0
@@ -471,8 +469,7 @@ class RobertaForMaskedLM(_Base):
         if labels is not None and self.mlm_masking == "dynamic":
             mask = self.mask_batch(input_ids, attention_mask, labels)
             input_ids = mask.input_ids
-        h = self.encoder(input_ids, attention_mask, token_type_ids, self.rng, self.training, cu_seqlens=cu_seqlens,
-                         max_seqlen=max_seqlen, position_ids=position_ids)
+        h = self._encode(input_ids, attention_mask, token_type_ids, cu_seqlens, max_seqlen, position_ids)
         if cu_seqlens is not None:
             h = h.unsqueeze(0)  # packed [T, H] -> [1, T, H]; labels are the packed [T]
         B, S, H = h.shape

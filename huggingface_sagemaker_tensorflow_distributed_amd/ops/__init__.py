@@ -217,6 +217,33 @@ def join_side_streams() -> None:
         _hipmod().join_side_streams()
 
 
+def _with_stats(loss, stats, pred=None):
+    """The attribute protocol of the fused heads: ``loss._hsd_stats`` = the head's device stats (the metric meter folds
+    them lazily) with the argmax hits on ``loss._hsd_correct``, or, for a span head, its best spans on
+    ``loss._hsd_pred``."""
+    loss._hsd_stats = stats
+    if pred is None:
+        loss._hsd_correct = stats[1]
+    else:
+        loss._hsd_pred = pred
+    return loss
+
+
+def _sum_ce(logits, tgt, n=None):
+    """Composed CE: ``Σ CE / max(n, 1)`` over the rows whose target is not -100, carrying {mean loss, hits, n, loss
+    sum}. ``n``: the number of such rows as a device fp32 scalar (counted here when not given)."""
+    lsum = torch.nn.functional.cross_entropy(logits.float(), tgt, ignore_index=-100, reduction="sum")
+    with torch.no_grad():
+        ok = tgt.ne(-100)
+        if n is None:
+            n = ok.sum().to(torch.float32)
+        hits = ((logits.argmax(dim=-1) == tgt) & ok).sum().to(torch.float32)
+    loss = lsum / n.clamp(min=1.0)
+    with torch.no_grad():
+        stats = torch.stack([loss.detach().float(), hits, n, lsum.detach().float()])
+    return _with_stats(loss, stats)
+
+
 def cross_entropy(logits, labels):
     """Mean CE over non-ignored labels. On the HIP path the fused kernel also counts argmax hits; the count
     rides on the loss tensor (``loss._hsd_correct``) so metrics need no second pass over the logits."""
@@ -235,16 +262,10 @@ def cls_head(h, w1, b1, w2, b2, labels, act: str, p_in: float, seed_in: int, p: 
     and the fused {mean loss, hits, rows, loss sum} on ``loss._hsd_stats`` (HIP path). On GPUs the dense layer runs on gemm2 and everything after it (activation, dropout, classifier, CE,
     accuracy) in one fused kernel per direction (csrc/kernels/cls_head.hip); the first-token rows are read in place
     (no gather copy) and their gradient is written straight into the zeroed ``dh`` rows."""
-    if _hip(h) and labels is not None and _hipmod().cls_head_ok(h, w1, w2):
-        loss, logits, stats = _hipmod().cls_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed)
-        loss._hsd_correct = stats[1]
-        loss._hsd_stats = stats  # {mean loss, hits, rows, loss sum}: the metric meter folds these lazily
-        return loss, logits
-    if _hip32(h) and labels is not None and _hip32mod().cls_head_ok(h, w1, w2):
-        loss, logits, stats = _hip32mod().cls_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed)
-        loss._hsd_correct = stats[1]
-        loss._hsd_stats = stats
-        return loss, logits
+    mod = _hipmod() if _hip(h) else _hip32mod() if _hip32(h) else None
+    if mod is not None and labels is not None and mod.cls_head_ok(h, w1, w2):
+        loss, logits, stats = mod.cls_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed)
+        return _with_stats(loss, stats), logits
     x = h[:, 0].contiguous()
     if _hip(h) or _hip32(h):
         x = dropout(x, p_in, seed_in)
@@ -276,29 +297,15 @@ def token_head(h2d, w, b, labels, p: float, seed: int):
         if lab is None:  # inference: the fused forward alone (differentiable logits take the composed ops below)
             return _hipmod().token_head_logits(h2d, w, b, p, seed)
         loss, logits, stats = _hipmod().token_head(h2d, w, b, lab, p, seed)
-        loss._hsd_correct = stats[1]
-        loss._hsd_stats = stats
-        return loss, logits
+        return _with_stats(loss, stats), logits
     if _hip(h2d) or (_hip32(h2d) and w.shape[0] % 4 == 0):  # (the fp32 GEMM epilogue takes whole groups of 4 columns)
         logits = linear(dropout(h2d, p, seed), w, b)
-        if lab is None:
-            return logits
-        lsum = torch.nn.functional.cross_entropy(logits.float(), lab.long(), ignore_index=-100, reduction="sum")
-        with torch.no_grad():
-            ok = lab.ne(-100)
-            n = ok.sum().to(torch.float32)
-            hits = ((logits.argmax(dim=-1) == lab) & ok).sum().to(torch.float32)
-        loss = lsum / n.clamp(min=1.0)
-        with torch.no_grad():
-            stats = torch.stack([loss.detach().float(), hits, n, lsum.detach().float()])
-    else:
-        out = _ref.token_head(h2d, w, b, lab, p, seed, True)
-        if lab is None:
-            return out
-        loss, logits, stats = out
-    loss._hsd_correct = stats[1]
-    loss._hsd_stats = stats
-    return loss, logits
+        return logits if lab is None else (_sum_ce(logits, lab.long()), logits)
+    out = _ref.token_head(h2d, w, b, lab, p, seed, True)
+    if lab is None:
+        return out
+    loss, logits, stats = out
+    return _with_stats(loss, stats), logits
 
 
 def qa_head(h2d, w, b, positions, cu, row_mask, p: float, seed: int, max_answer_length: int = 30, max_seqlen=None):
@@ -332,9 +339,7 @@ def qa_head(h2d, w, b, positions, cu, row_mask, p: float, seed: int, max_answer_
         if positions is None:
             return out
         loss, logits, stats, pred = out
-    loss._hsd_stats = stats
-    loss._hsd_pred = pred
-    return loss, logits
+    return _with_stats(loss, stats, pred), logits
 
 
 def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
@@ -384,9 +389,7 @@ def mlm_head_fixed(h2d, mask, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
     if _hip(h2d) and h2d.dtype == torch.bfloat16 and _hipmod().mlm_head_ok(h2d, w1, wemb):
         loss, logits, stats = _hipmod().mlm_head_fixed(h2d, sel, tgt, mask.inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb,
                                                        bias, vocab)
-        loss._hsd_correct = stats[1]
-        loss._hsd_stats = stats
-        return loss, logits
+        return _with_stats(loss, stats), logits
     x = h2d.index_select(0, sel)
     if _hip(h2d) or _hip32(h2d):
         x = layer_norm(linear_gelu(x, w1, b1), ln_w, ln_b, eps)
@@ -394,15 +397,7 @@ def mlm_head_fixed(h2d, mask, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
     else:
         x = _ref.layer_norm(_ref.linear_gelu(x, w1, b1), ln_w, ln_b, eps)
         logits = torch.nn.functional.linear(x, wemb[:vocab], bias[:vocab])
-    lsum = torch.nn.functional.cross_entropy(logits.float(), tgt, ignore_index=-100, reduction="sum")
-    nv = n_valid[0].clamp(min=1.0)
-    loss = lsum / nv
-    with torch.no_grad():
-        hits = ((logits.argmax(dim=-1) == tgt) & tgt.ne(-100)).sum().to(torch.float32)
-        stats = torch.stack([loss.detach().float(), hits, n_valid[0], lsum.detach().float()])
-    loss._hsd_correct = stats[1]
-    loss._hsd_stats = stats
-    return loss, logits
+    return _sum_ce(logits, tgt, n_valid[0]), logits
 
 
 def accuracy_count(logits, labels):

@@ -1319,6 +1319,13 @@ def key_mask_bias(attention_mask):
 _ACT = {"tanh": 0, "relu": 1}
 
 
+def _dloss1(dloss, device):
+    """The incoming loss gradient as the fp32 [1] tensor the head kernels read (None: the loss is unused -> 0)."""
+    if dloss is None:
+        dloss = torch.zeros((), dtype=torch.float32, device=device)
+    return dloss.reshape(1).to(torch.float32).contiguous()
+
+
 def cls_head_ok(h, w1, w2) -> bool:
     H = h.shape[-1]
     return (h.dtype == torch.bfloat16 and h.dim() == 3 and H % 8 == 0 and H <= 1024 and 1 <= w2.shape[0] <= 4
@@ -1357,10 +1364,7 @@ class _ClsHead(torch.autograd.Function):
         act, p_in, seed_in, p, seed, B, S, H = ctx.cfg
         g_w1, g_b1, g_w2, g_b2 = _Grad(w1), _Grad(b1), _Grad(w2), _Grad(b2)
         dpre = torch.empty_like(t)
-        if dloss is None:
-            dloss = torch.zeros((), dtype=torch.float32, device=t.device)
-        dl = dloss.reshape(1).to(torch.float32).contiguous()
-        _C.cls_head_bwd(t, w2, logits, lab, stats, dl, dpre, g_w2.buf, g_b2.buf, _ACT[act], p, _s64(seed))
+        _C.cls_head_bwd(t, w2, logits, lab, stats, _dloss1(dloss, t.device), dpre, g_w2.buf, g_b2.buf, _ACT[act], p, _s64(seed))
         r_w2, r_b2 = g_w2.done(), g_b2.done()
         _C.colsum(dpre, g_b1.buf)
         r_b1 = g_b1.done()
@@ -1398,6 +1402,26 @@ def token_head_ok(h2d, w) -> bool:
             and 8 <= H <= 1024 and 2 <= w.shape[0] <= 16 and w.shape[1] == H)
 
 
+def _token_logits(x, wc, bc, p, seed):
+    """tok_fwd_kernel in its logits-only mode (no labels, no stats): the one streaming pass over h."""
+    logits = torch.empty((x.shape[0], wc.shape[0]), dtype=x.dtype, device=x.device)
+    scratch = torch.empty(_C.token_head_fwd_blocks(x.shape[0]) * 4 + 4, dtype=torch.float32, device=x.device)
+    _C.token_head_fwd(x, wc, bc, None, logits, scratch[4:], scratch[:4], float(p), _s64(seed))
+    return logits
+
+
+def _token_bwd_args(ctx, x, w, b, dloss):
+    """What both backward entries of token_head.hip take besides their gradient source: the two gradient targets,
+    dloss as fp32 [1], dh (None when h needs no gradient) and the per-block slab workspace."""
+    R, H = x.shape
+    C = w.shape[0]
+    g_w, g_b = _Grad(w), _Grad(b)
+    dl = _dloss1(dloss, x.device)
+    dh = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+    part = _workspace(_C.token_head_bwd_blocks(R) * (C * H + C), x.device)
+    return g_w, g_b, dl, dh, part
+
+
 class _TokenHead(torch.autograd.Function):
     """Every row of h -> fused dropout / classifier / CE / accuracy (token_head.hip: one kernel + the stats reducer).
     Backward: one fused kernel (CE grad, dh with the dropout mask, per-block fp32 dW / db slabs in the shared
@@ -1424,14 +1448,7 @@ class _TokenHead(torch.autograd.Function):
     def backward(ctx, dloss, _dlogits, _dstats):
         x, w, b, logits, lab, stats = ctx.saved_tensors
         p, seed = ctx.cfg
-        R, H = x.shape
-        C = w.shape[0]
-        g_w, g_b = _Grad(w), _Grad(b)
-        if dloss is None:
-            dloss = torch.zeros((), dtype=torch.float32, device=x.device)
-        dl = dloss.reshape(1).to(torch.float32).contiguous()
-        dh = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        part = _workspace(_C.token_head_bwd_blocks(R) * (C * H + C), x.device)
+        g_w, g_b, dl, dh, part = _token_bwd_args(ctx, x, w, b, dloss)
         _C.token_head_bwd(x, w.contiguous(), logits, lab, stats, dl, dh, part, g_w.buf.view(-1), g_b.buf.view(-1),
                           p, _s64(seed))
         return dh, g_w.done(), g_b.done(), None, None, None
@@ -1445,13 +1462,7 @@ def token_head(h2d, w, b, labels, p, seed):
 
 def token_head_logits(h2d, w, b, p, seed):
     """The fused head's logits alone (inference: no labels, no autograd)."""
-    x = h2d.contiguous()
-    logits = torch.empty((x.shape[0], w.shape[0]), dtype=x.dtype, device=x.device)
-    partials = torch.empty(_C.token_head_fwd_blocks(x.shape[0]) * 4, dtype=torch.float32, device=x.device)
-    stats = torch.empty(4, dtype=torch.float32, device=x.device)
-    _C.token_head_fwd(x.detach(), w.detach().contiguous(), b.detach().contiguous(), None, logits, partials, stats,
-                      float(p), _s64(seed))
-    return logits
+    return _token_logits(h2d.detach().contiguous(), w.detach().contiguous(), b.detach().contiguous(), p, seed)
 
 
 # ------------------------------------------------------------------------------------------ question-answering head
@@ -1475,14 +1486,6 @@ def _span_args(x, cu, row_mask):
     return cu32.contiguous(), mask
 
 
-def _qa_logits(x, wc, bc, p, seed):
-    """tok_fwd_kernel in its logits-only mode with C = 2: the one streaming pass over h."""
-    logits = torch.empty((x.shape[0], 2), dtype=x.dtype, device=x.device)
-    scratch = torch.empty(_C.token_head_fwd_blocks(x.shape[0]) * 4 + 4, dtype=torch.float32, device=x.device)
-    _C.token_head_fwd(x, wc, bc, None, logits, scratch[4:], scratch[:4], float(p), _s64(seed))
-    return logits
-
-
 class _QAHead(torch.autograd.Function):
     """Every row of h -> logits (token_head.hip, logits-only) -> span_ce_kernel + span_stats_kernel (qa_head.hip).
     Backward: the token head's backward from the saved gradient table g0 (tok_bwd_kernel<true>) + the slab reducer
@@ -1495,7 +1498,7 @@ class _QAHead(torch.autograd.Function):
         R = x.shape[0]
         B = cu.numel() - 1
         cu32, mask = _span_args(x, cu, row_mask)
-        logits = _qa_logits(x, wc, bc, p, seed)
+        logits = _token_logits(x, wc, bc, p, seed)
         pos = positions.reshape(B, 2).contiguous().long()
         rec = torch.empty(B * 8, dtype=torch.float32, device=x.device)
         pred = torch.empty((B, 2), dtype=torch.int32, device=x.device)
@@ -1512,13 +1515,7 @@ class _QAHead(torch.autograd.Function):
     def backward(ctx, dloss, _dlogits, _dstats, _dpred):
         x, w, b, g0, stats = ctx.saved_tensors
         p, seed = ctx.cfg
-        R, H = x.shape
-        g_w, g_b = _Grad(w), _Grad(b)
-        if dloss is None:
-            dloss = torch.zeros((), dtype=torch.float32, device=x.device)
-        dl = dloss.reshape(1).to(torch.float32).contiguous()
-        dh = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        part = _workspace(_C.token_head_bwd_blocks(R) * (2 * H + 2), x.device)
+        g_w, g_b, dl, dh, part = _token_bwd_args(ctx, x, w, b, dloss)
         # g = g0 · dloss · ½ / max(n_c, 1), n_c = stats[4 + c]
         _C.token_head_bwd_given(x, w.contiguous(), g0, stats[4:6], 0.5, dl, dh, part, g_w.buf.view(-1),
                                 g_b.buf.view(-1), p, _s64(seed))
@@ -1536,7 +1533,7 @@ def qa_head_logits(h2d, w, b, cu, row_mask, p, seed, max_answer_length):
     x = h2d.detach().contiguous()
     B = cu.numel() - 1
     cu32, mask = _span_args(x, cu, row_mask)
-    logits = _qa_logits(x, w.detach().contiguous(), b.detach().contiguous(), p, seed)
+    logits = _token_logits(x, w.detach().contiguous(), b.detach().contiguous(), p, seed)
     pred = torch.empty((B, 2), dtype=torch.int32, device=x.device)
     none = torch.empty(0, dtype=torch.float32, device=x.device)
     _C.span_ce(logits, cu32, mask, None, int(max_answer_length), none, pred, none, none)
@@ -1549,6 +1546,51 @@ def mlm_head_ok(h2d, w1, wemb) -> bool:
     Vp = wemb.shape[0]
     return (H % 64 == 0 and w1.shape == (H, H) and Vp % 256 == 0 and wemb.shape[1] == H and wemb.is_contiguous()
             and _C.gemm2_supported(0, 0, EPI_BIAS, 64, Vp, H) and _C.gemm2_supported(0, 1, EPI_STORE, 64, H, Vp))
+
+
+def _mlm_fwd(ctx, x, rows, tgt, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
+    """The masked-LM head's forward chain on the selected rows ``x [rows, H]`` (a multiple of 64, ``tgt = -100`` on
+    the padding rows): gemm2 NT with the bias + GELU epilogue -> LN -> gemm2 NT against the tied table -> xent over
+    the real vocabulary columns, which also leaves dlogits / n_valid for the backward. ``n_valid``: fp32 [1] on the
+    device, or the host count. ``rows`` is the caller's row map (saved for its own scatter of dh). Returns
+    (logits [rows, Vp], raw = fp32 {loss sum, argmax hits})."""
+    act = torch.empty_like(x)
+    pre = gemm_fwd(x, w1, EPI_BIAS_GELU, bias=b1, out2=act)
+    y, mean, rstd = _ln_fwd(act, ln_w, ln_b, eps)
+    logits = gemm_fwd(y, wemb, EPI_BIAS, bias=bias)
+    raw = torch.zeros(2, dtype=torch.float32, device=x.device)
+    if not torch.is_tensor(n_valid):
+        n_valid = torch.full((1,), float(n_valid), dtype=torch.float32, device=x.device)
+    dlogits = torch.empty_like(logits)
+    _C.xent(logits, tgt, dlogits, raw, n_valid, vocab)
+    ctx.save_for_backward(x, rows, w1, b1, pre, act, y, mean, rstd, ln_w, ln_b, wemb, bias, dlogits)
+    return logits, raw
+
+
+def _mlm_bwd(ctx, dloss):
+    """The backward chain of :func:`_mlm_fwd` down to dx (None when h needs no gradient). Returns (dx, rows, g_w1,
+    g_b1, g_lnw, g_lnb, r_wemb, g_bias): the tied table's gradient is already handed over (its weight gradient may run
+    on the side stream), the other targets are for the caller to finish after its scatter of dh."""
+    x, rows, w1, b1, pre, act, y, mean, rstd, ln_w, ln_b, wemb, bias, dlogits = ctx.saved_tensors
+    g_wemb, g_w1, g_b1, g_lnw, g_lnb, g_bias = _Grad(wemb), _Grad(w1), _Grad(b1), _Grad(ln_w), _Grad(ln_b), _Grad(bias)
+    dl = _dloss1(dloss, x.device)
+    # decoder bias: column sums of dlogits, scaled by the incoming loss gradient
+    cs = torch.zeros(dlogits.shape[1], dtype=torch.float32, device=x.device)
+    _C.colsum(dlogits, cs)
+    g_bias.buf.add_(cs * dl)
+    # tied embedding table: += dlogitsᵀ · (y · dloss)   (dlogits is already 1/n-scaled by the CE kernel)
+    gemm_wgrad_(g_wemb, dlogits, (y * dl.to(y.dtype)).contiguous())
+    r_wemb = g_wemb.done()
+    dy = torch.empty_like(y)
+    _C.gemm2(dlogits, wemb, dy, 0, 1, EPI_STORE, None, None, None, 0.0, 0, 0, None, None)
+    dy.mul_(dl.to(dy.dtype))
+    dact = torch.empty_like(act)
+    _C.ln_bwd(dy, act, mean, rstd, ln_w, None, dact, None, g_lnw.buf, g_lnb.buf, None, 0.0, 0)
+    dpre = torch.empty_like(pre)
+    _C.gelu_bwd_colsum(dact, pre, dpre, g_b1.buf)
+    gemm_wgrad_(g_w1, dpre, x)
+    dx = gemm_dgrad(dpre, w1) if ctx.needs_input_grad[0] else None
+    return dx, rows, g_w1, g_b1, g_lnw, g_lnb, r_wemb, g_bias
 
 
 class _MlmHead(torch.autograd.Function):
@@ -1566,7 +1608,6 @@ class _MlmHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
         T, H = h2d.shape
-        Vp = wemb.shape[0]
         lab = labels.reshape(-1)
         sel = lab.ne(-100).nonzero(as_tuple=True)[0]
         n = int(sel.numel())
@@ -1576,16 +1617,8 @@ class _MlmHead(torch.autograd.Function):
         tgt = torch.full((npad,), -100, dtype=torch.long, device=h2d.device)
         tgt[:n] = lab.index_select(0, sel)
         x = h2d.index_select(0, idx)
-        act = torch.empty((npad, H), dtype=h2d.dtype, device=h2d.device)
-        pre = gemm_fwd(x, w1, EPI_BIAS_GELU, bias=b1, out2=act)
-        y, mean, rstd = _ln_fwd(act, ln_w, ln_b, eps)
-        logits = gemm_fwd(y, wemb, EPI_BIAS, bias=bias)
-        stats = torch.zeros(2, dtype=torch.float32, device=h2d.device)
-        n_valid = torch.full((1,), float(n), dtype=torch.float32, device=h2d.device)
-        dlogits = torch.empty_like(logits)
-        _C.xent(logits, tgt, dlogits, stats, n_valid, vocab)
+        logits, stats = _mlm_fwd(ctx, x, sel, tgt, n, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab)
         loss = stats[0] * (1.0 / max(n, 1))
-        ctx.save_for_backward(x, sel, w1, b1, pre, act, y, mean, rstd, ln_w, ln_b, wemb, bias, dlogits)
         ctx.cfg = (T, H, n)
         ctx.mark_non_differentiable(stats)
         ctx.set_materialize_grads(False)
@@ -1593,30 +1626,10 @@ class _MlmHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, _dlogits, _dcorrect):
-        x, sel, w1, b1, pre, act, y, mean, rstd, ln_w, ln_b, wemb, bias, dlogits = ctx.saved_tensors
         T, H, n = ctx.cfg
-        g_wemb, g_w1, g_b1, g_lnw, g_lnb, g_bias = _Grad(wemb), _Grad(w1), _Grad(b1), _Grad(ln_w), _Grad(ln_b), _Grad(bias)
-        if dloss is None:
-            dloss = torch.zeros((), dtype=torch.float32, device=x.device)
-        dl = dloss.reshape(1).to(torch.float32)
-        # decoder bias: column sums of dlogits, scaled by the incoming loss gradient
-        cs = torch.zeros(dlogits.shape[1], dtype=torch.float32, device=x.device)
-        _C.colsum(dlogits, cs)
-        g_bias.buf.add_(cs * dl)
-        # tied embedding table: += dlogitsᵀ · (y · dloss)   (dlogits is already 1/n-scaled by the CE kernel)
-        gemm_wgrad_(g_wemb, dlogits, (y * dl.to(y.dtype)).contiguous())
-        r_wemb = g_wemb.done()
-        dy = torch.empty_like(y)
-        _C.gemm2(dlogits, wemb, dy, 0, 1, EPI_STORE, None, None, None, 0.0, 0, 0, None, None)
-        dy.mul_(dl.to(dy.dtype))
-        dact = torch.empty_like(act)
-        _C.ln_bwd(dy, act, mean, rstd, ln_w, None, dact, None, g_lnw.buf, g_lnb.buf, None, 0.0, 0)
-        dpre = torch.empty_like(pre)
-        _C.gelu_bwd_colsum(dact, pre, dpre, g_b1.buf)
-        gemm_wgrad_(g_w1, dpre, x)
+        dx, sel, g_w1, g_b1, g_lnw, g_lnb, r_wemb, g_bias = _mlm_bwd(ctx, dloss)
         dh = None
-        if ctx.needs_input_grad[0]:
-            dx = gemm_dgrad(dpre, w1)
+        if dx is not None:
             dh = torch.empty((T, H), dtype=dx.dtype, device=dx.device)
             _C.memset0(dh)
             dh.index_copy_(0, sel, dx[:n])
@@ -1678,16 +1691,9 @@ class _MlmHeadFixed(torch.autograd.Function):
     def forward(ctx, h2d, sel, tgt, inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
         T, H = h2d.shape
         x = h2d.index_select(0, sel)
-        act = torch.empty((sel.shape[0], H), dtype=h2d.dtype, device=h2d.device)
-        pre = gemm_fwd(x, w1, EPI_BIAS_GELU, bias=b1, out2=act)
-        y, mean, rstd = _ln_fwd(act, ln_w, ln_b, eps)
-        logits = gemm_fwd(y, wemb, EPI_BIAS, bias=bias)
-        raw = torch.zeros(2, dtype=torch.float32, device=h2d.device)
-        dlogits = torch.empty_like(logits)
-        _C.xent(logits, tgt, dlogits, raw, n_valid, vocab)
+        logits, raw = _mlm_fwd(ctx, x, inv, tgt, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab)
         loss = raw[0] / n_valid[0].clamp(min=1.0)
         stats = torch.stack([loss, raw[1], n_valid[0], raw[0]])
-        ctx.save_for_backward(x, inv, w1, b1, pre, act, y, mean, rstd, ln_w, ln_b, wemb, bias, dlogits)
         ctx.cfg = (T, H)
         ctx.mark_non_differentiable(stats)
         ctx.set_materialize_grads(False)
@@ -1695,28 +1701,10 @@ class _MlmHeadFixed(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, _dlogits, _dstats):
-        x, inv, w1, b1, pre, act, y, mean, rstd, ln_w, ln_b, wemb, bias, dlogits = ctx.saved_tensors
         T, H = ctx.cfg
-        g_wemb, g_w1, g_b1, g_lnw, g_lnb, g_bias = _Grad(wemb), _Grad(w1), _Grad(b1), _Grad(ln_w), _Grad(ln_b), _Grad(bias)
-        if dloss is None:
-            dloss = torch.zeros((), dtype=torch.float32, device=x.device)
-        dl = dloss.reshape(1).to(torch.float32)
-        cs = torch.zeros(dlogits.shape[1], dtype=torch.float32, device=x.device)
-        _C.colsum(dlogits, cs)
-        g_bias.buf.add_(cs * dl)
-        gemm_wgrad_(g_wemb, dlogits, (y * dl.to(y.dtype)).contiguous())
-        r_wemb = g_wemb.done()
-        dy = torch.empty_like(y)
-        _C.gemm2(dlogits, wemb, dy, 0, 1, EPI_STORE, None, None, None, 0.0, 0, 0, None, None)
-        dy.mul_(dl.to(dy.dtype))
-        dact = torch.empty_like(act)
-        _C.ln_bwd(dy, act, mean, rstd, ln_w, None, dact, None, g_lnw.buf, g_lnb.buf, None, 0.0, 0)
-        dpre = torch.empty_like(pre)
-        _C.gelu_bwd_colsum(dact, pre, dpre, g_b1.buf)
-        gemm_wgrad_(g_w1, dpre, x)
+        dx, inv, g_w1, g_b1, g_lnw, g_lnb, r_wemb, g_bias = _mlm_bwd(ctx, dloss)
         dh = None
-        if ctx.needs_input_grad[0]:
-            dx = gemm_dgrad(dpre, w1)
+        if dx is not None:
             dh = torch.empty((T, H), dtype=dx.dtype, device=dx.device)
             _C.mlm_scatter_rows(dx, inv, dh)
         return (dh, None, None, None, None, g_w1.done(), g_b1.done(), g_lnw.done(), g_lnb.done(), None, r_wemb,
