@@ -1182,6 +1182,86 @@ void cls_head_bwd(torch::Tensor t, torch::Tensor W2, torch::Tensor logits, torch
                            (uint64_t)seed, cur_stream());
 }
 
+// fused sequence-level head for --problem_type (seq_head.hip): the shapes of cls_head with 1 <= C <= 64. mode 0: CE,
+// labels int64 [R]; 1: BCE-with-logits, 2: MSE, labels fp32 [R][C]; labels may be none in the forward (logits only)
+static void seq_head_labels(const c10::optional<torch::Tensor>& labels, int64_t mode, int64_t R, int64_t C,
+                            const int64_t** lab_i, const float** lab_f) {
+  TORCH_CHECK(mode >= 0 && mode <= 2, "seq_head mode: 0 CE, 1 BCE, 2 MSE");
+  *lab_i = nullptr;
+  *lab_f = nullptr;
+  if (!labels.has_value()) return;
+  TORCH_CHECK(labels->is_cuda(), "seq_head labels device");
+  if (mode == 0) {
+    *lab_i = head_labels(*labels, R);
+  } else {
+    check_f32(*labels, "labels");
+    TORCH_CHECK(labels->is_contiguous() && labels->numel() == R * C, "seq_head labels: fp32 [R][C]");
+    *lab_f = labels->data_ptr<float>();
+  }
+}
+
+void seq_head_fwd(torch::Tensor pre, torch::Tensor W2, torch::Tensor b2, c10::optional<torch::Tensor> labels,
+                  torch::Tensor t_out, torch::Tensor logits, torch::Tensor partials, torch::Tensor stats, int64_t mode,
+                  double tol, int64_t act, double p, int64_t seed) {
+  TORCH_CHECK(pre.is_cuda() && pre.dim() == 2 && pre.stride(1) == 1 && pre.stride(0) % 8 == 0 &&
+              pre.scalar_type() == torch::kBFloat16, "seq_head pre");
+  const int64_t R = pre.size(0), H = pre.size(1), C = W2.size(0);
+  TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 16 && H % 8 == 0 && H >= 8 && H <= 1024 && C >= 1 && C <= 64,
+              "seq_head: 1 <= rows < 2^31, H % 8 == 0, H <= 1024, 1 <= classes <= 64");
+  check_bf16_2d(W2, C, H, "seq_head W2");
+  check_bf16_vec(b2, C, "seq_head b2");
+  check_bf16_2d(t_out, R, H, "seq_head t");
+  check_bf16_2d(logits, R, C, "seq_head logits");
+  check_f32(partials, "partials");
+  check_f32(stats, "stats");
+  TORCH_CHECK(partials.numel() >= 4 * (int64_t)hsd::seq_head_blocks((int)R) && stats.numel() >= 4, "seq_head stats");
+  const int64_t* lab_i;
+  const float* lab_f;
+  seq_head_labels(labels, mode, R, C, &lab_i, &lab_f);
+  TORCH_CHECK(act == 0 || act == 1, "seq_head act: 0 tanh, 1 relu");
+  hsd::launch_seq_head_fwd(CBF(pre), pre.stride(0), CBF(W2), CBF(b2), lab_i, lab_f, BF(t_out), BF(logits),
+                           partials.data_ptr<float>(), stats.data_ptr<float>(), (int)R, (int)H, (int)C, (int)mode,
+                           (float)tol, (int)act, p, (uint64_t)seed, cur_stream());
+}
+
+// g fp32 [R][C] and part fp32 (>= seq_head_splits(R) · seq_head_slab(H, C)) are workspaces; dW2 / db2 are ADDED to
+void seq_head_bwd(torch::Tensor t, torch::Tensor W2, torch::Tensor logits, torch::Tensor labels, torch::Tensor stats,
+                  torch::Tensor dloss, torch::Tensor dpre, torch::Tensor g, torch::Tensor part, torch::Tensor dW2,
+                  torch::Tensor db2, int64_t mode, int64_t act, double p, int64_t seed) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.is_contiguous() && t.scalar_type() == torch::kBFloat16, "seq_head t");
+  const int64_t R = t.size(0), H = t.size(1), C = W2.size(0);
+  TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 16 && H % 8 == 0 && H >= 8 && H <= 1024 && C >= 1 && C <= 64,
+              "seq_head shape");
+  check_bf16_2d(W2, C, H, "seq_head W2");
+  check_bf16_2d(logits, R, C, "seq_head logits");
+  const int64_t* lab_i;
+  const float* lab_f;
+  seq_head_labels(labels, mode, R, C, &lab_i, &lab_f);
+  TORCH_CHECK(act == 0 || act == 1, "seq_head act: 0 tanh, 1 relu");
+  check_f32(stats, "stats");
+  check_f32(dloss, "dloss");
+  TORCH_CHECK(stats.numel() >= 4 && dloss.numel() >= 1, "seq_head stats / dloss");
+  check_bf16_2d(dpre, R, H, "dpre");
+  check_f32(g, "g");
+  check_f32(part, "part");
+  check_f32(dW2, "dW2");
+  check_f32(db2, "db2");
+  TORCH_CHECK(g.numel() >= R * C, "seq_head g");
+  TORCH_CHECK(part.numel() >= (int64_t)hsd::seq_head_splits((int)R) * hsd::seq_head_slab((int)H, (int)C) &&
+              (reinterpret_cast<uintptr_t>(part.data_ptr<float>()) & 15) == 0, "seq_head workspace");
+  TORCH_CHECK(dW2.numel() == C * H && db2.numel() == C, "seq_head grads");
+  hsd::launch_seq_head_bwd(CBF(t), CBF(W2), CBF(logits), lab_i, lab_f, stats.data_ptr<float>(),
+                           dloss.data_ptr<float>(), BF(dpre), g.data_ptr<float>(), part.data_ptr<float>(),
+                           dW2.data_ptr<float>(), db2.data_ptr<float>(), (int)R, (int)H, (int)C, (int)mode, (int)act, p,
+                           (uint64_t)seed, cur_stream());
+}
+
+int64_t seq_head_blocks(int64_t R) { return hsd::seq_head_blocks((int)R); }
+// floats of the backward's slab workspace
+int64_t seq_head_workspace(int64_t R, int64_t H, int64_t C) {
+  return (int64_t)hsd::seq_head_splits((int)R) * hsd::seq_head_slab((int)H, (int)C);
+}
+
 // C [N][K] fp32 += dy [T][N]ᵀ · x [T][K] for small T (row strides allowed; unit inner strides)
 void small_wgrad(torch::Tensor dy, torch::Tensor x, torch::Tensor C) {
   TORCH_CHECK(dy.is_cuda() && x.is_cuda() && dy.dim() == 2 && x.dim() == 2 && dy.size(0) == x.size(0), "small_wgrad");
@@ -1611,6 +1691,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cls_head_fwd", &cls_head_fwd);
   m.def("cls_head_bwd", &cls_head_bwd);
   m.def("cls_head_blocks", &cls_head_blocks);
+  m.def("seq_head_fwd", &seq_head_fwd);
+  m.def("seq_head_bwd", &seq_head_bwd);
+  m.def("seq_head_blocks", &seq_head_blocks);
+  m.def("seq_head_workspace", &seq_head_workspace);
   m.def("token_head_fwd", &token_head_fwd);
   m.def("token_head_bwd", &token_head_bwd);
   m.def("token_head_bwd_given", &token_head_bwd_given);

@@ -130,6 +130,20 @@ void launch_cls_head_fwd(const bf16_t* pre, int64_t ld_pre, const bf16_t* W2, co
 void launch_cls_head_bwd(const bf16_t* t_in, const bf16_t* W2, const bf16_t* logits, const int64_t* labels,
                          const float* stats, const float* dloss, bf16_t* dpre, float* dW2, float* db2, int R, int H,
                          int C, int act, double p, uint64_t seed, hipStream_t st);
+// seq_head.hip: the same place in the sequence-classification model for 1 <= C <= 64 and three losses. mode 0: CE,
+// labels lab_i int64 [R]; 1: BCE-with-logits, 2: MSE, labels lab_f fp32 [R][C] (a row whose first label is NaN is
+// ignored). The backward writes g fp32 [R][C] and seq_head_splits(R) slabs of seq_head_slab(H, C) floats, and adds
+// them into dW2 / db2 in split order (no atomics).
+int seq_head_blocks(int R);
+int seq_head_splits(int R);
+int64_t seq_head_slab(int H, int C);
+void launch_seq_head_fwd(const bf16_t* pre, int64_t ld_pre, const bf16_t* W2, const bf16_t* b2, const int64_t* lab_i,
+                         const float* lab_f, bf16_t* t_out, bf16_t* logits, float* partials, float* stats, int R, int H,
+                         int C, int mode, float tol, int act, double p, uint64_t seed, hipStream_t st);
+void launch_seq_head_bwd(const bf16_t* t_in, const bf16_t* W2, const bf16_t* logits, const int64_t* lab_i,
+                         const float* lab_f, const float* stats, const float* dloss, bf16_t* dpre, float* g, float* slab,
+                         float* dW2, float* db2, int R, int H, int C, int mode, int act, double p, uint64_t seed,
+                         hipStream_t st);
 // token_head.hip: fused token-classification head over every row (dropout, classifier, CE, accuracy); H % 8 == 0,
 // H <= 1024, 2 <= C <= 16. labels may be null (logits only: stats untouched). The backward writes
 // token_head_bwd_blocks(R) fp32 partial slabs of C·H + C into `part` and adds them into dW / db; dh may be null.

@@ -34,6 +34,7 @@ class ArrayDataset:
     labels: np.ndarray           # [N] int64 (or [N, S] for MLM / token classification, [N, 2] for question answering)
     token_type_ids: Optional[np.ndarray] = None  # [N, S] segment ids (question answering with BERT), else None
     span_labels: bool = False    # labels are [N, 2] (start, end) token positions, not one label per row
+    row_targets: bool = False    # labels are fp32 [N, C] row targets (--problem_type regression / multi-label)
 
     def __len__(self) -> int:
         return int(self.input_ids.shape[0])
@@ -64,6 +65,75 @@ def synthetic_classification(num_examples: int, seq_len: int, vocab_size: int, s
         ids[i, L:] = pad_id
     mask = (np.arange(seq_len)[None, :] < lengths[:, None]).astype(np.int8)
     return ArrayDataset(ids.astype(np.int32), mask, labels)
+
+
+def regression_marker_table(vocab_size: int) -> np.ndarray:
+    """The 16 marker token ids of the synthetic regression corpus: distinct, a function of ``vocab_size`` and a
+    constant only, so the train and eval splits share them (as :func:`tag_table`)."""
+    lo = 1000 if vocab_size > 4000 else 4
+    return lo + np.random.default_rng([0x5E67, int(vocab_size)]).permutation(vocab_size - lo)[:16].astype(np.int64)
+
+
+def multi_label_marker_table(vocab_size: int, num_labels: int) -> np.ndarray:
+    """The marker token id of every label of the synthetic multi-label corpus (distinct; shared by the splits)."""
+    lo = 1000 if vocab_size > 4000 else 4
+    if num_labels > vocab_size - lo:
+        raise ValueError(f"{num_labels} labels need as many marker ids; the vocabulary has {vocab_size - lo}")
+    return lo + np.random.default_rng([0x3B17, int(vocab_size), int(num_labels)]).permutation(
+        vocab_size - lo)[:num_labels].astype(np.int64)
+
+
+def _marker_free_ids(rng, shape, vocab_size: int, markers: np.ndarray) -> np.ndarray:
+    """Uniform filler tokens that are none of ``markers`` (a hit is moved to the next free id)."""
+    lo = 1000 if vocab_size > 4000 else 4
+    ids = rng.integers(lo, vocab_size, size=shape, dtype=np.int64)
+    taken = np.zeros(vocab_size, dtype=bool)
+    taken[markers] = True
+    free = np.nonzero(~taken[lo:])[0] + lo
+    hit = taken[ids]
+    ids[hit] = free[ids[hit] % free.size]
+    return ids
+
+
+def synthetic_regression(num_examples: int, seq_len: int, vocab_size: int, seed: int = 0, num_labels: int = 1,
+                         full_length: bool = False, cls_id: int = 101, sep_id: int = 102,
+                         pad_id: int = 0) -> ArrayDataset:
+    """``--problem_type regression --dataset synthetic``: one marker token, drawn from 16 fixed ids
+    (:func:`regression_marker_table`) with index ``j``, at a random interior position of a ragged ``[CLS] … [SEP]``
+    row; target ``y[c] = ((j·(2c+1)) mod 16) / 4 - 2``. ``labels`` fp32 ``[N, C]``."""
+    rng = np.random.default_rng(seed)
+    marks = regression_marker_table(vocab_size)
+    ids = _marker_free_ids(rng, (num_examples, seq_len), vocab_size, marks)
+    lengths = _ragged_lengths(rng, num_examples, seq_len, full_length)
+    j = rng.integers(0, 16, size=num_examples)
+    pos = 1 + (rng.integers(0, 1 << 30, size=num_examples) % np.maximum(lengths - 2, 1))
+    ids[np.arange(num_examples), pos] = marks[j]
+    mask = _frame(ids, lengths, cls_id % vocab_size, sep_id % vocab_size, pad_id)
+    c = np.arange(num_labels)[None, :]
+    y = ((j[:, None] * (2 * c + 1)) % 16) / 4.0 - 2.0
+    return ArrayDataset(ids.astype(np.int32), mask, y.astype(np.float32), row_targets=True)
+
+
+def synthetic_multi_label(num_examples: int, seq_len: int, vocab_size: int, seed: int = 0, num_labels: int = 6,
+                          full_length: bool = False, cls_id: int = 101, sep_id: int = 102,
+                          pad_id: int = 0) -> ArrayDataset:
+    """``--problem_type multi_label_classification --dataset synthetic``: label ``c`` has its own marker id
+    (:func:`multi_label_marker_table`) and is present independently with probability 1/4; the markers of a row go
+    to distinct interior positions, and one that finds no free position is dropped (its label is 0). ``labels`` fp32
+    ``[N, C]`` of 0 / 1."""
+    rng = np.random.default_rng(seed)
+    marks = multi_label_marker_table(vocab_size, num_labels)
+    ids = _marker_free_ids(rng, (num_examples, seq_len), vocab_size, marks)
+    lengths = _ragged_lengths(rng, num_examples, seq_len, full_length)
+    want = rng.random((num_examples, num_labels)) < 0.25
+    y = np.zeros((num_examples, num_labels), dtype=np.float32)
+    for i in range(num_examples):
+        interior = rng.permutation(np.arange(1, max(int(lengths[i]) - 1, 1)))
+        cs = np.nonzero(want[i])[0][:interior.size]
+        ids[i, interior[:cs.size]] = marks[cs]
+        y[i, cs] = 1.0
+    mask = _frame(ids, lengths, cls_id % vocab_size, sep_id % vocab_size, pad_id)
+    return ArrayDataset(ids.astype(np.int32), mask, y, row_targets=True)
 
 
 def synthetic_mlm(num_examples: int, seq_len: int, vocab_size: int, seed: int = 0, mask_id: int = 50264,
@@ -386,7 +456,26 @@ def mask_dataset_static(ds: ArrayDataset, seed: int, mlm_probability: float, mas
 
 
 # ------------------------------------------------------------------------------------------ text
-def _read_table(path: str) -> Tuple[List[str], List[int]]:
+def _row_targets(t: dict, problem_type: str, num_labels: int, path: str) -> List[List[float]]:
+    """The float targets of a csv / json table: regression reads a float ``label`` (or ``label_0..label_{C-1}``);
+    multi-label a ``labels`` list per row or ``label_0..label_{C-1}`` columns."""
+    cols = [f"label_{c}" for c in range(num_labels)]
+    if all(c in t for c in cols):
+        rows = [[float(t[c][i]) for c in cols] for i in range(len(t[cols[0]]))]
+    elif problem_type == "multi_label_classification" and "labels" in t:
+        rows = [[float(v) for v in (json.loads(x) if isinstance(x, str) else x)] for x in t["labels"]]
+    elif problem_type == "regression" and "label" in t:
+        rows = [[float(x)] for x in t["label"]]
+    else:
+        want = "a float label column" if problem_type == "regression" else "a labels list"
+        raise ValueError(f"{path}: --problem_type {problem_type} reads {want} or label_0..label_{num_labels - 1} columns")
+    bad = [i for i, r in enumerate(rows) if len(r) != num_labels]
+    if bad:
+        raise ValueError(f"{path}: row {bad[0]} has {len(rows[bad[0]])} targets, --num_labels is {num_labels}")
+    return rows
+
+
+def _read_table(path: str, problem_type: Optional[str] = None, num_labels: int = 2) -> Tuple[List[str], list]:
     ext = os.path.splitext(path)[1].lower()
     if ext == ".parquet":
         import pyarrow.parquet as pq
@@ -402,19 +491,28 @@ def _read_table(path: str) -> Tuple[List[str], List[int]]:
     else:
         raise ValueError(f"unsupported dataset file {path}")
     text_key = "text" if "text" in t else "sentence"
+    if problem_type in ("regression", "multi_label_classification"):
+        return [str(x) for x in t[text_key]], _row_targets(t, problem_type, num_labels, path)
     return [str(x) for x in t[text_key]], [int(x) for x in t["label"]]
 
 
-def load_text_split(name_or_path: str, split: str, dataset_dir: Optional[str] = None) -> Tuple[List[str], List[int]]:
-    """``split`` in {"train", "test"}; SST-2's ``validation`` serves as its test split."""
+def load_text_split(name_or_path: str, split: str, dataset_dir: Optional[str] = None,
+                    problem_type: Optional[str] = None, num_labels: int = 2) -> Tuple[List[str], list]:
+    """``split`` in {"train", "test"}; SST-2's ``validation`` serves as its test split. ``problem_type`` regression /
+    multi_label_classification: csv / tsv / json files yield float targets (``_row_targets``; rows of ``num_labels``
+    floats) instead of int labels; the other layouts hold one class per text and are refused."""
+    floats = problem_type in ("regression", "multi_label_classification")
+    if floats and name_or_path in ("imdb", "sst2"):
+        raise ValueError(f"--dataset {name_or_path} holds one class per text, not the float targets of "
+                         f"--problem_type {problem_type}")
     roots = [p for p in (name_or_path, dataset_dir, os.path.join(dataset_dir or "", name_or_path)) if p]
     for root in roots:
         if not os.path.exists(root):
             continue
         if os.path.isfile(root):
-            return _read_table(root)
+            return _read_table(root, problem_type, num_labels)
         # HF datasets save_to_disk
-        if os.path.isfile(os.path.join(root, "dataset_dict.json")):
+        if not floats and os.path.isfile(os.path.join(root, "dataset_dict.json")):
             from datasets import load_from_disk
 
             dd = load_from_disk(root)
@@ -431,12 +529,12 @@ def load_text_split(name_or_path: str, split: str, dataset_dir: Optional[str] = 
         if cands:
             texts, labels = [], []
             for c in cands:
-                t, l = _read_table(c)
+                t, l = _read_table(c, problem_type, num_labels)
                 texts += t
                 labels += l
             return texts, labels
         raw = os.path.join(root, split)
-        if os.path.isdir(os.path.join(raw, "pos")):  # aclImdb layout
+        if not floats and os.path.isdir(os.path.join(raw, "pos")):  # aclImdb layout
             texts, labels = [], []
             for lab, sub in ((0, "neg"), (1, "pos")):
                 for f in sorted(glob.glob(os.path.join(raw, sub, "*.txt"))):
@@ -454,4 +552,7 @@ def tokenize_dataset(tokenizer, texts: List[str], labels: List[int], max_length:
         enc = tokenizer.encode_batch(texts[i:i + chunk], max_length)
         ids.append(enc["input_ids"])
         mask.append(enc["attention_mask"])
+    if len(labels) and isinstance(labels[0], (list, tuple, np.ndarray)):  # float row targets (--problem_type)
+        return ArrayDataset(np.concatenate(ids), np.concatenate(mask), np.asarray(labels, dtype=np.float32),
+                            row_targets=True)
     return ArrayDataset(np.concatenate(ids), np.concatenate(mask), np.asarray(labels, dtype=np.int64))

@@ -49,9 +49,15 @@ class BatchLoader:
         pad = ix < 0  # ShardSampler(mark_padding=True): repeats that only even out the ranks
         if pad.any():
             ix = np.where(pad, -ix - 1, ix)
-        labels = self.ds.labels[ix].astype(np.int64)
-        if pad.any():
-            labels[pad] = -100  # ignored by the loss and by the metric meter
+        row_targets = bool(getattr(self.ds, "row_targets", False))
+        if row_targets:  # fp32 [B, C] targets (--problem_type regression / multi-label): NaN marks an ignored row
+            labels = self.ds.labels[ix].astype(np.float32)
+            if pad.any():
+                labels[pad] = np.nan
+        else:
+            labels = self.ds.labels[ix].astype(np.int64)
+            if pad.any():
+                labels[pad] = -100  # ignored by the loss and by the metric meter
         ints = {}
         tt = getattr(self.ds, "token_type_ids", None)
         if self.pack:
@@ -60,6 +66,8 @@ class BatchLoader:
                 extra["token_type_ids"] = tt[ix]
             if getattr(self.ds, "span_labels", False):
                 extra["span_labels"] = True
+            if row_targets:
+                extra["row_targets"] = True
             pk = pack_batch(self.ds.input_ids[ix], self.ds.attention_mask[ix], labels, **self.pack_rule, **extra)
             ints = {k: pk.pop(k) for k in ("max_seqlen", "real_tokens")}
             b = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in pk.items()}

@@ -21,7 +21,7 @@ import numpy as np
 
 def pack_batch(input_ids: np.ndarray, attention_mask: np.ndarray, labels: np.ndarray, *, pad_id: int, pos_base: int,
                pad_pos: int, row_multiple: int = 256, token_type_ids: Optional[np.ndarray] = None,
-               span_labels: bool = False) -> Dict[str, object]:
+               span_labels: bool = False, row_targets: bool = False) -> Dict[str, object]:
     """Pack a right-padded ``[B, S]`` batch.
 
     ``position_ids[t] = pos_base + i`` for the ``i``-th token of its sequence (BERT / DistilBERT: ``pos_base = 0``,
@@ -29,7 +29,9 @@ def pack_batch(input_ids: np.ndarray, attention_mask: np.ndarray, labels: np.nda
     ``Embeddings.position_ids`` yields for a prefix mask). ``labels``: ``[B]`` (classification, returned as is) or
     ``[B, S]`` (masked LM, packed to ``[T]`` with -100 on the dead rows). ``span_labels=True``: ``labels`` are the
     ``[B, 2]`` (start, end) positions of question answering, relative to the sequence's first token and so the same
-    numbers packed: returned as they are. ``token_type_ids [B, S]``, when given, are packed to ``[1, T]`` (0 on the
+    numbers packed: returned as they are. ``row_targets=True``: ``labels`` are the fp32 ``[B, C]`` row targets of
+    ``--problem_type`` regression / multi-label (one row per sequence, never ``[B, S]`` token labels, whatever
+    ``C`` is): returned as they are. ``token_type_ids [B, S]``, when given, are packed to ``[1, T]`` (0 on the
     dead rows) and returned under that key.
 
     Returns ``input_ids [1, T]``, ``position_ids [1, T]`` (int64), ``cu_seqlens [B+1]`` (int32), ``labels`` and the
@@ -61,6 +63,9 @@ def pack_batch(input_ids: np.ndarray, attention_mask: np.ndarray, labels: np.nda
     if span_labels:
         if lab.shape != (B, 2):
             raise ValueError(f"pack_batch: span labels {lab.shape} must be [B, 2] = {(B, 2)}")
+    elif row_targets:
+        if lab.ndim != 2 or lab.shape[0] != B:
+            raise ValueError(f"pack_batch: row targets {lab.shape} must be [B, C] with B = {B}")
     elif lab.ndim == 2:
         if lab.shape != ids.shape:
             raise ValueError(f"pack_batch: per-token labels {lab.shape} do not match input_ids {ids.shape}")

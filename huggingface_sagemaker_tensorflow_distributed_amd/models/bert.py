@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..ops.rng import DropoutSeeds
-from .config import ModelConfig
+from .config import ModelConfig, check_problem_type
 from .encoder import EncoderLayer, _param, layer_hf_names
 
 
@@ -203,13 +203,20 @@ class _Base(nn.Module):
 
 
 class TransformerForSequenceClassification(_Base):
-    """BertForSequenceClassification / RobertaForSequenceClassification / DistilBertForSequenceClassification."""
+    """BertForSequenceClassification / RobertaForSequenceClassification / DistilBertForSequenceClassification.
+
+    ``cfg.problem_type`` picks the loss as HF's ``config.problem_type`` does: ``None`` /
+    ``"single_label_classification"`` cross-entropy on int labels ``[B]``; ``"multi_label_classification"``
+    BCE-with-logits and ``"regression"`` MSE on fp32 labels ``[B, num_labels]`` (``ops.reference.seq_loss``). Nothing
+    reads a device value on the host on any of them."""
 
     arch_suffix = "ForSequenceClassification"
 
     def __init__(self, cfg: ModelConfig):
         super().__init__(cfg)
         H, L = cfg.hidden_size, cfg.num_labels
+        check_problem_type(cfg.problem_type)
+        self.regression_tolerance = 0.5  # --regression_tolerance: |z - y| <= this on every target scores a hit
         if cfg.model_type == "bert":
             self.pooler_weight, self.pooler_bias = _param(H, H), _param(H)
         else:  # roberta classifier.dense / distilbert pre_classifier
@@ -257,7 +264,11 @@ class TransformerForSequenceClassification(_Base):
             w1, b1, act, p_in, seed_in = self.head_dense_weight, self.head_dense_bias, "relu", 0.0, 0
         seed = self.rng.next() if p else 0
         # logits without labels, else (loss, logits)
-        return ops.cls_head(h, w1, b1, self.classifier_weight, self.classifier_bias, labels, act, p_in, seed_in, p, seed)
+        if c.problem_type is None:
+            return ops.cls_head(h, w1, b1, self.classifier_weight, self.classifier_bias, labels, act, p_in, seed_in, p,
+                                seed)
+        return ops.cls_head(h, w1, b1, self.classifier_weight, self.classifier_bias, labels, act, p_in, seed_in, p, seed,
+                            problem_type=c.problem_type, tol=self.regression_tolerance)
 
 
 class TransformerForTokenClassification(_Base):
@@ -490,7 +501,14 @@ class RobertaForMaskedLM(_Base):
         return logits.view(B, S, -1)
 
 
-def build_model(cfg: ModelConfig, task: str = "sequence-classification", seed: Optional[int] = 0) -> _Base:
+def build_model(cfg: ModelConfig, task: str = "sequence-classification", seed: Optional[int] = 0,
+                problem_type: Optional[str] = None) -> _Base:
+    """``problem_type``: sets ``cfg.problem_type`` of a sequence-classification model (models/config.py); any other
+    task refuses it."""
+    if problem_type is not None:
+        if task not in ("sequence-classification", "seq-cls"):
+            raise ValueError(f"problem_type={problem_type!r} is for task sequence-classification, not {task!r}")
+        cfg = cfg.replace(problem_type=check_problem_type(problem_type))
     if task in ("sequence-classification", "seq-cls"):
         m = TransformerForSequenceClassification(cfg)
     elif task in ("masked-lm", "mlm"):

@@ -16,6 +16,15 @@ from dataclasses import dataclass, field
 from typing import Any, Dict, Optional
 
 
+PROBLEM_TYPES = ("single_label_classification", "multi_label_classification", "regression")
+
+
+def check_problem_type(problem_type: Optional[str]) -> Optional[str]:
+    if problem_type is not None and problem_type not in PROBLEM_TYPES:
+        raise ValueError(f"problem_type {problem_type!r}: one of {PROBLEM_TYPES} or None")
+    return problem_type
+
+
 @dataclass
 class ModelConfig:
     model_type: str = "bert"  # bert | roberta | distilbert
@@ -36,6 +45,10 @@ class ModelConfig:
     bos_token_id: Optional[int] = None
     eos_token_id: Optional[int] = None
     num_labels: int = 2
+    # HF config.problem_type of a sequence-classification model: None (= single-label cross-entropy, also for one
+    # label: it is never inferred from the labels' dtype), "single_label_classification",
+    # "multi_label_classification" (BCE-with-logits) or "regression" (MSE)
+    problem_type: Optional[str] = None
     tie_word_embeddings: bool = True
     # distilbert-only
     sinusoidal_pos_embds: bool = False
@@ -69,6 +82,8 @@ class ModelConfig:
         }
         if architecture:
             common["architectures"] = [architecture]
+        if self.problem_type is not None:
+            common["problem_type"] = self.problem_type
         if mt == "distilbert":
             common.update({
                 "dim": self.hidden_size, "n_layers": self.num_hidden_layers,
@@ -115,7 +130,7 @@ class ModelConfig:
                 pad_token_id=d.get("pad_token_id", 0), num_labels=nl,
                 sinusoidal_pos_embds=d.get("sinusoidal_pos_embds", False),
                 seq_classif_dropout=d.get("seq_classif_dropout", 0.2), qa_dropout=d.get("qa_dropout", 0.1),
-                id2label=labels,
+                id2label=labels, problem_type=check_problem_type(d.get("problem_type")),
             )
         return cls(
             model_type=mt, vocab_size=d.get("vocab_size", 30522), hidden_size=d.get("hidden_size", 768),
@@ -129,7 +144,7 @@ class ModelConfig:
             type_vocab_size=d.get("type_vocab_size", 2), initializer_range=d.get("initializer_range", 0.02),
             layer_norm_eps=d.get("layer_norm_eps", 1e-12), pad_token_id=d.get("pad_token_id", 0),
             bos_token_id=d.get("bos_token_id"), eos_token_id=d.get("eos_token_id"),
-            num_labels=nl, id2label=labels,
+            num_labels=nl, id2label=labels, problem_type=check_problem_type(d.get("problem_type")),
         )
 
 

@@ -110,10 +110,12 @@ def read_checkpoint(path: str) -> Optional[Dict[str, torch.Tensor]]:
 
 
 def from_pretrained(name_or_path: str, task: str = "sequence-classification", num_labels: Optional[int] = None,
-                    seed: Optional[int] = 0) -> _Base:
+                    seed: Optional[int] = 0, problem_type: Optional[str] = None) -> _Base:
+    """``problem_type``: overrides the ``problem_type`` of the config (sequence-classification only)."""
     cfg = resolve_config(name_or_path, num_labels=num_labels)
     # the command line's --task question-answering is build_model's "span-extraction"
-    model = build_model(cfg, task="span-extraction" if task == "question-answering" else task, seed=seed)
+    model = build_model(cfg, task="span-extraction" if task == "question-answering" else task, seed=seed,
+                        problem_type=problem_type)
     model.weights_source = "random-init"  # what the run's provenance record reports
     if os.path.isdir(name_or_path):
         sd = read_checkpoint(name_or_path)

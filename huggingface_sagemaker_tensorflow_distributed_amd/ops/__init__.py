@@ -11,7 +11,8 @@
 does so for fp32 tensors only. ``HSD_CLS_ROWS_ONLY=0`` keeps the last encoder layer of a sequence-classification
 model on all rows (:func:`attn_block_cls`; tests and same-process A/Bs). ``HSD_TOKEN_HEAD=composed`` runs the
 token-classification head (:func:`token_head`) as composed ops instead of its fused kernels (A/B measurements);
-``HSD_QA_HEAD=composed`` does the same for the question-answering head (:func:`qa_head`).
+``HSD_QA_HEAD=composed`` does the same for the question-answering head (:func:`qa_head`), ``HSD_SEQ_HEAD=composed``
+for the sequence-level head of ``--problem_type`` (:func:`cls_head` beyond single-label heads of at most 4 classes).
 """
 from __future__ import annotations
 
@@ -32,6 +33,9 @@ TOKEN_HEAD_FUSED = os.environ.get("HSD_TOKEN_HEAD", "fused").strip().lower() != 
 # HSD_QA_HEAD=composed: the question-answering head as dropout -> linear -> masked span cross-entropy in torch instead
 # of the fused kernels of csrc/kernels/qa_head.hip (A/B measurements)
 QA_HEAD_FUSED = os.environ.get("HSD_QA_HEAD", "fused").strip().lower() != "composed"
+# HSD_SEQ_HEAD=composed: the sequence-level head of --problem_type (and of single-label heads with 5..64 classes) as
+# composed ops + reference.seq_loss instead of the fused kernels of csrc/kernels/seq_head.hip (A/B measurements)
+SEQ_HEAD_FUSED = os.environ.get("HSD_SEQ_HEAD", "fused").strip().lower() != "composed"
 
 
 def _hip(x: torch.Tensor) -> bool:
@@ -254,17 +258,32 @@ def cross_entropy(logits, labels):
     return _ref.cross_entropy(logits, labels)
 
 
-def cls_head(h, w1, b1, w2, b2, labels, act: str, p_in: float, seed_in: int, p: float, seed: int):
+def cls_head(h, w1, b1, w2, b2, labels, act: str, p_in: float, seed_in: int, p: float, seed: int, *,
+             problem_type: Optional[str] = None, tol: float = 0.5):
     """Classification head on the first token of ``h`` [B, S, H] (+ the loss when ``labels`` is given). ``S`` is 1 when
     the encoder already pruned its last layer to the first-token rows (``Encoder.forward(first_token_only=True)``).
 
     Returns ``logits`` without labels, else ``(loss, logits)`` with the argmax-hit count on ``loss._hsd_correct``
     and the fused {mean loss, hits, rows, loss sum} on ``loss._hsd_stats`` (HIP path). On GPUs the dense layer runs on gemm2 and everything after it (activation, dropout, classifier, CE,
     accuracy) in one fused kernel per direction (csrc/kernels/cls_head.hip); the first-token rows are read in place
-    (no gather copy) and their gradient is written straight into the zeroed ``dh`` rows."""
+    (no gather copy) and their gradient is written straight into the zeroed ``dh`` rows.
+
+    ``problem_type`` (HF ``config.problem_type``; ``None`` = single-label): ``"multi_label_classification"`` and
+    ``"regression"`` take fp32 labels ``[B, C]`` (a row whose first label is NaN is ignored) and return the loss of
+    ``reference.seq_loss`` with its {mean loss, hits, n, loss sum} on ``loss._hsd_stats`` on every path; ``tol`` is
+    the regression hit tolerance. bf16 GPU tensors within ``hip.seq_head_ok`` (H % 8 == 0, H <= 1024, C <= 64) run
+    csrc/kernels/seq_head.hip for both and for single-label heads of 5..64 classes, unless ``HSD_SEQ_HEAD=composed``;
+    everything else runs the composed ops with the same seeds and so the same masks."""
+    if problem_type not in (None,) + _ref.PROBLEM_TYPES:
+        raise ValueError(f"problem_type {problem_type!r}: one of {_ref.PROBLEM_TYPES} or None")
+    single = problem_type in (None, "single_label_classification")
     mod = _hipmod() if _hip(h) else _hip32mod() if _hip32(h) else None
-    if mod is not None and labels is not None and mod.cls_head_ok(h, w1, w2):
+    if single and mod is not None and labels is not None and mod.cls_head_ok(h, w1, w2):
         loss, logits, stats = mod.cls_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed)
+        return _with_stats(loss, stats), logits
+    if _hip(h) and SEQ_HEAD_FUSED and labels is not None and _hipmod().seq_head_ok(h, w1, w2):
+        loss, logits, stats = _hipmod().seq_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed,
+                                                 problem_type, tol)
         return _with_stats(loss, stats), logits
     x = h[:, 0].contiguous()
     if _hip(h) or _hip32(h):
@@ -277,7 +296,10 @@ def cls_head(h, w1, b1, w2, b2, labels, act: str, p_in: float, seed_in: int, p: 
         logits = _ref.cls_head(x, w1, b1, w2, b2, act, p_in, seed_in, p, seed, True)
     if labels is None:
         return logits
-    return cross_entropy(logits, labels), logits
+    if single and problem_type is None:
+        return cross_entropy(logits, labels), logits
+    loss, stats = _ref.seq_loss(logits, labels, problem_type, tol)
+    return _with_stats(loss, stats), logits
 
 
 def token_head(h2d, w, b, labels, p: float, seed: int):

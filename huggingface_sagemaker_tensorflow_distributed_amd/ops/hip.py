@@ -1392,6 +1392,88 @@ def cls_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed):
     return _ClsHead.apply(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed)
 
 
+# ------------------------------------------------------------------------------------------ sequence-level head
+_SEQ_MODE = {None: 0, "single_label_classification": 0, "multi_label_classification": 1, "regression": 2}
+
+
+def seq_head_ok(h, w1, w2) -> bool:
+    """What csrc/kernels/seq_head.hip takes: cls_head's shapes (bf16 [B, S, H], H % 8 == 0, H <= 1024) with
+    1 <= C <= 64."""
+    H = h.shape[-1]
+    return (h.dtype == torch.bfloat16 and w2.dtype == torch.bfloat16 and h.dim() == 3 and H % 8 == 0 and 8 <= H <= 1024
+            and 1 <= w2.shape[0] <= 64 and w2.shape[1] == H and w1.shape[0] == H and (h.shape[1] * H) % 8 == 0
+            and 1 <= h.shape[0] < (1 << 31) - 16)
+
+
+class _SeqHead(torch.autograd.Function):
+    """_ClsHead with the kernels of seq_head.hip after the dense GEMM: CE (int64 labels [B]), BCE-with-logits or MSE
+    (fp32 labels [B, C]; a row whose first label is NaN is ignored) for up to 64 classes. Backward: the fused g / dpre
+    kernel, the classifier weight gradient over row splits (fp32 slabs in the shared workspace) and its in-order
+    reducer into main_grad (no atomics), then the dense layer's colsum / wgrad / dgrad as in _ClsHead."""
+
+    @staticmethod
+    def forward(ctx, h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed, mode, tol):
+        B, S, H = h.shape
+        C = w2.shape[0]
+        x = h.reshape(B, S * H)[:, :H]  # the [CLS] rows, read in place (row stride S*H)
+        if p_in > 0:
+            x = dropout(x.contiguous(), p_in, seed_in)
+        pre, _ = _dense_fwd(x, w1, b1, bf16_only=False)
+        t = torch.empty_like(pre)
+        logits = torch.empty((B, C), dtype=h.dtype, device=h.device)
+        nblk = _C.seq_head_blocks(B)
+        partials = torch.empty(nblk * 4, dtype=torch.float32, device=h.device)
+        stats = torch.empty(4, dtype=torch.float32, device=h.device)
+        if mode == 0:
+            lab = labels.reshape(B).contiguous().long()
+        else:
+            lab = labels.to(torch.float32).reshape(B, C).contiguous()
+        w2c, b2c = w2.contiguous(), b2.contiguous()
+        _C.seq_head_fwd(pre, w2c, b2c, lab, t, logits, partials, stats, mode, float(tol), _ACT[act], float(p), _s64(seed))
+        ctx.save_for_backward(x, w1, b1, t, w2, b2, logits, lab, stats)
+        ctx.cfg = (act, float(p_in), seed_in, float(p), seed, B, S, H, mode)
+        ctx.mark_non_differentiable(logits, stats)
+        ctx.set_materialize_grads(False)  # no zero-filled gradients for the non-differentiable outputs
+        return stats[0], logits, stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits, _dstats):
+        x, w1, b1, t, w2, b2, logits, lab, stats = ctx.saved_tensors
+        act, p_in, seed_in, p, seed, B, S, H, mode = ctx.cfg
+        C = w2.shape[0]
+        g_w1, g_b1, g_w2, g_b2 = _Grad(w1), _Grad(b1), _Grad(w2), _Grad(b2)
+        dpre = torch.empty_like(t)
+        nws = _C.seq_head_workspace(B, H, C)
+        ws = _workspace(nws + B * C, t.device)  # the slabs (a multiple of 4 floats each), then g [B][C]
+        _C.seq_head_bwd(t, w2.contiguous(), logits, lab, stats, _dloss1(dloss, t.device), dpre, ws[nws:nws + B * C],
+                        ws[:nws], g_w2.buf.view(-1), g_b2.buf.view(-1), mode, _ACT[act], p, _s64(seed))
+        r_w2, r_b2 = g_w2.done(), g_b2.done()
+        _C.colsum(dpre, g_b1.buf)
+        r_b1 = g_b1.done()
+        _dense_wgrad_(g_w1, dpre, x, bf16_only=False, small_rows=True)
+        r_w1 = g_w1.done()
+        dh = None
+        if ctx.needs_input_grad[0]:
+            dh = torch.empty((B, S, H), dtype=dpre.dtype, device=dpre.device)
+            _C.memset0(dh)
+            dst = dh.reshape(B, S * H)[:, :H]  # the [CLS] rows of dh (row stride S*H)
+            if p_in > 0:
+                dx = _dense_dgrad(dpre, w1, bf16_only=False)
+                _C.dropout(dx, dx, p_in, _s64(seed_in))
+                dst.copy_(dx)
+            elif _C.gemm2_supported(0, 1, EPI_STORE, B, H, H):
+                _C.gemm2(dpre, w1, dst, 0, 1, EPI_STORE, None, None, None, 0.0, 0, 0, None, None)  # reads W1 as is
+            else:
+                dst.copy_(torch.mm(dpre, w1))
+        return dh, r_w1, r_b1, r_w2, r_b2, None, None, None, None, None, None, None, None
+
+
+def seq_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed, problem_type=None, tol=0.5):
+    """(loss, logits, stats) of the fused sequence-level head (labels required); stats = fp32 {mean loss, hits, rows
+    scored, loss sum} as ``reference.seq_loss`` defines them."""
+    return _SeqHead.apply(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed, _SEQ_MODE[problem_type], float(tol))
+
+
 # ------------------------------------------------------------------------------------------ token-classification head
 def token_head_ok(h2d, w) -> bool:
     """What csrc/kernels/token_head.hip takes: bf16 rows [R, H] with H % 8 == 0, H <= 1024, and 2 <= C <= 16."""

@@ -156,6 +156,56 @@ def cls_head(x, w1, b1, w2, b2, act: str, p_in: float, seed_in: int, p: float, s
     return F.linear(h, w2, b2)
 
 
+PROBLEM_TYPES = ("single_label_classification", "multi_label_classification", "regression")
+
+
+def seq_loss(logits, labels, problem_type: Optional[str] = None, tol: float = 0.5):
+    """Loss and metric of the sequence-level head on ``logits`` [B, C] (HF ``*ForSequenceClassification`` with
+    ``config.problem_type``) -> ``(loss, stats)``, ``stats`` = fp32 {mean loss, hits, n, loss sum}.
+
+    * ``None`` / ``"single_label_classification"``: labels int [B]; CE over the rows whose label is not -100;
+      hits = first-maximum argmax == label.
+    * ``"multi_label_classification"``: labels float [B, C] in [0, 1]; per element
+      ``max(z,0) - z·y + log1p(exp(-|z|))`` (``BCEWithLogitsLoss``); hits = rows with ``(z > 0) == (y > 0.5)`` for
+      every label (subset accuracy).
+    * ``"regression"``: labels float [B, C] ([B] when C = 1); per element ``(z - y)²`` (``MSELoss``); hits = rows with
+      ``|z - y| <= tol`` for every target.
+
+    A float-label row whose FIRST label is NaN is ignored. ``n`` counts the other rows; the float losses are
+    ``Σ_valid rows Σ_c term / (max(n, 1)·C)``: 0, not NaN, with zero gradients, when every row is ignored."""
+    z = logits.float()
+    if problem_type in (None, "single_label_classification"):
+        lab = labels.reshape(-1).long()
+        lsum = F.cross_entropy(z, lab, ignore_index=-100, reduction="sum")
+        with torch.no_grad():
+            ok = lab.ne(-100)
+            hits = ((z.argmax(dim=-1) == lab) & ok).sum().to(torch.float32)
+    elif problem_type in ("multi_label_classification", "regression"):
+        C = z.shape[-1]
+        y = labels.to(torch.float32).reshape(z.shape[0], C)
+        ok = ~torch.isnan(y[:, 0])
+        y = torch.where(ok.unsqueeze(1), y, torch.zeros_like(y))  # no NaN reaches the graph of an ignored row
+        if problem_type == "regression":
+            term = (z - y) ** 2
+            with torch.no_grad():
+                good = ((z - y).abs() <= tol).all(dim=-1)
+        else:
+            term = z.clamp(min=0) - z * y + torch.log1p(torch.exp(-z.abs()))
+            with torch.no_grad():
+                good = ((z > 0) == (y > 0.5)).all(dim=-1)
+        lsum = (term * ok.unsqueeze(1).to(term.dtype)).sum() / C
+        with torch.no_grad():
+            hits = (good & ok).sum().to(torch.float32)
+    else:
+        raise ValueError(f"problem_type {problem_type!r}: one of {PROBLEM_TYPES} or None")
+    with torch.no_grad():
+        n = ok.sum().to(torch.float32)
+    loss = lsum / n.clamp(min=1.0)
+    with torch.no_grad():
+        stats = torch.stack([loss.detach().float(), hits, n, lsum.detach().float()])
+    return loss, stats
+
+
 def token_head(h2d, w, b, labels, p: float, seed: int, training: bool = True):
     """Token-classification head on every row of ``h2d`` [R, H] (HF ``*ForTokenClassification``):
     ``logits = dropout(h) Wᵀ + b`` [R, C]; the dropout site is the flat ``[R, H]`` buffer. With ``labels`` [R]

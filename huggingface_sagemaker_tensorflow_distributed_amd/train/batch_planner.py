@@ -94,6 +94,10 @@ def _probe_peak(model, store, cfg, batch: int, seq_len: int, device) -> int:
         labels = torch.randint(0, max(2, cfg.num_labels), (batch, seq_len), generator=g)
         labels[:, ::4] = -100
         labels = labels.to(device)
+    elif getattr(cfg, "problem_type", None) in ("regression", "multi_label_classification") \
+            and model.__class__.__name__ == "TransformerForSequenceClassification":
+        # fp32 row targets [B, C]
+        labels = torch.rand((batch, cfg.num_labels), generator=g).to(device)
     elif model.__class__.__name__ == "TransformerForQuestionAnswering":
         # span labels [B, 2] = (start, end) token positions
         start = torch.randint(0, max(1, seq_len - 4), (batch, 1), generator=g)

@@ -123,6 +123,26 @@ def _datasets(args, cfg, tokenizer, max_len: int):
         raise ValueError("--dataset conll holds per-token tags (--task token-classification)")
     if args.dataset == "synthetic-bigram":
         raise ValueError("--dataset synthetic-bigram is a masked-lm corpus (--task masked-lm)")
+    ptype = getattr(cfg, "problem_type", None)
+    if ptype in ("regression", "multi_label_classification"):
+        if args.dataset == "synthetic":
+            make = hdata.synthetic_regression if ptype == "regression" else hdata.synthetic_multi_label
+            kw = {"num_labels": cfg.num_labels, "pad_id": cfg.pad_token_id}
+            if cfg.model_type == "roberta":
+                kw.update(cls_id=cfg.bos_token_id if cfg.bos_token_id is not None else 0,
+                          sep_id=cfg.eos_token_id if cfg.eos_token_id is not None else 2)
+            return (make(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed, **kw),
+                    make(n_eval or 512, max_len, cfg.vocab_size, seed=args.seed + 1, **kw))
+        if args.dataset in ("imdb", "sst2"):
+            raise ValueError(_PTYPE_DATASETS.format(ptype, args.dataset))
+        out = []
+        for split, n in (("train", n_train), ("test", n_eval)):
+            texts, labels = hdata.load_text_split(args.dataset, split, args.dataset_dir, problem_type=ptype,
+                                                  num_labels=cfg.num_labels)
+            if n:
+                texts, labels = texts[:n], labels[:n]
+            out.append(hdata.tokenize_dataset(tokenizer, texts, labels, max_len))
+        return out[0], out[1]
     if args.dataset == "synthetic":
         tr = hdata.synthetic_classification(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed,
                                             num_labels=cfg.num_labels)
@@ -140,6 +160,8 @@ def _datasets(args, cfg, tokenizer, max_len: int):
     return tr, te
 
 
+_PTYPE_DATASETS = ("--problem_type {} needs float targets: --dataset synthetic or local csv / json files "
+                   "(--dataset_dir); --dataset {} holds one class per text")
 _QA_DATASETS = ("--task question-answering trains on --dataset synthetic or squad (start / end positions); "
                 "--dataset {} holds no answer spans")
 
@@ -193,6 +215,26 @@ def _provenance(args, model, rank: int, n_train: int, n_eval: int, batch_plan=No
         info["metric"] = ("loss and exact match of the best (start, end) token span over the windows with both "
                           "labels valid (not text-level EM / F1)")
         logger.info("question-answering corpus: %s; max_answer_length %d", info["corpus"], info["max_answer_length"])
+    ptype = getattr(model.cfg, "problem_type", None)
+    if ptype is not None and getattr(args, "task", "sequence-classification") == "sequence-classification":
+        info["problem_type"] = ptype
+        info["num_labels"] = int(model.cfg.num_labels)
+        if ptype == "regression":
+            info["regression_tolerance"] = float(getattr(model, "regression_tolerance", 0.5))
+            if synthetic:
+                info["corpus"] = ("synthetic regression corpus (one of 16 marker tokens, index j, at a random interior "
+                                  "position; y[c] = ((j(2c+1)) mod 16)/4 - 2; ragged lengths)")
+            info["metric"] = ("MSE loss; accuracy = rows with |prediction - target| <= regression_tolerance on every "
+                              "target (not Pearson / Spearman)")
+        elif ptype == "multi_label_classification":
+            if synthetic:
+                info["corpus"] = ("synthetic multi-label corpus (one marker token per label, each present with "
+                                  "probability 1/4 at distinct interior positions; ragged lengths)")
+            info["metric"] = ("BCE-with-logits loss; accuracy = subset accuracy, rows with every label right at "
+                              "threshold 0 (not F1)")
+        else:
+            info["metric"] = "cross-entropy loss and argmax accuracy"
+        logger.info("sequence-classification problem_type %s; %d labels; %s", ptype, info["num_labels"], info["metric"])
     if batch_plan is not None:
         info["auto_batch"] = batch_plan.as_dict()
     if synthetic or weights == "random-init":
@@ -229,13 +271,23 @@ def build(args, mode: str):
                          f"--dataset {args.dataset} holds one label per text")
     if task == "question-answering" and args.dataset not in ("synthetic", "squad"):
         raise ValueError(_QA_DATASETS.format(args.dataset))
+    ptype = getattr(args, "problem_type", None)
+    if ptype is not None and task != "sequence-classification":
+        raise ValueError(f"--problem_type {ptype} is valid only with --task sequence-classification, not --task {task}")
+    if ptype in ("regression", "multi_label_classification") and args.dataset in ("imdb", "sst2"):
+        raise ValueError(_PTYPE_DATASETS.format(ptype, args.dataset))
     tags = _conll_tags(args)
     if tags is not None:
         if args.num_labels != len(tags):
             logger.info("--dataset conll: %d tags %s; --num_labels %d -> %d", len(tags), tags, args.num_labels, len(tags))
         args.num_labels = len(tags)
     model = from_pretrained(args.model_name_or_path or "bert-base-uncased", task=task, num_labels=args.num_labels,
-                            seed=args.seed)
+                            seed=args.seed, problem_type=ptype)
+    if task == "sequence-classification":
+        tol = float(getattr(args, "regression_tolerance", 0.5))
+        if not tol >= 0.0:
+            raise ValueError(f"--regression_tolerance {tol} must be >= 0")
+        model.regression_tolerance = tol
     if tags is not None:
         model.cfg.id2label = {str(i): t for i, t in enumerate(tags)}  # config.json id2label / label2id
     model.to(dev)

@@ -145,6 +145,16 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
                         "per token (NER / POS tagging; --dataset synthetic or conll, --num_labels follows the tag list "
                         "of a CoNLL directory); question-answering: extractive start / end span prediction "
                         "(--dataset synthetic or squad)")
+    g.add_argument("--problem_type", choices=["single_label_classification", "multi_label_classification",
+                                              "regression"], default=None,
+                   help="sequence-classification only (HF config.problem_type; default single-label cross-entropy on "
+                        "int labels): multi_label_classification = BCE-with-logits on --num_labels 0/1 targets, "
+                        "accuracy = rows with every label right (subset accuracy); regression = MSE on --num_labels "
+                        "float targets, accuracy = rows within --regression_tolerance on every target. --dataset "
+                        "synthetic or local csv / json files with float targets; imdb / sst2 are refused")
+    g.add_argument("--regression_tolerance", type=float, default=0.5,
+                   help="--problem_type regression: a row scores a hit when |prediction - target| <= this on every "
+                        "target")
     g.add_argument("--max_answer_length", type=int, default=30,
                    help="question-answering: the longest span (in tokens) the best-span search returns")
     g.add_argument("--doc_stride", type=int, default=128,
