@@ -1095,8 +1095,15 @@ void gemm2_on(int64_t stream_ptr, torch::Tensor A, torch::Tensor B, torch::Tenso
 // logits [R, V] (bf16 | fp32), labels int64 [R] (-100 = ignore); stats fp32 [2] += {Σ loss, correct};
 // dlogits (optional, same dtype/shape) = (softmax - onehot) / n_valid
 // logits [rows][ld] (unit inner stride), the first V columns scored (V = 0: all); dlogits same shape / strides
+// label_smoothing eps in [0, 1): the target is (1-eps)·onehot + eps/V over the V real classes; 0 is the plain CE
+static float check_smoothing(double eps, const char* what) {
+  TORCH_CHECK(eps >= 0.0 && eps < 1.0, what, ": 0 <= label_smoothing < 1");
+  return (float)eps;
+}
+
 void xent(torch::Tensor logits, torch::Tensor labels, c10::optional<torch::Tensor> dlogits, torch::Tensor stats,
-          torch::Tensor n_valid, int64_t V) {
+          torch::Tensor n_valid, int64_t V, double label_smoothing) {
+  const float eps = check_smoothing(label_smoothing, "xent");
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "xent logits");
   const bool bf = logits.scalar_type() == torch::kBFloat16;
   TORCH_CHECK(bf || logits.scalar_type() == torch::kFloat32, "xent logits dtype");
@@ -1116,7 +1123,7 @@ void xent(torch::Tensor logits, torch::Tensor labels, c10::optional<torch::Tenso
     dl = dlogits->data_ptr();
   }
   hsd::launch_xent(logits.data_ptr(), bf, labels.data_ptr<int64_t>(), dl, stats.data_ptr<float>(),
-                   n_valid.data_ptr<float>(), (int)logits.size(0), (int)V, ld, cur_stream());
+                   n_valid.data_ptr<float>(), (int)logits.size(0), (int)V, ld, cur_stream(), eps);
 }
 
 // ---- argument checks shared by the fused task heads (cls_head.hip, token_head.hip, qa_head.hip)
@@ -1202,7 +1209,9 @@ static void seq_head_labels(const c10::optional<torch::Tensor>& labels, int64_t 
 
 void seq_head_fwd(torch::Tensor pre, torch::Tensor W2, torch::Tensor b2, c10::optional<torch::Tensor> labels,
                   torch::Tensor t_out, torch::Tensor logits, torch::Tensor partials, torch::Tensor stats, int64_t mode,
-                  double tol, int64_t act, double p, int64_t seed) {
+                  double tol, int64_t act, double p, int64_t seed, double label_smoothing) {
+  const float eps = check_smoothing(label_smoothing, "seq_head");
+  TORCH_CHECK(eps == 0.f || mode == 0, "seq_head: label_smoothing is for mode 0 (CE) only");
   TORCH_CHECK(pre.is_cuda() && pre.dim() == 2 && pre.stride(1) == 1 && pre.stride(0) % 8 == 0 &&
               pre.scalar_type() == torch::kBFloat16, "seq_head pre");
   const int64_t R = pre.size(0), H = pre.size(1), C = W2.size(0);
@@ -1221,13 +1230,15 @@ void seq_head_fwd(torch::Tensor pre, torch::Tensor W2, torch::Tensor b2, c10::op
   TORCH_CHECK(act == 0 || act == 1, "seq_head act: 0 tanh, 1 relu");
   hsd::launch_seq_head_fwd(CBF(pre), pre.stride(0), CBF(W2), CBF(b2), lab_i, lab_f, BF(t_out), BF(logits),
                            partials.data_ptr<float>(), stats.data_ptr<float>(), (int)R, (int)H, (int)C, (int)mode,
-                           (float)tol, (int)act, p, (uint64_t)seed, cur_stream());
+                           (float)tol, (int)act, p, (uint64_t)seed, cur_stream(), eps);
 }
 
 // g fp32 [R][C] and part fp32 (>= seq_head_splits(R) · seq_head_slab(H, C)) are workspaces; dW2 / db2 are ADDED to
 void seq_head_bwd(torch::Tensor t, torch::Tensor W2, torch::Tensor logits, torch::Tensor labels, torch::Tensor stats,
                   torch::Tensor dloss, torch::Tensor dpre, torch::Tensor g, torch::Tensor part, torch::Tensor dW2,
-                  torch::Tensor db2, int64_t mode, int64_t act, double p, int64_t seed) {
+                  torch::Tensor db2, int64_t mode, int64_t act, double p, int64_t seed, double label_smoothing) {
+  const float eps = check_smoothing(label_smoothing, "seq_head");
+  TORCH_CHECK(eps == 0.f || mode == 0, "seq_head: label_smoothing is for mode 0 (CE) only");
   TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.is_contiguous() && t.scalar_type() == torch::kBFloat16, "seq_head t");
   const int64_t R = t.size(0), H = t.size(1), C = W2.size(0);
   TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 16 && H % 8 == 0 && H >= 8 && H <= 1024 && C >= 1 && C <= 64,
@@ -1253,7 +1264,7 @@ void seq_head_bwd(torch::Tensor t, torch::Tensor W2, torch::Tensor logits, torch
   hsd::launch_seq_head_bwd(CBF(t), CBF(W2), CBF(logits), lab_i, lab_f, stats.data_ptr<float>(),
                            dloss.data_ptr<float>(), BF(dpre), g.data_ptr<float>(), part.data_ptr<float>(),
                            dW2.data_ptr<float>(), db2.data_ptr<float>(), (int)R, (int)H, (int)C, (int)mode, (int)act, p,
-                           (uint64_t)seed, cur_stream());
+                           (uint64_t)seed, cur_stream(), eps);
 }
 
 int64_t seq_head_blocks(int64_t R) { return hsd::seq_head_blocks((int)R); }
@@ -1370,7 +1381,9 @@ static void token_head_check(const torch::Tensor& h, const torch::Tensor& W, con
 }
 
 void token_head_fwd(torch::Tensor h, torch::Tensor W, torch::Tensor b, c10::optional<torch::Tensor> labels,
-                    torch::Tensor logits, torch::Tensor partials, torch::Tensor stats, double p, int64_t seed) {
+                    torch::Tensor logits, torch::Tensor partials, torch::Tensor stats, double p, int64_t seed,
+                    double label_smoothing) {
+  const float eps = check_smoothing(label_smoothing, "token_head");
   token_head_check(h, W, logits);
   const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
   check_bf16_vec(b, C, "token_head b");
@@ -1379,7 +1392,7 @@ void token_head_fwd(torch::Tensor h, torch::Tensor W, torch::Tensor b, c10::opti
   TORCH_CHECK(partials.numel() >= 4 * (int64_t)hsd::token_head_fwd_blocks((int)R) && stats.numel() >= 4,
               "token_head stats");
   hsd::launch_token_head_fwd(CBF(h), CBF(W), CBF(b), head_labels(labels, R), BF(logits), partials.data_ptr<float>(),
-                             stats.data_ptr<float>(), (int)R, (int)H, (int)C, p, (uint64_t)seed, cur_stream());
+                             stats.data_ptr<float>(), (int)R, (int)H, (int)C, p, (uint64_t)seed, cur_stream(), eps);
 }
 
 // the outputs both backward entries share. dh [R][H] bf16 (or none: parameter gradients only; returns null); part
@@ -1402,7 +1415,8 @@ static hsd::bf16_t* token_head_bwd_check(const torch::Tensor& h, const torch::Te
 
 void token_head_bwd(torch::Tensor h, torch::Tensor W, torch::Tensor logits, torch::Tensor labels, torch::Tensor stats,
                     torch::Tensor dloss, c10::optional<torch::Tensor> dh, torch::Tensor part, torch::Tensor dW,
-                    torch::Tensor db, double p, int64_t seed) {
+                    torch::Tensor db, double p, int64_t seed, double label_smoothing) {
+  const float eps = check_smoothing(label_smoothing, "token_head");
   token_head_check(h, W, logits);
   const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
   const int64_t* lab = head_labels(labels, R);
@@ -1411,7 +1425,7 @@ void token_head_bwd(torch::Tensor h, torch::Tensor W, torch::Tensor logits, torc
   hsd::bf16_t* dhp = token_head_bwd_check(h, W, dloss, dh, part, dW, db);
   hsd::launch_token_head_bwd(CBF(h), CBF(W), CBF(logits), lab, stats.data_ptr<float>(), dloss.data_ptr<float>(), dhp,
                              part.data_ptr<float>(), dW.data_ptr<float>(), db.data_ptr<float>(), (int)R, (int)H,
-                             (int)C, p, (uint64_t)seed, cur_stream());
+                             (int)C, p, (uint64_t)seed, cur_stream(), eps);
 }
 
 // the token head's backward from a given gradient table (question-answering: qa_head.hip). g0 fp32 [R][C]; cnt fp32,
@@ -1687,16 +1701,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_set_force_generic", &hsd::attn_set_force_generic);
   m.def("transpose_many", &transpose_many);
   m.def("xent", &xent, py::arg("logits"), py::arg("labels"), py::arg("dlogits"), py::arg("stats"),
-        py::arg("n_valid"), py::arg("V") = 0);
+        py::arg("n_valid"), py::arg("V") = 0, py::arg("label_smoothing") = 0.0);
   m.def("cls_head_fwd", &cls_head_fwd);
   m.def("cls_head_bwd", &cls_head_bwd);
   m.def("cls_head_blocks", &cls_head_blocks);
-  m.def("seq_head_fwd", &seq_head_fwd);
-  m.def("seq_head_bwd", &seq_head_bwd);
+  m.def("seq_head_fwd", &seq_head_fwd, py::arg("pre"), py::arg("W2"), py::arg("b2"), py::arg("labels"), py::arg("t_out"),
+        py::arg("logits"), py::arg("partials"), py::arg("stats"), py::arg("mode"), py::arg("tol"), py::arg("act"),
+        py::arg("p"), py::arg("seed"), py::arg("label_smoothing") = 0.0);
+  m.def("seq_head_bwd", &seq_head_bwd, py::arg("t"), py::arg("W2"), py::arg("logits"), py::arg("labels"),
+        py::arg("stats"), py::arg("dloss"), py::arg("dpre"), py::arg("g"), py::arg("part"), py::arg("dW2"),
+        py::arg("db2"), py::arg("mode"), py::arg("act"), py::arg("p"), py::arg("seed"),
+        py::arg("label_smoothing") = 0.0);
   m.def("seq_head_blocks", &seq_head_blocks);
   m.def("seq_head_workspace", &seq_head_workspace);
-  m.def("token_head_fwd", &token_head_fwd);
-  m.def("token_head_bwd", &token_head_bwd);
+  m.def("token_head_fwd", &token_head_fwd, py::arg("h"), py::arg("W"), py::arg("b"), py::arg("labels"),
+        py::arg("logits"), py::arg("partials"), py::arg("stats"), py::arg("p"), py::arg("seed"),
+        py::arg("label_smoothing") = 0.0);
+  m.def("token_head_bwd", &token_head_bwd, py::arg("h"), py::arg("W"), py::arg("logits"), py::arg("labels"),
+        py::arg("stats"), py::arg("dloss"), py::arg("dh"), py::arg("part"), py::arg("dW"), py::arg("db"), py::arg("p"),
+        py::arg("seed"), py::arg("label_smoothing") = 0.0);
   m.def("token_head_bwd_given", &token_head_bwd_given);
   m.def("span_ce", &span_ce);
   m.def("token_head_fwd_blocks", &token_head_fwd_blocks);

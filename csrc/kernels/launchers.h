@@ -80,9 +80,10 @@ void launch_mask_bias(const void* mask, bool i64, float* out, int64_t n, hipStre
 // C[N][K] (fp32, ldc) += dy[T][N]ᵀ · x[T][K] for small T (K % 4 == 0)
 void launch_small_wgrad(const bf16_t* dy, int64_t ldy, const bf16_t* x, int64_t ldx, float* C, int64_t ldc, int T,
                         int N, int K, hipStream_t st);
-// xent.hip: fused softmax cross-entropy (+ gradient, + argmax-correct count); stats = {Σloss, correct}
+// xent.hip: fused softmax cross-entropy (+ gradient, + argmax-correct count); stats = {Σloss, correct}.
+// label_smoothing eps in [0, 1): target (1-eps)·onehot + eps/V over the V real classes (0: the plain CE's own code)
 void launch_xent(const void* logits, bool bf16, const int64_t* labels, void* dlogits, float* stats,
-                 const float* n_valid, int rows, int V, int64_t ld, hipStream_t st);
+                 const float* n_valid, int rows, int V, int64_t ld, hipStream_t st, float label_smoothing = 0.0f);
 // mlm_mask.hip: dynamic MLM masking with ordered compaction into fixed-capacity buffers (ops/rng.py "MLM mask").
 // ids / attention_mask (optional) / labels_in (optional): int64 [N]; ids_out, labels_out: int64 [N]; sel, tgt: int64
 // [cap]; inv: int32 [N]; counts: int32 [2] = {n, dropped}; n_valid: fp32 [1]; ws: int32 [mlm_mask_blocks(N)].
@@ -139,11 +140,14 @@ int seq_head_splits(int R);
 int64_t seq_head_slab(int H, int C);
 void launch_seq_head_fwd(const bf16_t* pre, int64_t ld_pre, const bf16_t* W2, const bf16_t* b2, const int64_t* lab_i,
                          const float* lab_f, bf16_t* t_out, bf16_t* logits, float* partials, float* stats, int R, int H,
-                         int C, int mode, float tol, int act, double p, uint64_t seed, hipStream_t st);
+                         int C, int mode, float tol, int act, double p, uint64_t seed, hipStream_t st,
+                         float label_smoothing = 0.0f);
 void launch_seq_head_bwd(const bf16_t* t_in, const bf16_t* W2, const bf16_t* logits, const int64_t* lab_i,
                          const float* lab_f, const float* stats, const float* dloss, bf16_t* dpre, float* g, float* slab,
                          float* dW2, float* db2, int R, int H, int C, int mode, int act, double p, uint64_t seed,
-                         hipStream_t st);
+                         hipStream_t st, float label_smoothing = 0.0f);
+// label_smoothing (CE mode of seq_head, token_head with labels): eps in [0, 1), target (1-eps)·onehot + eps/C. It is a
+// host constant of the launch; 0 launches the unsmoothed template instantiations.
 // token_head.hip: fused token-classification head over every row (dropout, classifier, CE, accuracy); H % 8 == 0,
 // H <= 1024, 2 <= C <= 16. labels may be null (logits only: stats untouched). The backward writes
 // token_head_bwd_blocks(R) fp32 partial slabs of C·H + C into `part` and adds them into dW / db; dh may be null.
@@ -151,10 +155,11 @@ int token_head_fwd_blocks(int R);
 int token_head_bwd_blocks(int R);
 void launch_token_head_fwd(const bf16_t* h, const bf16_t* W, const bf16_t* b, const int64_t* labels, bf16_t* logits,
                            float* partials, float* stats, int R, int H, int C, double p, uint64_t seed,
-                           hipStream_t st);
+                           hipStream_t st, float label_smoothing = 0.0f);
 void launch_token_head_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* logits, const int64_t* labels,
                            const float* stats, const float* dloss, bf16_t* dh, float* part, float* dW, float* db,
-                           int R, int H, int C, double p, uint64_t seed, hipStream_t st);
+                           int R, int H, int C, double p, uint64_t seed, hipStream_t st,
+                           float label_smoothing = 0.0f);
 // the same backward from a GIVEN per-row gradient table g0 [R][C] fp32 (zero rows are ignored rows):
 // g[row][c] = g0[row][c] · dloss · gmul / max(cnt[c], 1), cnt fp32 [C] on the device
 void launch_token_head_bwd_given(const bf16_t* h, const bf16_t* W, const float* g0, const float* cnt, float gmul,

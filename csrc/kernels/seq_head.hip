@@ -10,6 +10,10 @@
 //             MSE     loss = Σ_c (z - y)² / C                           hit = |z - y| <= tol for every c
 //             ignored rows: label not in [0, C) (CE), first label NaN (BCE / MSE); they add nothing anywhere
 //   backward  g       = softmax(z) - onehot | sigmoid(z) - y | 2(z - y), times dloss / max(n,1) (and 1/C for BCE / MSE)
+//             label smoothing eps > 0 (CE only, the kSmooth instantiations; eps a host constant of the launch):
+//                     loss = lse - (1-eps)·z[label] - (eps/C)·Σ_c z[c],  g = softmax(z) - (1-eps)·onehot - eps/C.
+//                     With eps > 0 ops.cls_head sends every single-label head of 1..64 classes here (cls_head.hip
+//                     has no smoothed form); eps = 0 launches the <false> instantiations, the code as it was
 //             dpre    = (g·W2 · keep · 1/(1-p)) · act'(t)   bf16; g goes to an fp32 [R][C] table as well
 //             dW2    += gᵀ·d, db2 += Σ g     seq_wgrad_kernel: register tiles of 8 columns x 8 classes over a row
 //                                            split, one fp32 slab per split; seq_wgrad_reduce_kernel adds the slabs
@@ -19,8 +23,8 @@
 // partials {loss, hits, n_valid} in the [nblk][4] layout of head_stats.hip.
 //
 // hipcc -Rpass-analysis=kernel-resource-usage (gfx950, -O3), scratch 0 in each:
-//   seq_fwd_kernel 152 VGPRs, LDS 48 B; seq_bwd_kernel 66 VGPRs, LDS 0; seq_wgrad_kernel 97 VGPRs, LDS 0;
-//   seq_wgrad_reduce_kernel 6 VGPRs, LDS 0
+//   seq_fwd_kernel<false> 152 VGPRs (<true>: 154), LDS 48 B; seq_bwd_kernel<false> 66 VGPRs (<true>: 68), LDS 0;
+//   seq_wgrad_kernel 97 VGPRs, LDS 0; seq_wgrad_reduce_kernel 6 VGPRs, LDS 0
 #include "head_common.h"
 #include "launchers.h"
 
@@ -45,12 +49,15 @@ __device__ __forceinline__ float act_fwd(float x, int act) { return act == 0 ? t
 __device__ __forceinline__ float act_bwd(float t, int act) { return act == 0 ? 1.0f - t * t : (t > 0.0f ? 1.0f : 0.0f); }
 
 // labels: int64 [R] (CE) or fp32 [R][C] (BCE / MSE); either may be null (logits only)
+// kSmooth (CE only): loss = lse - (1-eps)·z[label] - (eps/C)·Σ_c z[c]; an instantiation of its own, <false> is the
+// code as it was before eps existed
+template <bool kSmooth>
 __global__ __launch_bounds__(256) void seq_fwd_kernel(const bf16_t* __restrict__ pre, int64_t ld_pre,
                                                       const bf16_t* __restrict__ W2, const bf16_t* __restrict__ b2,
                                                       const int64_t* __restrict__ lab_i, const float* __restrict__ lab_f,
                                                       bf16_t* __restrict__ t_out, bf16_t* __restrict__ logits,
                                                       float* __restrict__ partials, int R, int H, int C, int mode,
-                                                      float tol, int act, DropoutParams dp) {
+                                                      float tol, int act, DropoutParams dp, float eps) {
   dp = resolve_seed(dp);
   __shared__ float red[4][3];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -118,7 +125,12 @@ __global__ __launch_bounds__(256) void seq_fwd_kernel(const bf16_t* __restrict__
         const float am = -wave_max(mine && z == m ? -(float)lane : -64.f);  // first maximum, as torch.argmax
         const float s = wave_sum(mine ? __expf(z - m) : 0.f);
         const float zl = wave_sum(lane == (int)lab ? z : 0.f);
-        loss = __logf(s) + m - zl;
+        if constexpr (kSmooth) {
+          const float zs = wave_sum(mine ? z : 0.f);
+          loss = __logf(s) + m - (1.0f - eps) * zl - eps * invC * zs;
+        } else {
+          loss = __logf(s) + m - zl;
+        }
         hit = (int)am == (int)lab;
       }
     } else {
@@ -156,12 +168,14 @@ __global__ __launch_bounds__(256) void seq_fwd_kernel(const bf16_t* __restrict__
 }
 
 // g [R][C] fp32 (zero rows: ignored rows) and dpre [R][H] bf16
+// kSmooth (CE only): g = (softmax - (1-eps)·onehot - eps/C) · scale
+template <bool kSmooth>
 __global__ __launch_bounds__(256) void seq_bwd_kernel(const bf16_t* __restrict__ t_in, const bf16_t* __restrict__ W2,
                                                       const bf16_t* __restrict__ logits, const int64_t* __restrict__ lab_i,
                                                       const float* __restrict__ lab_f, const float* __restrict__ stats,
                                                       const float* __restrict__ dloss, bf16_t* __restrict__ dpre,
                                                       float* __restrict__ g_out, int R, int H, int C, int mode, int act,
-                                                      DropoutParams dp) {
+                                                      DropoutParams dp, float eps) {
   dp = resolve_seed(dp);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nch = H >> 3;
@@ -186,7 +200,8 @@ __global__ __launch_bounds__(256) void seq_bwd_kernel(const bf16_t* __restrict__
         const float m = wave_max(mine ? z : -3.0e38f);
         const float e = mine ? __expf(z - m) : 0.f;
         const float s = wave_sum(e);
-        g = e / s - (lane == lab ? 1.f : 0.f);
+        if constexpr (kSmooth) g = e / s - (lane == lab ? 1.0f - eps : 0.f) - eps / (float)C;
+        else g = e / s - (lane == lab ? 1.f : 0.f);
       } else {
         const float y = mine ? lab_f[(int64_t)row * C + lane] : 0.f;
         g = mode == BCE ? 1.0f / (1.0f + __expf(-z)) - y : 2.0f * (z - y);
@@ -318,11 +333,16 @@ int64_t seq_head_slab(int H, int C) { return (((int64_t)C * H + C) + 3) / 4 * 4;
 
 void launch_seq_head_fwd(const bf16_t* pre, int64_t ld_pre, const bf16_t* W2, const bf16_t* b2, const int64_t* lab_i,
                          const float* lab_f, bf16_t* t_out, bf16_t* logits, float* partials, float* stats, int R, int H,
-                         int C, int mode, float tol, int act, double p, uint64_t seed, hipStream_t st) {
+                         int C, int mode, float tol, int act, double p, uint64_t seed, hipStream_t st,
+                         float label_smoothing) {
   const int nblk = seq_head_blocks(R);
   const DropoutParams dp = make_dropout(p, seed);
-  hipLaunchKernelGGL(seq::seq_fwd_kernel, dim3(nblk), dim3(256), 0, st, pre, ld_pre, W2, b2, lab_i, lab_f, t_out, logits,
-                     partials, R, H, C, mode, tol, act, dp);
+  if (mode == seq::CE && label_smoothing > 0.f)
+    hipLaunchKernelGGL(seq::seq_fwd_kernel<true>, dim3(nblk), dim3(256), 0, st, pre, ld_pre, W2, b2, lab_i, lab_f, t_out,
+                       logits, partials, R, H, C, mode, tol, act, dp, label_smoothing);
+  else
+    hipLaunchKernelGGL(seq::seq_fwd_kernel<false>, dim3(nblk), dim3(256), 0, st, pre, ld_pre, W2, b2, lab_i, lab_f,
+                       t_out, logits, partials, R, H, C, mode, tol, act, dp, 0.f);
   HSD_CHECK_LAUNCH();
   launch_head_stats(partials, nblk, stats, st);
 }
@@ -330,10 +350,14 @@ void launch_seq_head_fwd(const bf16_t* pre, int64_t ld_pre, const bf16_t* W2, co
 void launch_seq_head_bwd(const bf16_t* t_in, const bf16_t* W2, const bf16_t* logits, const int64_t* lab_i,
                          const float* lab_f, const float* stats, const float* dloss, bf16_t* dpre, float* g, float* slab,
                          float* dW2, float* db2, int R, int H, int C, int mode, int act, double p, uint64_t seed,
-                         hipStream_t st) {
+                         hipStream_t st, float label_smoothing) {
   const DropoutParams dp = make_dropout(p, seed);
-  hipLaunchKernelGGL(seq::seq_bwd_kernel, dim3(seq_head_blocks(R)), dim3(256), 0, st, t_in, W2, logits, lab_i, lab_f,
-                     stats, dloss, dpre, g, R, H, C, mode, act, dp);
+  if (mode == seq::CE && label_smoothing > 0.f)
+    hipLaunchKernelGGL(seq::seq_bwd_kernel<true>, dim3(seq_head_blocks(R)), dim3(256), 0, st, t_in, W2, logits, lab_i,
+                       lab_f, stats, dloss, dpre, g, R, H, C, mode, act, dp, label_smoothing);
+  else
+    hipLaunchKernelGGL(seq::seq_bwd_kernel<false>, dim3(seq_head_blocks(R)), dim3(256), 0, st, t_in, W2, logits, lab_i,
+                       lab_f, stats, dloss, dpre, g, R, H, C, mode, act, dp, 0.f);
   HSD_CHECK_LAUNCH();
   const int nsplit = seq_head_splits(R);
   const int64_t stride = seq_head_slab(H, C);

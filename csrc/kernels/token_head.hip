@@ -10,6 +10,9 @@
 //             per-block partial sums -> head_stats_kernel (head_stats.hip) -> stats = {mean loss, hits, n_valid,
 //             loss sum}
 //   backward  g       = (softmax(logits) - onehot(label)) · dloss / max(n_valid, 1)      0 on ignored rows
+//   label smoothing eps > 0 (--label_smoothing_factor; the kSmooth instantiations, eps a host constant of the launch):
+//             loss = lse - (1-eps)·logits[label] - (eps/C)·Σ_c logits[c],  g = (softmax - (1-eps)·onehot - eps/C) · ...
+//             over the C real classes; everything from g on is the same code. eps = 0 launches the <false> forms.
 //             dh      = bf16((g·W) · keep · 1/(1-p))   every row written once, 16-byte stores
 //             dW, db  : per-block fp32 partial slabs [C][H] + [C] -> tok_reduce_kernel adds them in a fixed order
 //                       INTO the gradient buffers (+=: main_grad accumulates over micro-batches). No float atomics, so
@@ -42,10 +45,13 @@
 //
 // g is rounded to bf16 for the two backward products (as a bf16 autograd chain rounds dlogits); db sums the fp32 g.
 //
-// hipcc -Rpass-analysis=kernel-resource-usage (gfx950, -O3; one instantiation each, C and H are run-time values):
-//   tok_fwd_kernel     152 VGPRs + 4 AGPRs, scratch 0, occupancy 3 waves / SIMD, LDS 33,072 B
-//   tok_bwd_kernel     233 VGPRs,           scratch 0, occupancy 2 waves / SIMD, LDS 48,640 B
-//   tok_bwd_kernel<true> (the given-gradient entry of qa_head.hip): 235 VGPRs, scratch 0, LDS 48,640 B
+// hipcc -Rpass-analysis=kernel-resource-usage (gfx950, -O3; C and H are run-time values; profiles/label_smoothing/
+// resource_usage.txt):
+//   tok_fwd_kernel<false>         152 VGPRs + 4 AGPRs, scratch 0, occupancy 3 waves / SIMD, LDS 33,072 B
+//   tok_fwd_kernel<true>          154 VGPRs + 4 AGPRs, scratch 0, occupancy 3,              LDS 33,072 B   (kSmooth)
+//   tok_bwd_kernel<false, false>  233 VGPRs,           scratch 0, occupancy 2 waves / SIMD, LDS 48,640 B
+//   tok_bwd_kernel<false, true>   235 VGPRs,           scratch 0, occupancy 2,              LDS 48,640 B   (kSmooth)
+//   tok_bwd_kernel<true, false> (the given-gradient entry of qa_head.hip): 235 VGPRs, scratch 0, LDS 48,640 B
 //   tok_reduce_kernel   12 VGPRs,           scratch 0
 #include "head_common.h"
 #include "launchers.h"
@@ -90,11 +96,14 @@ __device__ __forceinline__ void wave_lds_fence() {
 }
 
 // ------------------------------------------------------------------------------------------------ forward
+// kSmooth: the row's loss is lse - (1-eps)·logit[label] - (eps/C)·Σ_c logit[c] (label smoothing over the C real classes);
+// an instantiation of its own, so that <false> is the code it was before eps existed
+template <bool kSmooth>
 __global__ __launch_bounds__(256) void tok_fwd_kernel(const bf16_t* __restrict__ h, const bf16_t* __restrict__ W,
                                                       const bf16_t* __restrict__ bias,
                                                       const int64_t* __restrict__ labels, bf16_t* __restrict__ logits,
                                                       float* __restrict__ partials, int R, int H, int C,
-                                                      DropoutParams dp) {
+                                                      DropoutParams dp, float eps) {
   dp = resolve_seed(dp);
   __shared__ __attribute__((aligned(16))) bf16_t Wimg[CP * (MAXH + WROW_PAD)];
   __shared__ float red[4][3];
@@ -163,19 +172,24 @@ __global__ __launch_bounds__(256) void tok_fwd_kernel(const bf16_t* __restrict__
         const int oa = __shfl_xor(am, o, 64);
         if (om > m || (om == m && oa < am)) { m = om; am = oa; }
       }
-      float se = 0.f, picked = 0.f;
+      float se = 0.f, picked = 0.f, zs = 0.f;  // zs (kSmooth): Σ lg over the row's classes
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (4 * q + j < C) se += __expf(lg[j] - m);
+        if (4 * q + j < C) {
+          se += __expf(lg[j] - m);
+          if constexpr (kSmooth) zs += lg[j];
+        }
         if (4 * q + j == lab) picked = lg[j];
       }
 #pragma unroll
       for (int o = 16; o <= 32; o <<= 1) {
         se += __shfl_xor(se, o, 64);
         picked += __shfl_xor(picked, o, 64);
+        if constexpr (kSmooth) zs += __shfl_xor(zs, o, 64);
       }
       if (q == 0 && valid) {
-        loss_sum += __logf(se) + m - picked;
+        if constexpr (kSmooth) loss_sum += __logf(se) + m - (1.0f - eps) * picked - eps / (float)C * zs;
+        else loss_sum += __logf(se) + m - picked;
         hits += am == (int)lab ? 1.f : 0.f;
         nvalid += 1.f;
       }
@@ -214,7 +228,8 @@ __device__ __forceinline__ void load_tile(const bf16_t* __restrict__ h, int tile
 // per-row gradient table g0 [R][C] fp32 (launch_token_head_bwd_given: the span head of qa_head.hip, whose softmax runs
 // along the sequence), g[row][c] = g0[row][c] · dloss · gmul / max(cnt[c], 1); logits, labels and stats are not read.
 // A row of zeros in g0 is an ignored row. Everything from g on is the same code.
-template <bool GIVEN>
+// kSmooth (GIVEN = false only): g = (softmax - (1-eps)·onehot - eps/C) · scale, the label-smoothed CE's gradient.
+template <bool GIVEN, bool kSmooth>
 __global__ __launch_bounds__(256, 2) void tok_bwd_kernel(const bf16_t* __restrict__ h, const bf16_t* __restrict__ W,
                                                          const bf16_t* __restrict__ logits,
                                                          const int64_t* __restrict__ labels,
@@ -222,7 +237,8 @@ __global__ __launch_bounds__(256, 2) void tok_bwd_kernel(const bf16_t* __restric
                                                          const float* __restrict__ dloss, bf16_t* __restrict__ dh,
                                                          float* __restrict__ part, int R, int H, int C, int write_dh,
                                                          DropoutParams dp, const float* __restrict__ g0,
-                                                         const float* __restrict__ cnt, float gmul) {
+                                                         const float* __restrict__ cnt, float gmul, float eps) {
+  static_assert(!(GIVEN && kSmooth), "a given gradient table is not smoothed");
   dp = resolve_seed(dp);
   __shared__ __attribute__((aligned(16))) bf16_t Wt[MAXH * WT_STRIDE];
   __shared__ __attribute__((aligned(16))) bf16_t Dst[4][TR * D_STRIDE];
@@ -321,7 +337,9 @@ __global__ __launch_bounds__(256, 2) void tok_bwd_kernel(const bf16_t* __restric
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int c = 4 * q + j;
-          g[j] = valid && c < C ? (e[j] * inv - (c == (int)lab ? 1.f : 0.f)) * scale : 0.f;
+          if constexpr (kSmooth)
+            g[j] = valid && c < C ? (e[j] * inv - (c == (int)lab ? 1.0f - eps : 0.f) - eps / (float)C) * scale : 0.f;
+          else g[j] = valid && c < C ? (e[j] * inv - (c == (int)lab ? 1.f : 0.f)) * scale : 0.f;
           accb[j] += g[j];
         }
       }
@@ -442,21 +460,32 @@ int token_head_bwd_blocks(int R) {
 
 void launch_token_head_fwd(const bf16_t* h, const bf16_t* W, const bf16_t* b, const int64_t* labels, bf16_t* logits,
                            float* partials, float* stats, int R, int H, int C, double p, uint64_t seed,
-                           hipStream_t st) {
+                           hipStream_t st, float label_smoothing) {
   const int nblk = token_head_fwd_blocks(R);
   const DropoutParams dp = make_dropout(p, seed);
-  hipLaunchKernelGGL(tok::tok_fwd_kernel, dim3(nblk), dim3(256), 0, st, h, W, b, labels, logits, partials, R, H, C, dp);
+  if (labels != nullptr && label_smoothing > 0.f)
+    hipLaunchKernelGGL(tok::tok_fwd_kernel<true>, dim3(nblk), dim3(256), 0, st, h, W, b, labels, logits, partials, R, H,
+                       C, dp, label_smoothing);
+  else
+    hipLaunchKernelGGL(tok::tok_fwd_kernel<false>, dim3(nblk), dim3(256), 0, st, h, W, b, labels, logits, partials, R,
+                       H, C, dp, 0.f);
   HSD_CHECK_LAUNCH();
   if (labels != nullptr) launch_head_stats(partials, nblk, stats, st);
 }
 
 void launch_token_head_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* logits, const int64_t* labels,
                            const float* stats, const float* dloss, bf16_t* dh, float* part, float* dW, float* db,
-                           int R, int H, int C, double p, uint64_t seed, hipStream_t st) {
+                           int R, int H, int C, double p, uint64_t seed, hipStream_t st, float label_smoothing) {
   const int nblk = token_head_bwd_blocks(R);
   const DropoutParams dp = make_dropout(p, seed);
-  hipLaunchKernelGGL(tok::tok_bwd_kernel<false>, dim3(nblk), dim3(256), 0, st, h, W, logits, labels, stats, dloss, dh,
-                     part, R, H, C, dh != nullptr ? 1 : 0, dp, (const float*)nullptr, (const float*)nullptr, 0.f);
+  if (label_smoothing > 0.f)
+    hipLaunchKernelGGL((tok::tok_bwd_kernel<false, true>), dim3(nblk), dim3(256), 0, st, h, W, logits, labels, stats,
+                       dloss, dh, part, R, H, C, dh != nullptr ? 1 : 0, dp, (const float*)nullptr,
+                       (const float*)nullptr, 0.f, label_smoothing);
+  else
+    hipLaunchKernelGGL((tok::tok_bwd_kernel<false, false>), dim3(nblk), dim3(256), 0, st, h, W, logits, labels, stats,
+                       dloss, dh, part, R, H, C, dh != nullptr ? 1 : 0, dp, (const float*)nullptr,
+                       (const float*)nullptr, 0.f, 0.f);
   HSD_CHECK_LAUNCH();
   const int n = C * H + C;
   hipLaunchKernelGGL(tok::tok_reduce_kernel, dim3((n + tok::RED_X - 1) / tok::RED_X), dim3(tok::RED_X * tok::RED_G), 0,
@@ -470,9 +499,9 @@ void launch_token_head_bwd_given(const bf16_t* h, const bf16_t* W, const float* 
                                  int C, double p, uint64_t seed, hipStream_t st) {
   const int nblk = token_head_bwd_blocks(R);
   const DropoutParams dp = make_dropout(p, seed);
-  hipLaunchKernelGGL(tok::tok_bwd_kernel<true>, dim3(nblk), dim3(256), 0, st, h, W, (const bf16_t*)nullptr,
+  hipLaunchKernelGGL((tok::tok_bwd_kernel<true, false>), dim3(nblk), dim3(256), 0, st, h, W, (const bf16_t*)nullptr,
                      (const int64_t*)nullptr, (const float*)nullptr, dloss, dh, part, R, H, C, dh != nullptr ? 1 : 0,
-                     dp, g0, cnt, gmul);
+                     dp, g0, cnt, gmul, 0.f);
   HSD_CHECK_LAUNCH();
   const int n = C * H + C;
   hipLaunchKernelGGL(tok::tok_reduce_kernel, dim3((n + tok::RED_X - 1) / tok::RED_X), dim3(tok::RED_X * tok::RED_G), 0,

@@ -5,6 +5,12 @@
 //   dx_r  = (softmax(x_r) - onehot(y_r)) / n_valid                 (written in the same launch)
 //   correct += [argmax(x_r) == y_r]                                (accuracy metric)
 //
+// Label smoothing (--label_smoothing_factor eps, xent_kernel<kBF16, true>): the target of a row is (1-eps)·onehot + eps/V
+// over the V REAL classes, so loss_r = lse - (1-eps)·x_r[y_r] - (eps/V)·Σ_{j<V} x_r[j] and dx_r = (softmax - (1-eps)·onehot
+// - eps/V) / n_valid; the columns V..ld of a padded vocabulary keep their exact zeros. Pass 1 carries one more per-lane
+// fp32 sum. hipcc -Rpass-analysis=kernel-resource-usage: <true, false> 96 VGPRs (5 waves / SIMD), <true, true> 98 (4),
+// <false, false> 60, <false, true> 62 (8 both); scratch 0 in all four.
+//
 // One wave per row, any vocabulary size: pass 1 streams the row with 16-B loads keeping a per-lane
 // online (max, Σexp) pair and argmax, wave-reduced; pass 2 re-reads the row and writes the gradient.
 // The 2-way classifier (V = 2) and the 50265-way RoBERTa MLM decoder use the same kernel, so the MLM
@@ -38,10 +44,14 @@ __device__ __forceinline__ void ldvec(const void* __restrict__ x, int64_t i, flo
   }
 }
 
-template <bool kBF16>
+// kSmooth: label smoothing eps in (0, 1) over the V real classes (HF LabelSmoother, F.cross_entropy(label_smoothing=)):
+//   term = lse - (1-eps)·x[y] - (eps/V)·Σ_{j<V} x[j],  dx[j] = scale·(softmax[j] - (1-eps)·[j == y] - eps/V) for j < V.
+// An instantiation of its own: eps = 0 launches xent_kernel<kBF16, false>, whose code does not know eps.
+template <bool kBF16, bool kSmooth>
 __global__ __launch_bounds__(256) void xent_kernel(const void* __restrict__ logits, const int64_t* __restrict__ labels,
                                                    void* __restrict__ dlogits, float* __restrict__ stats,
-                                                   const float* __restrict__ n_valid, int rows, int V, int64_t ld) {
+                                                   const float* __restrict__ n_valid, int rows, int V, int64_t ld,
+                                                   float eps) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -49,6 +59,7 @@ __global__ __launch_bounds__(256) void xent_kernel(const void* __restrict__ logi
   const int64_t y = labels[row];
   const bool valid = y >= 0 && y < V;
   float m = -INFINITY, s = 0.f, best = -INFINITY;
+  float zsum = 0.f;  // kSmooth: Σ x[j] over this lane's j < V
   int besti = 0;
   // vector path: 8 bf16 (or 4 fp32) per 16-B load over the 16-B-aligned part of the row, scalar tail. XU 16-B loads
   // per lane are issued before any is used: one wave per row holds XU KiB in flight instead of 1 (the MLM head's
@@ -61,6 +72,10 @@ __global__ __launch_bounds__(256) void xent_kernel(const void* __restrict__ logi
     float cm = v[0];
 #pragma unroll
     for (int k = 1; k < VEC; ++k) cm = fmaxf(cm, v[k]);
+    if constexpr (kSmooth) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) zsum += v[k];
+    }
     const float nm = fmaxf(m, cm);
     // nothing but -inf so far (a masked-out prefix): s stays 0; -inf - -inf below would turn it into NaN for good
     if (nm == -INFINITY) return;
@@ -87,6 +102,7 @@ __global__ __launch_bounds__(256) void xent_kernel(const void* __restrict__ logi
   }
   for (int j = Vv + lane; j < V; j += 64) {
     const float v = ld1<kBF16>(logits, base + j);
+    if constexpr (kSmooth) zsum += v;
     const float nm = fmaxf(m, v);
     if (nm == -INFINITY) continue;  // as in consume()
     s = s * __expf(m - nm) + __expf(v - nm);
@@ -103,11 +119,15 @@ __global__ __launch_bounds__(256) void xent_kernel(const void* __restrict__ logi
     const float ob = __shfl_xor(best, o, 64);
     const int oi = __shfl_xor(besti, o, 64);
     if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+    if constexpr (kSmooth) zsum += __shfl_xor(zsum, o, 64);
   }
   const float lse = m + __logf(s);
   const float inv_n = 1.0f / fmaxf(*n_valid, 1.0f);
+  const float uni = kSmooth ? eps / (float)V : 0.f;   // the uniform part of the smoothed target
+  const float hot = kSmooth ? 1.0f - eps : 1.0f;      // the label's part
   if (lane == 0 && valid) {
-    atomicAdd(stats + 0, lse - ld1<kBF16>(logits, base + y));
+    if constexpr (kSmooth) atomicAdd(stats + 0, lse - hot * ld1<kBF16>(logits, base + y) - uni * zsum);
+    else atomicAdd(stats + 0, lse - ld1<kBF16>(logits, base + y));
     atomicAdd(stats + 1, besti == (int)y ? 1.0f : 0.0f);
   }
   if (dlogits) {
@@ -119,7 +139,8 @@ __global__ __launch_bounds__(256) void xent_kernel(const void* __restrict__ logi
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
           const int jj = j + k;
-          g[k] = jj < V ? scale * (__expf(v[k] - lse) - (jj == y ? 1.0f : 0.0f)) : 0.0f;
+          if constexpr (kSmooth) g[k] = jj < V ? scale * (__expf(v[k] - lse) - (jj == y ? hot : 0.0f) - uni) : 0.0f;
+          else g[k] = jj < V ? scale * (__expf(v[k] - lse) - (jj == y ? 1.0f : 0.0f)) : 0.0f;
         }
         if constexpr (kBF16) {
           *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(dlogits) + base + j) =
@@ -144,7 +165,10 @@ __global__ __launch_bounds__(256) void xent_kernel(const void* __restrict__ logi
       }
     } else {
       for (int j = lane; j < ld; j += 64) {
-        const float g = j < V ? scale * (__expf(ld1<kBF16>(logits, base + j) - lse) - (j == y ? 1.0f : 0.0f)) : 0.0f;
+        float g;
+        if constexpr (kSmooth)
+          g = j < V ? scale * (__expf(ld1<kBF16>(logits, base + j) - lse) - (j == y ? hot : 0.0f) - uni) : 0.0f;
+        else g = j < V ? scale * (__expf(ld1<kBF16>(logits, base + j) - lse) - (j == y ? 1.0f : 0.0f)) : 0.0f;
         st1<kBF16>(dlogits, base + j, g);
       }
     }
@@ -153,12 +177,22 @@ __global__ __launch_bounds__(256) void xent_kernel(const void* __restrict__ logi
 
 // stats[0] += Σ loss terms, stats[1] += correct; n_valid: device scalar (number of non-ignored rows)
 // ld: row stride of logits / dlogits (>= V; a padded vocabulary's extra columns are ignored and get zero gradient)
+// label_smoothing: eps in [0, 1), a host constant of the launch; 0 runs the unsmoothed instantiation
+template <bool kBF16>
+static void launch_xent_t(const void* logits, const int64_t* labels, void* dlogits, float* stats, const float* n_valid,
+                          int rows, int V, int64_t ld, float eps, int blocks, hipStream_t st) {
+  if (eps > 0.f)
+    hipLaunchKernelGGL((xent_kernel<kBF16, true>), dim3(blocks), dim3(256), 0, st, logits, labels, dlogits, stats, n_valid, rows, V, ld, eps);
+  else
+    hipLaunchKernelGGL((xent_kernel<kBF16, false>), dim3(blocks), dim3(256), 0, st, logits, labels, dlogits, stats, n_valid, rows, V, ld, 0.f);
+}
+
 void launch_xent(const void* logits, bool bf16, const int64_t* labels, void* dlogits, float* stats,
-                 const float* n_valid, int rows, int V, int64_t ld, hipStream_t st) {
+                 const float* n_valid, int rows, int V, int64_t ld, hipStream_t st, float label_smoothing) {
   const int blocks = (rows + 3) / 4;
   if (blocks == 0) return;
-  if (bf16) hipLaunchKernelGGL(xent_kernel<true>, dim3(blocks), dim3(256), 0, st, logits, labels, dlogits, stats, n_valid, rows, V, ld);
-  else hipLaunchKernelGGL(xent_kernel<false>, dim3(blocks), dim3(256), 0, st, logits, labels, dlogits, stats, n_valid, rows, V, ld);
+  if (bf16) launch_xent_t<true>(logits, labels, dlogits, stats, n_valid, rows, V, ld, label_smoothing, blocks, st);
+  else launch_xent_t<false>(logits, labels, dlogits, stats, n_valid, rows, V, ld, label_smoothing, blocks, st);
   HSD_CHECK_LAUNCH();
 }
 

@@ -155,6 +155,9 @@ _FAMILY = {"bert": "Bert", "roberta": "Roberta", "distilbert": "DistilBert"}  # 
 class _Base(nn.Module):
     base_prefix = None  # HF's name of the base model: cfg.model_type, unless the class fixes it
     arch_suffix = None  # HF's class name is _FAMILY[cfg.model_type] + arch_suffix
+    # --label_smoothing_factor (HF TrainingArguments.label_smoothing_factor): a training argument, not a model property;
+    # the runner sets it on the object, it is never written to config.json. The single-label CE heads pass it on.
+    label_smoothing = 0.0
 
     def __init__(self, cfg: ModelConfig):
         super().__init__()
@@ -208,7 +211,8 @@ class TransformerForSequenceClassification(_Base):
     ``cfg.problem_type`` picks the loss as HF's ``config.problem_type`` does: ``None`` /
     ``"single_label_classification"`` cross-entropy on int labels ``[B]``; ``"multi_label_classification"``
     BCE-with-logits and ``"regression"`` MSE on fp32 labels ``[B, num_labels]`` (``ops.reference.seq_loss``). Nothing
-    reads a device value on the host on any of them."""
+    reads a device value on the host on any of them. ``label_smoothing`` (``--label_smoothing_factor``) smooths the
+    single-label cross-entropy, in training and in evaluation; the float-label types refuse it."""
 
     arch_suffix = "ForSequenceClassification"
 
@@ -266,15 +270,17 @@ class TransformerForSequenceClassification(_Base):
         # logits without labels, else (loss, logits)
         if c.problem_type is None:
             return ops.cls_head(h, w1, b1, self.classifier_weight, self.classifier_bias, labels, act, p_in, seed_in, p,
-                                seed)
+                                seed, label_smoothing=self.label_smoothing)
         return ops.cls_head(h, w1, b1, self.classifier_weight, self.classifier_bias, labels, act, p_in, seed_in, p, seed,
-                            problem_type=c.problem_type, tol=self.regression_tolerance)
+                            problem_type=c.problem_type, tol=self.regression_tolerance,
+                            label_smoothing=self.label_smoothing)
 
 
 class TransformerForTokenClassification(_Base):
     """BertForTokenClassification / RobertaForTokenClassification / DistilBertForTokenClassification:
     ``logits = classifier(dropout(sequence_output))`` over every row (no pooler, no dense layer), mean CE over the
-    rows whose label is not -100 (NER, POS tagging, chunking).
+    rows whose label is not -100 (NER, POS tagging, chunking); ``label_smoothing`` > 0 makes it the smoothed CE
+    (target ``(1-eps)·onehot + eps/num_labels``).
 
     Inputs: padded ``[B, S]`` ids with ``[B, S]`` labels (logits ``[B, S, L]``), or a packed ``[1, T]`` buffer with
     ``[T]`` labels (data/packing.py; logits ``[T, L]``). The head (``ops.token_head``) draws one dropout seed after
@@ -304,7 +310,8 @@ class TransformerForTokenClassification(_Base):
         H = h.shape[-1]
         p = self.head_dropout() if self.training else 0.0
         seed = self.rng.next() if p else 0
-        out = ops.token_head(h.reshape(-1, H), self.classifier_weight, self.classifier_bias, labels, p, seed)
+        out = ops.token_head(h.reshape(-1, H), self.classifier_weight, self.classifier_bias, labels, p, seed,
+                             label_smoothing=self.label_smoothing)
         shape = tuple(h.shape[:-1]) + (self.cfg.num_labels,)  # [B, S, L] padded, [T, L] packed
         if labels is None:
             return out.view(shape)
@@ -489,11 +496,13 @@ class RobertaForMaskedLM(_Base):
         if mask is not None:
             # fixed-capacity head: the rows the device compacted, no host read (graph-safe)
             return ops.mlm_head_fixed(x, mask, self.lm_dense_weight, self.lm_dense_bias, self.lm_ln_weight,
-                                      self.lm_ln_bias, c.layer_norm_eps, wemb, self.lm_bias, self.vocab)
+                                      self.lm_ln_bias, c.layer_norm_eps, wemb, self.lm_bias, self.vocab,
+                                      label_smoothing=self.label_smoothing)
         if labels is not None:
             # only masked positions feed the (large-vocab) decoder: dense + GELU -> LN -> tied decoder -> CE
             loss, logits = ops.mlm_head(x, labels.view(-1), self.lm_dense_weight, self.lm_dense_bias, self.lm_ln_weight,
-                                        self.lm_ln_bias, c.layer_norm_eps, wemb, self.lm_bias, self.vocab)
+                                        self.lm_ln_bias, c.layer_norm_eps, wemb, self.lm_bias, self.vocab,
+                                        label_smoothing=self.label_smoothing)
             return loss, logits
         x = ops.linear_gelu(x, self.lm_dense_weight, self.lm_dense_bias)
         x = ops.layer_norm(x, self.lm_ln_weight, self.lm_ln_bias, c.layer_norm_eps)

@@ -13,6 +13,11 @@ model on all rows (:func:`attn_block_cls`; tests and same-process A/Bs). ``HSD_T
 token-classification head (:func:`token_head`) as composed ops instead of its fused kernels (A/B measurements);
 ``HSD_QA_HEAD=composed`` does the same for the question-answering head (:func:`qa_head`), ``HSD_SEQ_HEAD=composed``
 for the sequence-level head of ``--problem_type`` (:func:`cls_head` beyond single-label heads of at most 4 classes).
+
+``label_smoothing`` (``--label_smoothing_factor``; :func:`cross_entropy`, :func:`cls_head`, :func:`token_head`,
+:func:`mlm_head`, :func:`mlm_head_fixed`): ε in [0, 1), the target of every CE row becomes ``(1-ε)·onehot + ε/C`` over
+the C real classes (definition: ``reference.cross_entropy``). On the HIP path ε is a host constant of the launch that
+selects the kernels' smoothed template instantiations; ε = 0 dispatches exactly as a call without the keyword.
 """
 from __future__ import annotations
 
@@ -233,10 +238,19 @@ def _with_stats(loss, stats, pred=None):
     return loss
 
 
-def _sum_ce(logits, tgt, n=None):
+def _smoothing(label_smoothing) -> float:
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:  # NaN fails both comparisons
+        raise ValueError(f"label_smoothing {label_smoothing!r}: 0 <= label_smoothing < 1")
+    return eps
+
+
+def _sum_ce(logits, tgt, n=None, label_smoothing: float = 0.0):
     """Composed CE: ``Σ CE / max(n, 1)`` over the rows whose target is not -100, carrying {mean loss, hits, n, loss
-    sum}. ``n``: the number of such rows as a device fp32 scalar (counted here when not given)."""
-    lsum = torch.nn.functional.cross_entropy(logits.float(), tgt, ignore_index=-100, reduction="sum")
+    sum}. ``n``: the number of such rows as a device fp32 scalar (counted here when not given). ``label_smoothing``:
+    the smoothed CE of ``reference.cross_entropy``."""
+    lsum = torch.nn.functional.cross_entropy(logits.float(), tgt, ignore_index=-100, reduction="sum",
+                                             label_smoothing=float(label_smoothing))
     with torch.no_grad():
         ok = tgt.ne(-100)
         if n is None:
@@ -248,18 +262,22 @@ def _sum_ce(logits, tgt, n=None):
     return _with_stats(loss, stats)
 
 
-def cross_entropy(logits, labels):
+def cross_entropy(logits, labels, label_smoothing: float = 0.0):
     """Mean CE over non-ignored labels. On the HIP path the fused kernel also counts argmax hits; the count
-    rides on the loss tensor (``loss._hsd_correct``) so metrics need no second pass over the logits."""
-    if _hip(logits):
-        loss, correct = _hipmod().cross_entropy(logits, labels)
+    rides on the loss tensor (``loss._hsd_correct``) so metrics need no second pass over the logits.
+
+    ``label_smoothing`` ε > 0: the smoothed CE, on the smoothed instantiation of the same kernel; fp32 GPU logits (the
+    composed fp32 heads) take that kernel too (``xent_kernel<false, true>``)."""
+    eps = _smoothing(label_smoothing)
+    if _hip(logits) or (eps > 0.0 and _hip32(logits) and logits.dim() == 2):
+        loss, correct = _hipmod().cross_entropy(logits, labels, eps)
         loss._hsd_correct = correct
         return loss
-    return _ref.cross_entropy(logits, labels)
+    return _ref.cross_entropy(logits, labels, eps)
 
 
 def cls_head(h, w1, b1, w2, b2, labels, act: str, p_in: float, seed_in: int, p: float, seed: int, *,
-             problem_type: Optional[str] = None, tol: float = 0.5):
+             problem_type: Optional[str] = None, tol: float = 0.5, label_smoothing: float = 0.0):
     """Classification head on the first token of ``h`` [B, S, H] (+ the loss when ``labels`` is given). ``S`` is 1 when
     the encoder already pruned its last layer to the first-token rows (``Encoder.forward(first_token_only=True)``).
 
@@ -273,17 +291,25 @@ def cls_head(h, w1, b1, w2, b2, labels, act: str, p_in: float, seed_in: int, p: 
     ``reference.seq_loss`` with its {mean loss, hits, n, loss sum} on ``loss._hsd_stats`` on every path; ``tol`` is
     the regression hit tolerance. bf16 GPU tensors within ``hip.seq_head_ok`` (H % 8 == 0, H <= 1024, C <= 64) run
     csrc/kernels/seq_head.hip for both and for single-label heads of 5..64 classes, unless ``HSD_SEQ_HEAD=composed``;
-    everything else runs the composed ops with the same seeds and so the same masks."""
+    everything else runs the composed ops with the same seeds and so the same masks.
+
+    ``label_smoothing`` ε > 0 (single-label only; the other two types refuse it): the smoothed CE. cls_head.hip and the
+    fp32 fused tail have no smoothed form, so single-label bf16 heads of 1..64 classes all run seq_head.hip's smoothed
+    instantiations and fp32 GPU heads the composed ops with :func:`cross_entropy` on the smoothed CE kernel. With
+    ε = 0 the dispatch is the one above."""
     if problem_type not in (None,) + _ref.PROBLEM_TYPES:
         raise ValueError(f"problem_type {problem_type!r}: one of {_ref.PROBLEM_TYPES} or None")
     single = problem_type in (None, "single_label_classification")
+    eps = _smoothing(label_smoothing)
+    if eps > 0.0 and not single:
+        raise ValueError(f"label_smoothing is for single-label classification, not problem_type {problem_type!r}")
     mod = _hipmod() if _hip(h) else _hip32mod() if _hip32(h) else None
-    if single and mod is not None and labels is not None and mod.cls_head_ok(h, w1, w2):
+    if eps == 0.0 and single and mod is not None and labels is not None and mod.cls_head_ok(h, w1, w2):
         loss, logits, stats = mod.cls_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed)
         return _with_stats(loss, stats), logits
     if _hip(h) and SEQ_HEAD_FUSED and labels is not None and _hipmod().seq_head_ok(h, w1, w2):
         loss, logits, stats = _hipmod().seq_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed,
-                                                 problem_type, tol)
+                                                 problem_type, tol, eps)
         return _with_stats(loss, stats), logits
     x = h[:, 0].contiguous()
     if _hip(h) or _hip32(h):
@@ -291,18 +317,26 @@ def cls_head(h, w1, b1, w2, b2, labels, act: str, p_in: float, seed_in: int, p: 
         y = linear(x, w1, b1)
         y = torch.tanh(y) if act == "tanh" else torch.relu(y)
         y = dropout(y, p, seed)
-        logits = linear(y, w2, b2)
+        C = w2.shape[0]
+        if _hip32(h) and C % 4:
+            # the fp32 GEMM epilogue takes whole groups of 4 columns (smoothed heads come here with any C): classes of
+            # zeros pad the classifier and their logits are cut off again, so they reach neither loss nor gradient
+            pad = 4 - C % 4
+            logits = linear(y, torch.cat([w2, w2.new_zeros(pad, w2.shape[1])]), torch.cat([b2, b2.new_zeros(pad)]))
+            logits = logits[:, :C].contiguous()
+        else:
+            logits = linear(y, w2, b2)
     else:
         logits = _ref.cls_head(x, w1, b1, w2, b2, act, p_in, seed_in, p, seed, True)
     if labels is None:
         return logits
     if single and problem_type is None:
-        return cross_entropy(logits, labels), logits
-    loss, stats = _ref.seq_loss(logits, labels, problem_type, tol)
+        return cross_entropy(logits, labels, eps), logits
+    loss, stats = _ref.seq_loss(logits, labels, problem_type, tol, eps)
     return _with_stats(loss, stats), logits
 
 
-def token_head(h2d, w, b, labels, p: float, seed: int):
+def token_head(h2d, w, b, labels, p: float, seed: int, label_smoothing: float = 0.0):
     """Token-classification head on every row of ``h2d`` [R, H]: ``logits = dropout(h) Wᵀ + b`` [R, C] and, with
     ``labels`` [R], the CE over the rows whose label is not -100 divided by ``max(n_valid, 1)`` (0 when every row is
     ignored). Returns ``logits`` without labels, else ``(loss, logits)`` with the fused {mean loss, hits, n_valid,
@@ -312,18 +346,22 @@ def token_head(h2d, w, b, labels, p: float, seed: int):
     bf16 GPU tensors within ``hip.token_head_ok`` (H % 8 == 0, H <= 1024, 2 <= C <= 16) run the fused kernels of
     csrc/kernels/token_head.hip, unless ``HSD_TOKEN_HEAD=composed``. Everything else (CPU tensors, fp32 GPU tensors,
     ``HSD_OPS=torch``, other shapes) runs the composed ``dropout -> linear -> cross_entropy`` with the same seed and
-    so the same mask; the all-torch form of it is ``reference.token_head``, the kernels' oracle."""
+    so the same mask; the all-torch form of it is ``reference.token_head``, the kernels' oracle.
+
+    ``label_smoothing`` ε > 0: the smoothed CE on every path (the fused kernels' smoothed instantiations, ``_sum_ce``,
+    ``reference.token_head``)."""
+    eps = _smoothing(label_smoothing)
     lab = labels.reshape(-1) if labels is not None else None
     needs_grad = torch.is_grad_enabled() and (h2d.requires_grad or w.requires_grad or b.requires_grad)
     if _hip(h2d) and TOKEN_HEAD_FUSED and _hipmod().token_head_ok(h2d, w) and not (lab is None and needs_grad):
         if lab is None:  # inference: the fused forward alone (differentiable logits take the composed ops below)
             return _hipmod().token_head_logits(h2d, w, b, p, seed)
-        loss, logits, stats = _hipmod().token_head(h2d, w, b, lab, p, seed)
+        loss, logits, stats = _hipmod().token_head(h2d, w, b, lab, p, seed, eps)
         return _with_stats(loss, stats), logits
     if _hip(h2d) or (_hip32(h2d) and w.shape[0] % 4 == 0):  # (the fp32 GEMM epilogue takes whole groups of 4 columns)
         logits = linear(dropout(h2d, p, seed), w, b)
-        return logits if lab is None else (_sum_ce(logits, lab.long()), logits)
-    out = _ref.token_head(h2d, w, b, lab, p, seed, True)
+        return logits if lab is None else (_sum_ce(logits, lab.long(), None, eps), logits)
+    out = _ref.token_head(h2d, w, b, lab, p, seed, True, eps)
     if lab is None:
         return out
     loss, logits, stats = out
@@ -364,14 +402,16 @@ def qa_head(h2d, w, b, positions, cu, row_mask, p: float, seed: int, max_answer_
     return _with_stats(loss, stats, pred), logits
 
 
-def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
+def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, label_smoothing: float = 0.0):
     """Masked-LM head (RoBERTa) on the masked rows of ``h2d`` -> (loss, logits over the real vocabulary).
 
     GPU: every GEMM on gemm2 (dense + GELU epilogue, LN kernel, the tied decoder over the 256-padded vocabulary, its
     dgrad reading the embedding table directly and the embedding-table weight gradient), the chunked-vocabulary CE
-    kernel; the argmax-hit count rides on ``loss._hsd_correct``."""
+    kernel; the argmax-hit count rides on ``loss._hsd_correct``. ``label_smoothing``: the smoothed CE over the
+    ``vocab`` real classes; the padding columns of the decoder keep an exactly zero gradient."""
+    ls = _smoothing(label_smoothing)
     if _hip(h2d) and h2d.dtype == torch.bfloat16 and _hipmod().mlm_head_ok(h2d, w1, wemb):
-        loss, logits, correct = _hipmod().mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab)
+        loss, logits, correct = _hipmod().mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, ls)
         loss._hsd_correct = correct
         return loss, logits
     if _hip(h2d):
@@ -379,8 +419,8 @@ def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
         x = h2d.index_select(0, sel)
         x = layer_norm(linear_gelu(x, w1, b1), ln_w, ln_b, eps)
         logits = linear(x, wemb[:vocab], bias[:vocab])
-        return cross_entropy(logits, labels.index_select(0, sel)), logits
-    return _ref.mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab)
+        return cross_entropy(logits, labels.index_select(0, sel), ls), logits
+    return _ref.mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, ls)
 
 
 def mlm_mask(input_ids, attention_mask, labels_in, seed, p, mask_id, special_ids, rand_range, cap=None,
@@ -399,18 +439,19 @@ def mlm_mask(input_ids, attention_mask, labels_in, seed, p, mask_id, special_ids
     return mlm_mask_reference(input_ids, attention_mask, labels_in, seed, p, mask_id, special_ids, rand_range, cap)
 
 
-def mlm_head_fixed(h2d, mask, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
+def mlm_head_fixed(h2d, mask, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, label_smoothing: float = 0.0):
     """Masked-LM head on the fixed-capacity rows of an :func:`mlm_mask` result -> (loss, logits [cap, vocab]).
 
     The loss is ``Σ CE / max(n, 1)`` computed on the device (0 when nothing was selected) and carries the fused
     {mean loss, hits, rows, loss sum} on ``loss._hsd_stats`` / the hits on ``loss._hsd_correct``: nothing in here reads a
     device value on the host. GPU bf16 tensors that :func:`hip.mlm_head_ok` accepts run the HIP head (the static
     head's kernels on ``cap`` rows, a row-scatter kernel for the hidden-state gradient); everything else the same
-    ``(sel, tgt)`` through the composed ops."""
+    ``(sel, tgt)`` through the composed ops. ``label_smoothing`` as in :func:`mlm_head`."""
+    ls = _smoothing(label_smoothing)
     sel, tgt, n_valid = mask.sel, mask.tgt, mask.n_valid
     if _hip(h2d) and h2d.dtype == torch.bfloat16 and _hipmod().mlm_head_ok(h2d, w1, wemb):
         loss, logits, stats = _hipmod().mlm_head_fixed(h2d, sel, tgt, mask.inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb,
-                                                       bias, vocab)
+                                                       bias, vocab, ls)
         return _with_stats(loss, stats), logits
     x = h2d.index_select(0, sel)
     if _hip(h2d) or _hip32(h2d):
@@ -419,7 +460,7 @@ def mlm_head_fixed(h2d, mask, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
     else:
         x = _ref.layer_norm(_ref.linear_gelu(x, w1, b1), ln_w, ln_b, eps)
         logits = torch.nn.functional.linear(x, wemb[:vocab], bias[:vocab])
-    return _sum_ce(logits, tgt, n_valid[0]), logits
+    return _sum_ce(logits, tgt, n_valid[0], ls), logits
 
 
 def accuracy_count(logits, labels):

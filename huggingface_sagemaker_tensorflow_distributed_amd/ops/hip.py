@@ -1412,7 +1412,7 @@ class _SeqHead(torch.autograd.Function):
     reducer into main_grad (no atomics), then the dense layer's colsum / wgrad / dgrad as in _ClsHead."""
 
     @staticmethod
-    def forward(ctx, h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed, mode, tol):
+    def forward(ctx, h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed, mode, tol, smooth):
         B, S, H = h.shape
         C = w2.shape[0]
         x = h.reshape(B, S * H)[:, :H]  # the [CLS] rows, read in place (row stride S*H)
@@ -1429,9 +1429,10 @@ class _SeqHead(torch.autograd.Function):
         else:
             lab = labels.to(torch.float32).reshape(B, C).contiguous()
         w2c, b2c = w2.contiguous(), b2.contiguous()
-        _C.seq_head_fwd(pre, w2c, b2c, lab, t, logits, partials, stats, mode, float(tol), _ACT[act], float(p), _s64(seed))
+        _C.seq_head_fwd(pre, w2c, b2c, lab, t, logits, partials, stats, mode, float(tol), _ACT[act], float(p), _s64(seed),
+                        smooth)
         ctx.save_for_backward(x, w1, b1, t, w2, b2, logits, lab, stats)
-        ctx.cfg = (act, float(p_in), seed_in, float(p), seed, B, S, H, mode)
+        ctx.cfg = (act, float(p_in), seed_in, float(p), seed, B, S, H, mode, smooth)
         ctx.mark_non_differentiable(logits, stats)
         ctx.set_materialize_grads(False)  # no zero-filled gradients for the non-differentiable outputs
         return stats[0], logits, stats
@@ -1439,14 +1440,14 @@ class _SeqHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dlogits, _dstats):
         x, w1, b1, t, w2, b2, logits, lab, stats = ctx.saved_tensors
-        act, p_in, seed_in, p, seed, B, S, H, mode = ctx.cfg
+        act, p_in, seed_in, p, seed, B, S, H, mode, smooth = ctx.cfg
         C = w2.shape[0]
         g_w1, g_b1, g_w2, g_b2 = _Grad(w1), _Grad(b1), _Grad(w2), _Grad(b2)
         dpre = torch.empty_like(t)
         nws = _C.seq_head_workspace(B, H, C)
         ws = _workspace(nws + B * C, t.device)  # the slabs (a multiple of 4 floats each), then g [B][C]
         _C.seq_head_bwd(t, w2.contiguous(), logits, lab, stats, _dloss1(dloss, t.device), dpre, ws[nws:nws + B * C],
-                        ws[:nws], g_w2.buf.view(-1), g_b2.buf.view(-1), mode, _ACT[act], p, _s64(seed))
+                        ws[:nws], g_w2.buf.view(-1), g_b2.buf.view(-1), mode, _ACT[act], p, _s64(seed), smooth)
         r_w2, r_b2 = g_w2.done(), g_b2.done()
         _C.colsum(dpre, g_b1.buf)
         r_b1 = g_b1.done()
@@ -1465,13 +1466,26 @@ class _SeqHead(torch.autograd.Function):
                 _C.gemm2(dpre, w1, dst, 0, 1, EPI_STORE, None, None, None, 0.0, 0, 0, None, None)  # reads W1 as is
             else:
                 dst.copy_(torch.mm(dpre, w1))
-        return dh, r_w1, r_b1, r_w2, r_b2, None, None, None, None, None, None, None, None
+        return dh, r_w1, r_b1, r_w2, r_b2, None, None, None, None, None, None, None, None, None
 
 
-def seq_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed, problem_type=None, tol=0.5):
+def _smoothing(label_smoothing) -> float:
+    """ε of a label-smoothed CE as the host constant the launches take (0 <= ε < 1)."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing {label_smoothing!r}: 0 <= label_smoothing < 1")
+    return eps
+
+
+def seq_head(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed, problem_type=None, tol=0.5,
+             label_smoothing: float = 0.0):
     """(loss, logits, stats) of the fused sequence-level head (labels required); stats = fp32 {mean loss, hits, rows
-    scored, loss sum} as ``reference.seq_loss`` defines them."""
-    return _SeqHead.apply(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed, _SEQ_MODE[problem_type], float(tol))
+    scored, loss sum} as ``reference.seq_loss`` defines them. ``label_smoothing`` (single-label CE only) selects the
+    kernels' smoothed instantiations; 0 launches the unsmoothed ones."""
+    mode, eps = _SEQ_MODE[problem_type], _smoothing(label_smoothing)
+    if eps and mode != 0:
+        raise ValueError(f"label_smoothing is for single-label classification, not problem_type {problem_type!r}")
+    return _SeqHead.apply(h, w1, b1, w2, b2, labels, act, p_in, seed_in, p, seed, mode, float(tol), eps)
 
 
 # ------------------------------------------------------------------------------------------ token-classification head
@@ -1510,7 +1524,7 @@ class _TokenHead(torch.autograd.Function):
     workspace) + the slab reducer that adds into main_grad."""
 
     @staticmethod
-    def forward(ctx, h2d, w, b, labels, p, seed):
+    def forward(ctx, h2d, w, b, labels, p, seed, smooth):
         R, H = h2d.shape
         C = w.shape[0]
         x = h2d.contiguous()
@@ -1519,9 +1533,9 @@ class _TokenHead(torch.autograd.Function):
         partials = torch.empty(_C.token_head_fwd_blocks(R) * 4, dtype=torch.float32, device=x.device)
         stats = torch.empty(4, dtype=torch.float32, device=x.device)
         lab = labels.contiguous().long()
-        _C.token_head_fwd(x, wc, bc, lab, logits, partials, stats, float(p), _s64(seed))
+        _C.token_head_fwd(x, wc, bc, lab, logits, partials, stats, float(p), _s64(seed), smooth)
         ctx.save_for_backward(x, w, b, logits, lab, stats)
-        ctx.cfg = (float(p), seed)
+        ctx.cfg = (float(p), seed, smooth)
         ctx.mark_non_differentiable(logits, stats)
         ctx.set_materialize_grads(False)
         return stats[0], logits, stats
@@ -1529,17 +1543,18 @@ class _TokenHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dlogits, _dstats):
         x, w, b, logits, lab, stats = ctx.saved_tensors
-        p, seed = ctx.cfg
+        p, seed, smooth = ctx.cfg
         g_w, g_b, dl, dh, part = _token_bwd_args(ctx, x, w, b, dloss)
         _C.token_head_bwd(x, w.contiguous(), logits, lab, stats, dl, dh, part, g_w.buf.view(-1), g_b.buf.view(-1),
-                          p, _s64(seed))
-        return dh, g_w.done(), g_b.done(), None, None, None
+                          p, _s64(seed), smooth)
+        return dh, g_w.done(), g_b.done(), None, None, None, None
 
 
-def token_head(h2d, w, b, labels, p, seed):
+def token_head(h2d, w, b, labels, p, seed, label_smoothing: float = 0.0):
     """(loss, logits, stats) of the fused token-classification head (labels [R] required); stats = fp32
-    {mean loss, argmax hits, rows scored, loss sum}."""
-    return _TokenHead.apply(h2d, w, b, labels, p, seed)
+    {mean loss, argmax hits, rows scored, loss sum}. ``label_smoothing`` > 0 launches the smoothed instantiations of
+    tok_fwd_kernel / tok_bwd_kernel."""
+    return _TokenHead.apply(h2d, w, b, labels, p, seed, _smoothing(label_smoothing))
 
 
 def token_head_logits(h2d, w, b, p, seed):
@@ -1630,12 +1645,13 @@ def mlm_head_ok(h2d, w1, wemb) -> bool:
             and _C.gemm2_supported(0, 0, EPI_BIAS, 64, Vp, H) and _C.gemm2_supported(0, 1, EPI_STORE, 64, H, Vp))
 
 
-def _mlm_fwd(ctx, x, rows, tgt, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
+def _mlm_fwd(ctx, x, rows, tgt, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, smooth=0.0):
     """The masked-LM head's forward chain on the selected rows ``x [rows, H]`` (a multiple of 64, ``tgt = -100`` on
     the padding rows): gemm2 NT with the bias + GELU epilogue -> LN -> gemm2 NT against the tied table -> xent over
     the real vocabulary columns, which also leaves dlogits / n_valid for the backward. ``n_valid``: fp32 [1] on the
     device, or the host count. ``rows`` is the caller's row map (saved for its own scatter of dh). Returns
-    (logits [rows, Vp], raw = fp32 {loss sum, argmax hits})."""
+    (logits [rows, Vp], raw = fp32 {loss sum, argmax hits}). ``smooth``: the CE's label smoothing over the ``vocab``
+    real classes (the padding columns keep their exact zero gradient)."""
     act = torch.empty_like(x)
     pre = gemm_fwd(x, w1, EPI_BIAS_GELU, bias=b1, out2=act)
     y, mean, rstd = _ln_fwd(act, ln_w, ln_b, eps)
@@ -1644,7 +1660,7 @@ def _mlm_fwd(ctx, x, rows, tgt, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vo
     if not torch.is_tensor(n_valid):
         n_valid = torch.full((1,), float(n_valid), dtype=torch.float32, device=x.device)
     dlogits = torch.empty_like(logits)
-    _C.xent(logits, tgt, dlogits, raw, n_valid, vocab)
+    _C.xent(logits, tgt, dlogits, raw, n_valid, vocab, smooth)
     ctx.save_for_backward(x, rows, w1, b1, pre, act, y, mean, rstd, ln_w, ln_b, wemb, bias, dlogits)
     return logits, raw
 
@@ -1688,7 +1704,7 @@ class _MlmHead(torch.autograd.Function):
               the masked rows' gradient into a zeroed dh."""
 
     @staticmethod
-    def forward(ctx, h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
+    def forward(ctx, h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, smooth):
         T, H = h2d.shape
         lab = labels.reshape(-1)
         sel = lab.ne(-100).nonzero(as_tuple=True)[0]
@@ -1699,7 +1715,7 @@ class _MlmHead(torch.autograd.Function):
         tgt = torch.full((npad,), -100, dtype=torch.long, device=h2d.device)
         tgt[:n] = lab.index_select(0, sel)
         x = h2d.index_select(0, idx)
-        logits, stats = _mlm_fwd(ctx, x, sel, tgt, n, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab)
+        logits, stats = _mlm_fwd(ctx, x, sel, tgt, n, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, smooth)
         loss = stats[0] * (1.0 / max(n, 1))
         ctx.cfg = (T, H, n)
         ctx.mark_non_differentiable(stats)
@@ -1715,12 +1731,14 @@ class _MlmHead(torch.autograd.Function):
             dh = torch.empty((T, H), dtype=dx.dtype, device=dx.device)
             _C.memset0(dh)
             dh.index_copy_(0, sel, dx[:n])
-        return (dh, None, g_w1.done(), g_b1.done(), g_lnw.done(), g_lnb.done(), None, r_wemb, g_bias.done(), None)
+        return (dh, None, g_w1.done(), g_b1.done(), g_lnw.done(), g_lnb.done(), None, r_wemb, g_bias.done(), None,
+                None)
 
 
-def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
-    """(loss, logits [n_masked, vocab], argmax hits) of the fused masked-LM head."""
-    return _MlmHead.apply(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab)
+def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, label_smoothing: float = 0.0):
+    """(loss, logits [n_masked, vocab], argmax hits) of the fused masked-LM head; ``label_smoothing`` is the CE
+    kernel's, over the ``vocab`` real classes."""
+    return _MlmHead.apply(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, _smoothing(label_smoothing))
 
 
 def mlm_mask(input_ids, attention_mask, labels_in, seed, p, mask_id, special_ids, rand_range, cap=None,
@@ -1770,10 +1788,10 @@ class _MlmHeadFixed(torch.autograd.Function):
     metric meter's fused protocol (train/trainer.py _Meter)."""
 
     @staticmethod
-    def forward(ctx, h2d, sel, tgt, inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
+    def forward(ctx, h2d, sel, tgt, inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, smooth):
         T, H = h2d.shape
         x = h2d.index_select(0, sel)
-        logits, raw = _mlm_fwd(ctx, x, inv, tgt, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab)
+        logits, raw = _mlm_fwd(ctx, x, inv, tgt, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, smooth)
         loss = raw[0] / n_valid[0].clamp(min=1.0)
         stats = torch.stack([loss, raw[1], n_valid[0], raw[0]])
         ctx.cfg = (T, H)
@@ -1790,27 +1808,31 @@ class _MlmHeadFixed(torch.autograd.Function):
             dh = torch.empty((T, H), dtype=dx.dtype, device=dx.device)
             _C.mlm_scatter_rows(dx, inv, dh)
         return (dh, None, None, None, None, g_w1.done(), g_b1.done(), g_lnw.done(), g_lnb.done(), None, r_wemb,
-                g_bias.done(), None)
+                g_bias.done(), None, None)
 
 
-def mlm_head_fixed(h2d, sel, tgt, inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab):
-    """(loss, logits [cap, vocab], stats) of the fixed-capacity masked-LM head."""
-    return _MlmHeadFixed.apply(h2d, sel, tgt, inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab)
+def mlm_head_fixed(h2d, sel, tgt, inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab,
+                   label_smoothing: float = 0.0):
+    """(loss, logits [cap, vocab], stats) of the fixed-capacity masked-LM head; ``label_smoothing`` as in
+    :func:`mlm_head`."""
+    return _MlmHeadFixed.apply(h2d, sel, tgt, inv, n_valid, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab,
+                               _smoothing(label_smoothing))
 
 
 # ------------------------------------------------------------------------------------------ loss
 class _CrossEntropy(torch.autograd.Function):
     """Mean softmax cross-entropy over non-ignored rows (-100) with the gradient produced by the same
-    kernel (xent.hip); also returns the argmax-correct count as a non-differentiable output."""
+    kernel (xent.hip); also returns the argmax-correct count as a non-differentiable output. ``smooth``: label
+    smoothing ε (target (1-ε)·onehot + ε/V); 0 launches the unsmoothed instantiation."""
 
     @staticmethod
-    def forward(ctx, logits, labels):
+    def forward(ctx, logits, labels, smooth=0.0):
         lg = logits.contiguous()
         lab = labels.contiguous().long()
         n_valid = lab.ne(-100).sum().to(torch.float32).reshape(1)
         stats = torch.zeros(2, dtype=torch.float32, device=lg.device)
         dl = torch.empty_like(lg) if ctx.needs_input_grad[0] else None
-        _C.xent(lg, lab, dl, stats, n_valid)
+        _C.xent(lg, lab, dl, stats, n_valid, 0, smooth)
         ctx.save_for_backward(dl if dl is not None else stats)
         loss = stats[0:1] / n_valid.clamp(min=1.0)
         ctx.mark_non_differentiable(stats)
@@ -1819,13 +1841,15 @@ class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dcorrect):
         (dl,) = ctx.saved_tensors
-        return dl * dloss.to(dl.dtype), None
+        return dl * dloss.to(dl.dtype), None, None
 
 
-def cross_entropy(logits, labels):
-    """(loss, correct_count) for [R, V] logits (bf16 / fp32) and int labels (-100 ignored)."""
+def cross_entropy(logits, labels, label_smoothing: float = 0.0):
+    """(loss, correct_count) for [R, V] logits (bf16 / fp32) and int labels (-100 ignored); ``label_smoothing`` ε in
+    [0, 1) smooths the target over the V classes (xent_kernel<…, kSmooth>)."""
+    eps = _smoothing(label_smoothing)
     if logits.dtype not in (torch.bfloat16, torch.float32) or logits.dim() != 2:
         from .reference import accuracy_count, cross_entropy as ref
 
-        return ref(logits, labels), accuracy_count(logits, labels)
-    return _CrossEntropy.apply(logits, labels)
+        return ref(logits, labels, eps), accuracy_count(logits, labels)
+    return _CrossEntropy.apply(logits, labels, eps)

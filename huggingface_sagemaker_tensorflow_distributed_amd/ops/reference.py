@@ -136,9 +136,13 @@ def attention_varlen(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: in
     return torch.cat(outs, dim=0)
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    """SparseCategoricalCrossentropy(from_logits=True), SUM_OVER_BATCH_SIZE (``scripts/train.py:118``)."""
-    return F.cross_entropy(logits.float(), labels.long())
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0) -> torch.Tensor:
+    """SparseCategoricalCrossentropy(from_logits=True), SUM_OVER_BATCH_SIZE (``scripts/train.py:118``).
+
+    ``label_smoothing`` ε in [0, 1) (HF ``LabelSmoother``, Keras ``label_smoothing=``): the target of a row is
+    ``(1-ε)·onehot + ε/C`` over the C classes, so its term is ``lse - (1-ε)·z[y] - (ε/C)·Σ_c z[c]`` and its gradient
+    ``softmax(z) - (1-ε)·onehot - ε/C``; ignored rows add nothing. Every CE in this module takes it the same way."""
+    return F.cross_entropy(logits.float(), labels.long(), label_smoothing=float(label_smoothing))
 
 
 def accuracy_count(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
@@ -159,11 +163,12 @@ def cls_head(x, w1, b1, w2, b2, act: str, p_in: float, seed_in: int, p: float, s
 PROBLEM_TYPES = ("single_label_classification", "multi_label_classification", "regression")
 
 
-def seq_loss(logits, labels, problem_type: Optional[str] = None, tol: float = 0.5):
+def seq_loss(logits, labels, problem_type: Optional[str] = None, tol: float = 0.5, label_smoothing: float = 0.0):
     """Loss and metric of the sequence-level head on ``logits`` [B, C] (HF ``*ForSequenceClassification`` with
     ``config.problem_type``) -> ``(loss, stats)``, ``stats`` = fp32 {mean loss, hits, n, loss sum}.
 
-    * ``None`` / ``"single_label_classification"``: labels int [B]; CE over the rows whose label is not -100;
+    * ``None`` / ``"single_label_classification"``: labels int [B]; CE over the rows whose label is not -100
+      (``label_smoothing`` as in :func:`cross_entropy`; the other two types refuse a non-zero one);
       hits = first-maximum argmax == label.
     * ``"multi_label_classification"``: labels float [B, C] in [0, 1]; per element
       ``max(z,0) - z·y + log1p(exp(-|z|))`` (``BCEWithLogitsLoss``); hits = rows with ``(z > 0) == (y > 0.5)`` for
@@ -174,9 +179,11 @@ def seq_loss(logits, labels, problem_type: Optional[str] = None, tol: float = 0.
     A float-label row whose FIRST label is NaN is ignored. ``n`` counts the other rows; the float losses are
     ``Σ_valid rows Σ_c term / (max(n, 1)·C)``: 0, not NaN, with zero gradients, when every row is ignored."""
     z = logits.float()
+    if label_smoothing and problem_type not in (None, "single_label_classification"):
+        raise ValueError(f"label_smoothing is for single-label classification, not problem_type {problem_type!r}")
     if problem_type in (None, "single_label_classification"):
         lab = labels.reshape(-1).long()
-        lsum = F.cross_entropy(z, lab, ignore_index=-100, reduction="sum")
+        lsum = F.cross_entropy(z, lab, ignore_index=-100, reduction="sum", label_smoothing=float(label_smoothing))
         with torch.no_grad():
             ok = lab.ne(-100)
             hits = ((z.argmax(dim=-1) == lab) & ok).sum().to(torch.float32)
@@ -206,17 +213,18 @@ def seq_loss(logits, labels, problem_type: Optional[str] = None, tol: float = 0.
     return loss, stats
 
 
-def token_head(h2d, w, b, labels, p: float, seed: int, training: bool = True):
+def token_head(h2d, w, b, labels, p: float, seed: int, training: bool = True, label_smoothing: float = 0.0):
     """Token-classification head on every row of ``h2d`` [R, H] (HF ``*ForTokenClassification``):
     ``logits = dropout(h) Wᵀ + b`` [R, C]; the dropout site is the flat ``[R, H]`` buffer. With ``labels`` [R]
     returns ``(loss, logits, stats)``: ``loss`` = CE summed over the rows whose label is not -100, divided by
     ``max(n_valid, 1)`` (0, not NaN, when every row is ignored), and ``stats`` = fp32 {mean loss, first-maximum argmax
-    hits, n_valid, loss sum}. Without labels: the logits."""
+    hits, n_valid, loss sum}. ``label_smoothing`` as in :func:`cross_entropy`. Without labels: the logits."""
     logits = F.linear(dropout(h2d, p, seed, training), w, b)
     if labels is None:
         return logits
     lab = labels.reshape(-1).long()
-    lsum = F.cross_entropy(logits.float(), lab, ignore_index=-100, reduction="sum")
+    lsum = F.cross_entropy(logits.float(), lab, ignore_index=-100, reduction="sum",
+                           label_smoothing=float(label_smoothing))
     with torch.no_grad():
         ok = lab.ne(-100)
         n = ok.sum().to(torch.float32)
@@ -327,11 +335,12 @@ def qa_head(h2d, w, b, positions, cu, row_mask, p: float, seed: int, max_answer_
     return loss, logits, stats, pred
 
 
-def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps: float, wemb, bias, vocab: int):
+def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps: float, wemb, bias, vocab: int, label_smoothing: float = 0.0):
     """RoBERTa LM head on the masked positions (labels != -100) of ``h2d`` [T, H]: ``LN(gelu(x W1ᵀ + b1))`` ->
-    tied decoder (``wemb[:vocab]``, ``bias[:vocab]``) -> mean CE. Returns (loss, logits [n_masked, vocab])."""
+    tied decoder (``wemb[:vocab]``, ``bias[:vocab]``) -> mean CE (``label_smoothing`` as in :func:`cross_entropy`,
+    over the ``vocab`` real classes). Returns (loss, logits [n_masked, vocab])."""
     sel = labels.ne(-100).nonzero(as_tuple=True)[0]
     x = h2d.index_select(0, sel)
     x = layer_norm(linear_gelu(x, w1, b1), ln_w, ln_b, eps)
     logits = F.linear(x, wemb[:vocab], bias[:vocab])
-    return cross_entropy(logits, labels.index_select(0, sel)), logits
+    return cross_entropy(logits, labels.index_select(0, sel), label_smoothing), logits

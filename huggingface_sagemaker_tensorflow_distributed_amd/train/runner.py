@@ -166,6 +166,20 @@ _QA_DATASETS = ("--task question-answering trains on --dataset synthetic or squa
                 "--dataset {} holds no answer spans")
 
 
+def _label_smoothing(args, task: str, ptype) -> float:
+    """``--label_smoothing_factor`` of the run, refused where no single-label cross-entropy is trained."""
+    eps = float(getattr(args, "label_smoothing_factor", 0.0) or 0.0)
+    if not 0.0 <= eps < 1.0:  # NaN fails both comparisons
+        raise ValueError(f"--label_smoothing_factor {eps} must be in [0, 1)")
+    if eps > 0.0 and task == "question-answering":
+        raise ValueError("--label_smoothing_factor smooths a single-label cross-entropy; --task question-answering "
+                         "trains a span loss, which it does not apply to")
+    if eps > 0.0 and ptype in ("regression", "multi_label_classification"):
+        raise ValueError(f"--label_smoothing_factor smooths a single-label cross-entropy; --problem_type {ptype} "
+                         f"trains {'an MSE' if ptype == 'regression' else 'a BCE-with-logits'} loss")
+    return eps
+
+
 def _conll_tags(args) -> Optional[List[str]]:
     """The tag list of ``--task token-classification --dataset conll`` (read once, kept on ``args``)."""
     if getattr(args, "task", "") != "token-classification" or args.dataset != "conll":
@@ -235,6 +249,13 @@ def _provenance(args, model, rank: int, n_train: int, n_eval: int, batch_plan=No
         else:
             info["metric"] = "cross-entropy loss and argmax accuracy"
         logger.info("sequence-classification problem_type %s; %d labels; %s", ptype, info["num_labels"], info["metric"])
+    eps = float(getattr(model, "label_smoothing", 0.0))
+    if eps > 0.0:
+        info["label_smoothing_factor"] = eps
+        if "metric" in info:
+            info["metric"] += (f"; the loss, in training and in evaluation, is the label-smoothed cross-entropy "
+                               f"(eps = {eps:g})")
+        logger.info("--label_smoothing_factor %g: training and evaluation report the smoothed cross-entropy", eps)
     if batch_plan is not None:
         info["auto_batch"] = batch_plan.as_dict()
     if synthetic or weights == "random-init":
@@ -276,6 +297,7 @@ def build(args, mode: str):
         raise ValueError(f"--problem_type {ptype} is valid only with --task sequence-classification, not --task {task}")
     if ptype in ("regression", "multi_label_classification") and args.dataset in ("imdb", "sst2"):
         raise ValueError(_PTYPE_DATASETS.format(ptype, args.dataset))
+    smoothing = _label_smoothing(args, task, ptype)
     tags = _conll_tags(args)
     if tags is not None:
         if args.num_labels != len(tags):
@@ -288,6 +310,7 @@ def build(args, mode: str):
         if not tol >= 0.0:
             raise ValueError(f"--regression_tolerance {tol} must be >= 0")
         model.regression_tolerance = tol
+    model.label_smoothing = smoothing  # a training argument on the model object (never in config.json)
     if tags is not None:
         model.cfg.id2label = {str(i): t for i, t in enumerate(tags)}  # config.json id2label / label2id
     model.to(dev)

@@ -155,6 +155,11 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
     g.add_argument("--regression_tolerance", type=float, default=0.5,
                    help="--problem_type regression: a row scores a hit when |prediction - target| <= this on every "
                         "target")
+    g.add_argument("--label_smoothing_factor", type=float, default=0.0,
+                   help="label smoothing of the cross-entropy (HF TrainingArguments.label_smoothing_factor, Keras "
+                        "label_smoothing=): the target becomes (1-eps)*onehot + eps/num_classes, in fit and in evaluate. "
+                        "0 <= eps < 1. For single-label sequence-classification, token-classification and masked-lm; "
+                        "question-answering and --problem_type regression / multi_label_classification refuse it")
     g.add_argument("--max_answer_length", type=int, default=30,
                    help="question-answering: the longest span (in tokens) the best-span search returns")
     g.add_argument("--doc_stride", type=int, default=128,

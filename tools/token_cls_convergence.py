@@ -4,6 +4,8 @@ FusedAdam at a constant learning rate. Writes one JSON line per 10 steps (traini
 and per 50 steps (held-out loss / token accuracy over 2,048 examples).
 
     python tools/token_cls_convergence.py OUT.jsonl VOCAB_SIZE STEPS LR      # profiles/token_cls: 256 600 3e-4
+    python tools/token_cls_convergence.py OUT.jsonl VOCAB_SIZE STEPS LR EPS  # + --label_smoothing_factor EPS (default 0):
+                                                                             # training and held-out loss are the smoothed one
 """
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,8 +18,10 @@ out = sys.argv[1]
 dev = torch.device("cuda", 0)
 L, S, B = 9, 128, 256
 V, STEPS, LR = int(sys.argv[2]), int(sys.argv[3]), float(sys.argv[4])
+EPS = float(sys.argv[5]) if len(sys.argv) > 5 else 0.0
 cfg = resolve_config("bert-base-uncased", num_labels=L).replace(num_hidden_layers=2, vocab_size=V)
 model = build_model(cfg, task="token-classification", seed=0).to(dev)
+model.label_smoothing = EPS
 store = FlatParamStore(model, dev, compute_dtype=torch.bfloat16)
 opt = FusedAdam(store, lr=LR)
 tr = hdata.synthetic_token_classification(B * STEPS, S, V, seed=0, num_labels=L)
@@ -36,6 +40,8 @@ def evaluate():
 with open(out, "w") as f:
     cfgline = {"config": {"model": "bert-base-uncased, 2 layers", "vocab_size": V, "num_labels": L, "seq_len": S, "batch": B,
                           "lr": LR, "optimizer": "FusedAdam", "dtype": "bf16", "head": "fused token_head.hip", "chance": 1.0 / L}}
+    if EPS:
+        cfgline["config"]["label_smoothing_factor"] = EPS
     f.write(json.dumps(cfgline) + "\n")
     model.train()
     for step in range(STEPS):
