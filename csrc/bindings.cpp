@@ -51,7 +51,7 @@ void stream_wait(int64_t dst_ptr, int64_t src_ptr) {
 void adam_step(torch::Tensor p, torch::Tensor m, torch::Tensor v, torch::Tensor g, c10::optional<torch::Tensor> out,
                c10::optional<torch::Tensor> decay, double step, double eps, double b1, double b2, double gscale,
                double lr_wd, c10::optional<torch::Tensor> coef, c10::optional<torch::Tensor> out_lo, bool zero_grad,
-               c10::optional<torch::Tensor> clip) {
+               c10::optional<torch::Tensor> clip, c10::optional<torch::Tensor> lr_mul) {
   CHECK_CUDA(p); CHECK_CONTIG(p); CHECK_DTYPE(p, torch::kFloat32);
   TORCH_CHECK(!zero_grad || g.is_contiguous(), "adam zero_grad: contiguous gradient");
   CHECK_DTYPE(m, torch::kFloat32); CHECK_DTYPE(v, torch::kFloat32);
@@ -88,9 +88,19 @@ void adam_step(torch::Tensor p, torch::Tensor m, torch::Tensor v, torch::Tensor 
     TORCH_CHECK(clip->numel() >= 1, "clip: fp32 [1]");
     dclip = clip->data_ptr<float>();
   }
+  // fp32 [numel / 64] on p's GPU: the learning-rate multiplier of each 64-element block of THIS slice (block_table)
+  const float* dmul = nullptr;
+  if (lr_mul.has_value()) {
+    TORCH_CHECK(lr_mul->is_cuda() && lr_mul->device() == p.device(), "lr_mul must be on the GPU of p");
+    TORCH_CHECK(lr_mul->scalar_type() == torch::kFloat32, "lr_mul must be fp32");
+    TORCH_CHECK(lr_mul->is_contiguous(), "lr_mul must be contiguous");
+    TORCH_CHECK(lr_mul->numel() == p.numel() / 64, "lr_mul: ", lr_mul->numel(), " entries, one per 64 elements = ",
+                p.numel() / 64, " needed");
+    dmul = lr_mul->data_ptr<float>();
+  }
   hsd::launch_adam(p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), g.data_ptr(), gbf, o, dm,
                    p.numel(), (float)step, (float)eps, (float)b1, (float)b2, (float)gscale, (float)lr_wd,
-                   dcoef, cur_stream(), lo, zero_grad, dclip);
+                   dcoef, cur_stream(), lo, zero_grad, dclip, dmul);
 }
 
 // Sum of squares of the gradient slice `g` (a contiguous, 64-aligned view into the flat gradient buffer): one fp32
@@ -182,7 +192,7 @@ void lamb_step(const LambPlan& plan, int64_t seg0, int64_t nsegs, torch::Tensor 
                torch::Tensor g, c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> out_lo,
                torch::Tensor partials, torch::Tensor ratio, double lr, double ibc1, double ibc2, double eps, double b1,
                double b2, double gscale, double wd, c10::optional<torch::Tensor> coef,
-               c10::optional<torch::Tensor> clip, bool zero_grad) {
+               c10::optional<torch::Tensor> clip, bool zero_grad, c10::optional<torch::Tensor> lr_mul) {
   auto flat = [&](const torch::Tensor& t, const char* name) {
     TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.device() == plan.tiles.device(), name,
                 ": contiguous tensor on the plan's GPU");
@@ -224,11 +234,20 @@ void lamb_step(const LambPlan& plan, int64_t seg0, int64_t nsegs, torch::Tensor 
     TORCH_CHECK(clip->numel() >= 1, "clip: fp32 [1]");
     dclip = clip->data_ptr<float>();
   }
+  const float* dmul = nullptr;  // fp32 [plan.nsegs] on the plan's GPU: each segment's learning-rate multiplier
+  if (lr_mul.has_value()) {
+    TORCH_CHECK(lr_mul->is_cuda() && lr_mul->device() == plan.tiles.device(), "lr_mul must be on the plan's GPU");
+    TORCH_CHECK(lr_mul->scalar_type() == torch::kFloat32, "lr_mul must be fp32");
+    TORCH_CHECK(lr_mul->is_contiguous(), "lr_mul must be contiguous");
+    TORCH_CHECK(lr_mul->numel() == plan.nsegs(), "lr_mul: ", lr_mul->numel(), " entries, one per segment = ",
+                plan.nsegs(), " needed");
+    dmul = lr_mul->data_ptr<float>();
+  }
   const int64_t t0 = plan.first_tile[seg0], t1 = plan.first_tile[seg0 + nsegs];
   hsd::launch_lamb(p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), g.data_ptr(), gbf, o, lo,
                    plan.tiles.data_ptr<int64_t>(), plan.segs.data_ptr<int64_t>(), t0, t1 - t0, seg0, nsegs,
                    partials.data_ptr<float>(), ratio.data_ptr<float>(), (float)lr, (float)ibc1, (float)ibc2, (float)eps,
-                   (float)b1, (float)b2, (float)gscale, (float)wd, dcoef, dclip, zero_grad, cur_stream());
+                   (float)b1, (float)b2, (float)gscale, (float)wd, dcoef, dclip, zero_grad, cur_stream(), dmul);
 }
 
 #define OPT_BF(o) ((o).has_value() ? reinterpret_cast<hsd::bf16_t*>((o)->data_ptr()) : nullptr)
@@ -1557,7 +1576,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_step", &adam_step, py::arg("p"), py::arg("m"), py::arg("v"), py::arg("g"), py::arg("out"),
         py::arg("decay"), py::arg("step"), py::arg("eps"), py::arg("b1"), py::arg("b2"), py::arg("gscale"),
         py::arg("lr_wd"), py::arg("coef") = py::none(), py::arg("out_lo") = py::none(), py::arg("zero_grad") = false,
-        py::arg("clip") = py::none());
+        py::arg("clip") = py::none(), py::arg("lr_mul") = py::none());
   m.def("grad_sumsq", &grad_sumsq, py::arg("g"), py::arg("partials"), py::arg("slot_base") = 0);
   m.def("grad_sumsq_blocks", [](int64_t n, bool bf16) { return (int64_t)hsd::grad_sumsq_blocks(n, bf16); });
   m.def("grad_clip_finalize", &grad_clip_finalize, py::arg("partials"), py::arg("nparts"), py::arg("gscale"),
@@ -1577,7 +1596,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v"), py::arg("g"), py::arg("out"), py::arg("out_lo"), py::arg("partials"), py::arg("ratio"),
         py::arg("lr"), py::arg("ibc1"), py::arg("ibc2"), py::arg("eps"), py::arg("b1"), py::arg("b2"),
         py::arg("gscale"), py::arg("wd"), py::arg("coef") = py::none(), py::arg("clip") = py::none(),
-        py::arg("zero_grad") = false);
+        py::arg("zero_grad") = false, py::arg("lr_mul") = py::none());
   m.def("ln_fwd_q8", &ln_fwd_q8);
   m.def("stream_wait", &stream_wait);
   m.def("gemm2_on", &gemm2_on);

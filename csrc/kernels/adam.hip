@@ -23,6 +23,13 @@ __device__ __forceinline__ f32x4 load_grad(const void* __restrict__ g_, int64_t 
   }
 }
 
+// A scalar that carries the learning rate, times a parameter's multiplier: one fp32 multiply the compiler may not fuse
+// into the operation that consumes it (kLrMul below).
+__device__ __forceinline__ float lr_scaled(float s, float mu) {
+#pragma clang fp contract(off)
+  return s * mu;
+}
+
 // kLo (fp32 compute, ops/hip32.py): `out` / `out_lo` receive the bf16 hi / lo halves of the updated weight (hi =
 // bf16(θ), lo = bf16(θ - hi), exactly split2's), which the split-product GEMMs read directly -- the weights are split
 // once per optimizer step instead of at every use in forward and backward.
@@ -35,14 +42,21 @@ __device__ __forceinline__ f32x4 load_grad(const void* __restrict__ g_, int64_t 
 // kClip (launched when `clip` is given): an instantiation of its own for clipped steps. As a run-time branch the one
 // extra load cost the unclipped bf16-compute kernel 4 VGPRs and a wave of occupancy (72 -> 76, 7 -> 6 waves/SIMD) and
 // the headline 0.2-0.7 % (profiles/grad_clip_cost.log); this way the unclipped kernels keep the code they had.
-template <bool kGradBf16, bool kWriteBf16, int U, bool kLo = false, bool kClip = false>
+// kLrMul (launched when `lr_mul` is given; optim/groups.py, --layerwise_lr_decay): per-parameter learning-rate
+// multipliers, an fp32 table with one entry per 64-element block indexed as `decay` is. The learning rate appears in
+// `step` and in `lr_wd`; each is scaled by ONE fp32 multiply (lr_scaled: never contracted into the 1 - lr_wd that
+// follows), so a segment gets the bits the kernel without the table gives it when launched on that segment alone with
+// the host scalars float32(step * mu), float32(lr_wd * mu), and a table of ones gives the bits of no table. An
+// instantiation of its own for kClip's reason: the kernels without the table keep the code they had.
+template <bool kGradBf16, bool kWriteBf16, int U, bool kLo = false, bool kClip = false, bool kLrMul = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ m,
                                                    float* __restrict__ v, void* __restrict__ g_,
                                                    bf16_t* __restrict__ out, const uint8_t* __restrict__ decay,
                                                    int64_t n4, float step, float eps, float b1, float b2,
                                                    float gscale, float lr_wd, const float* __restrict__ coef,
                                                    bf16_t* __restrict__ out_lo, int zero_g,
-                                                   const float* __restrict__ clip) {
+                                                   const float* __restrict__ clip,
+                                                   const float* __restrict__ lr_mul) {
   if (coef != nullptr) {  // HIP-graph replays: this step's scalars live on the device (train/graph.py)
     step = coef[0];
     eps = coef[1];
@@ -55,10 +69,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += stride * U) {
     f32x4 g[U], pp[U], mm[U], vv[U];
+    float mu[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t i = i0 + u * stride;
       if (i < n4) {
+        if constexpr (kLrMul) mu[u] = lr_mul[(i * 4) >> 6];
         g[u] = load_grad<kGradBf16, kWriteBf16>(g_, i);
         pp[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + i);
         mm[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m) + i);
@@ -70,13 +86,18 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
       const int64_t i = i0 + u * stride;
       if (i >= n4) break;
       float wdf = 1.0f;
-      if (decay != nullptr && lr_wd != 0.0f) wdf = decay[(i * 4) >> 6] ? (1.0f - lr_wd) : 1.0f;
+      float step_g = step, lrwd_g = lr_wd;
+      if constexpr (kLrMul) {
+        step_g = lr_scaled(step, mu[u]);
+        lrwd_g = lr_scaled(lr_wd, mu[u]);
+      }
+      if (decay != nullptr && lr_wd != 0.0f) wdf = decay[(i * 4) >> 6] ? (1.0f - lrwd_g) : 1.0f;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float gk = g[u][k] * gscale;
         mm[u][k] = b1 * mm[u][k] + (1.0f - b1) * gk;
         vv[u][k] = b2 * vv[u][k] + (1.0f - b2) * gk * gk;
-        pp[u][k] = pp[u][k] * wdf - step * mm[u][k] / (sqrtf(vv[u][k]) + eps);
+        pp[u][k] = pp[u][k] * wdf - step_g * mm[u][k] / (sqrtf(vv[u][k]) + eps);
       }
       __builtin_nontemporal_store(pp[u], reinterpret_cast<f32x4*>(p) + i);
       __builtin_nontemporal_store(mm[u], reinterpret_cast<f32x4*>(m) + i);
@@ -104,19 +125,23 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
 void launch_adam(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* out_bf16,
                  const uint8_t* decay, int64_t n, float step, float eps, float b1, float b2, float gscale,
                  float lr_wd, const float* coef, hipStream_t stream, bf16_t* out_lo, bool zero_grad,
-                 const float* clip) {
+                 const float* clip, const float* lr_mul) {
   const int zg = zero_grad ? 1 : 0;
   int64_t n4 = n / 4;  // n is a multiple of 1024 (FlatParamStore)
   int threads = 256;
   int64_t blocks = (n4 + threads - 1) / threads;
   if (blocks > 256 * 8) blocks = 256 * 8;  // grid-stride: 8 blocks (32 waves) per CU over 256 CUs
   // two 16-B chunks per thread per trip (1 and 4 measured slower: profiles/bench_adam_r2.json)
-#define HSD_ADAM_K(GB, WB, LO, CL)                                                                                  \
-  hipLaunchKernelGGL((adam_kernel<GB, WB, 2, LO, CL>), dim3((unsigned)blocks), dim3(threads), 0, stream, p, m, v, \
-                     g, out_bf16, decay, n4, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zg, clip)
+#define HSD_ADAM_K(GB, WB, LO, CL, LM)                                                                              \
+  hipLaunchKernelGGL((adam_kernel<GB, WB, 2, LO, CL, LM>), dim3((unsigned)blocks), dim3(threads), 0, stream, p, m, \
+                     v, g, out_bf16, decay, n4, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zg, clip, lr_mul)
+#define HSD_ADAM_C(GB, WB, LO, LM)                                                                                  \
+  do {                                                                                                              \
+    if (clip != nullptr) HSD_ADAM_K(GB, WB, LO, true, LM); else HSD_ADAM_K(GB, WB, LO, false, LM);                 \
+  } while (0)
 #define HSD_ADAM(GB, WB, LO)                                                                                        \
   do {                                                                                                              \
-    if (clip != nullptr) HSD_ADAM_K(GB, WB, LO, true); else HSD_ADAM_K(GB, WB, LO, false);                         \
+    if (lr_mul != nullptr) HSD_ADAM_C(GB, WB, LO, true); else HSD_ADAM_C(GB, WB, LO, false);                       \
   } while (0)
   if (out_lo != nullptr) {
     if (out_bf16 == nullptr) abort();
@@ -130,6 +155,7 @@ void launch_adam(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* 
     if (out_bf16) HSD_ADAM(false, true, false); else HSD_ADAM(false, false, false);
   }
 #undef HSD_ADAM
+#undef HSD_ADAM_C
 #undef HSD_ADAM_K
   HSD_CHECK_LAUNCH();
 }

@@ -3,7 +3,7 @@
 //   m = b1 m + (1-b1) g ;  v = b2 v + (1-b2) g² ;  m̂ = m / (1-b1ᵗ) ;  v̂ = v / (1-b2ᵗ)
 //   u = m̂ / (√v̂ + eps)  [+ wd · w on segments with decay]
 //   r = ‖w‖₂ / ‖u‖₂ if ‖w‖₂ > 0 and ‖u‖₂ > 0 else 1     per segment (r = 1 and no decay on excluded segments)
-//   w -= lr · r · u
+//   w -= lr · r · u                                       (lr · μ with per-segment multipliers: lamb_stage2's kLrMul)
 //
 // The norms are per parameter (segment), so a slice of whole segments is stepped on its own (under the backward). Each
 // segment's 64-aligned span is cut into tiles of kLambTile elements anchored at the segment's own offset (the last one
@@ -182,18 +182,25 @@ __global__ __launch_bounds__(kLambRatioThreads) void lamb_ratio_kernel(const flo
 }
 
 // kWriteBf16 / kLo: the bf16 compute copy, or the fp32 run's hi / lo halves, exactly as adam_kernel writes them.
-template <bool kWriteBf16, bool kLo>
+// kLrMul (launched when `lr_mul` is given; optim/groups.py, --layerwise_lr_decay): fp32 [segments], the tile's segment
+// takes the learning rate lr * lr_mul[seg], ONE fp32 multiply ahead of the existing lr * r -- the bits of a launch
+// without the table on that segment alone with the host scalar float32(lr * mu). u, the norms and r do not see it. An
+// instantiation of its own (adam_kernel's kClip): the kernels without the table keep the code they had.
+template <bool kWriteBf16, bool kLo, bool kLrMul = false>
 __global__ __launch_bounds__(kLambThreads) void lamb_stage2_kernel(
     float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v, bf16_t* __restrict__ out,
     bf16_t* __restrict__ out_lo, const int64_t* __restrict__ tiles, const int64_t* __restrict__ segs, int64_t tile0,
-    const float* __restrict__ ratio, LambScalars s, const float* __restrict__ coef) {
+    const float* __restrict__ ratio, LambScalars s, const float* __restrict__ coef,
+    const float* __restrict__ lr_mul) {
   s = lamb_scalars(s, coef);
   const int64_t t = tile0 + blockIdx.x;
   const int64_t base4 = tiles[t * 3] >> 2;
   const int n4 = (int)(tiles[t * 3 + 1] >> 2);
   const int64_t seg = tiles[t * 3 + 2];
   const float wd = segs[seg * 3 + 2] ? s.wd : 0.0f;
-  const float step = s.lr * ratio[seg * 3];
+  float lr = s.lr;
+  if constexpr (kLrMul) lr *= lr_mul[seg];
+  const float step = lr * ratio[seg * 3];
   for (int i0 = threadIdx.x; i0 < n4; i0 += kLambThreads * kLambU) {
     f32x4 pp[kLambU], mm[kLambU], vv[kLambU];
 #pragma unroll
@@ -234,7 +241,8 @@ __global__ __launch_bounds__(kLambThreads) void lamb_stage2_kernel(
 void launch_lamb(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* out_bf16, bf16_t* out_lo,
                  const int64_t* tiles, const int64_t* segs, int64_t tile0, int64_t ntiles, int64_t seg0, int64_t nsegs,
                  float* partials, float* ratio, float lr, float ibc1, float ibc2, float eps, float b1, float b2,
-                 float gscale, float wd, const float* coef, const float* clip, bool zero_grad, hipStream_t stream) {
+                 float gscale, float wd, const float* coef, const float* clip, bool zero_grad, hipStream_t stream,
+                 const float* lr_mul) {
   if (ntiles <= 0 || nsegs <= 0) return;
   if (out_lo != nullptr && out_bf16 == nullptr) abort();
   const LambScalars s{lr, ibc1, ibc2, eps, gscale, wd};
@@ -253,13 +261,18 @@ void launch_lamb(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* 
   hipLaunchKernelGGL(lamb_ratio_kernel, dim3((unsigned)nsegs), dim3(kLambRatioThreads), 0, stream, partials, segs,
                      seg0, ratio);
   HSD_CHECK_LAUNCH();
-#define HSD_LAMB2(WB, LO)                                                                                          \
-  hipLaunchKernelGGL((lamb_stage2_kernel<WB, LO>), grid, block, 0, stream, p, m, v, out_bf16, out_lo, tiles, segs, \
-                     tile0, ratio, s, coef)
+#define HSD_LAMB2_K(WB, LO, LM)                                                                                   \
+  hipLaunchKernelGGL((lamb_stage2_kernel<WB, LO, LM>), grid, block, 0, stream, p, m, v, out_bf16, out_lo, tiles, \
+                     segs, tile0, ratio, s, coef, lr_mul)
+#define HSD_LAMB2(WB, LO)                                                                                         \
+  do {                                                                                                            \
+    if (lr_mul != nullptr) HSD_LAMB2_K(WB, LO, true); else HSD_LAMB2_K(WB, LO, false);                           \
+  } while (0)
   if (out_lo != nullptr) HSD_LAMB2(true, true);
   else if (out_bf16 != nullptr) HSD_LAMB2(true, false);
   else HSD_LAMB2(false, false);
 #undef HSD_LAMB2
+#undef HSD_LAMB2_K
   HSD_CHECK_LAUNCH();
 }
 

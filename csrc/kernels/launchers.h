@@ -14,7 +14,8 @@ struct DropoutParams;
 void launch_adam(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* out_bf16,
                  const uint8_t* decay, int64_t n, float step, float eps, float b1, float b2, float gscale,
                  float lr_wd, const float* coef, hipStream_t stream,
-                 bf16_t* out_lo = nullptr, bool zero_grad = false, const float* clip = nullptr);
+                 bf16_t* out_lo = nullptr, bool zero_grad = false, const float* clip = nullptr,
+                 const float* lr_mul = nullptr);  // fp32 [n / 64]: learning-rate multiplier per 64-element block
 
 // gradnorm.hip: global-norm gradient clipping. grad_sumsq writes grad_sumsq_blocks(n, bf16) fp32 partials (one per
 // block, no atomics) for n gradients (a multiple of 64, 16-B aligned); finalize turns `nparts` partials into
@@ -30,12 +31,14 @@ void launch_grad_clip_finalize(const float* partials, int64_t nparts, float gsca
 // tile, tiles, adapt / decay flag); a tile is at most lamb_tile() elements and never straddles two segments. Three
 // launches: moments + per-tile (Σw², Σu²) into partials[2 tile ...], per-segment (r, Σw², Σu²) into ratio[3 seg ...],
 // then the weight update (with the bf16 copy, or the hi / lo halves). coef: fp32 [8] on the device (lr, 1/(1-b1ᵗ),
-// 1/(1-b2ᵗ), eps, grad_scale, wd, -, -) overriding the scalars; clip: fp32 [1] multiplied into grad_scale.
+// 1/(1-b2ᵗ), eps, grad_scale, wd, -, -) overriding the scalars; clip: fp32 [1] multiplied into grad_scale; lr_mul:
+// fp32 [segments], each segment's learning-rate multiplier (indexed by global segment id; the weight update only).
 int lamb_tile();
 void launch_lamb(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* out_bf16, bf16_t* out_lo,
                  const int64_t* tiles, const int64_t* segs, int64_t tile0, int64_t ntiles, int64_t seg0, int64_t nsegs,
                  float* partials, float* ratio, float lr, float ibc1, float ibc2, float eps, float b1, float b2,
-                 float gscale, float wd, const float* coef, const float* clip, bool zero_grad, hipStream_t stream);
+                 float gscale, float wd, const float* coef, const float* clip, bool zero_grad, hipStream_t stream,
+                 const float* lr_mul = nullptr);
 
 }  // namespace hsd
 

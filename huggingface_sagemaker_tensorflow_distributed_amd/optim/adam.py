@@ -28,17 +28,28 @@ the norm on the device (no host round trip: a captured whole-step graph replays 
 buffer that reads the coefficient from device memory. Data-parallel ranks take the norm over the all-reduced buffer,
 which holds the same values on every rank (also with a bf16 / fp16 wire: every rank casts back the same reduced
 values), so they agree on ``coef`` bit for bit without another collective.
+
+Per-parameter learning rates (``lr_multipliers``; ``--layerwise_lr_decay`` / ``--head_lr_multiplier``, optim/groups.py):
+every segment has a multiplier ``μ > 0`` and is stepped with ``lr·μ`` in both places the learning rate appears,
+``θ = θ·(1 - (lr·wd)·μ·mask) - (step·μ)·m/(√v + ε)``; ``m`` and ``v`` do not see it. ``μ`` is rounded to fp32 once and
+the kernel scales ``step`` and ``lr·wd`` by ONE fp32 multiply each, reading ``μ`` from an fp32 table with one entry per
+64-element block (:meth:`FlatParamStore.block_table`), so a segment gets the bits of a step on that segment alone with
+``float32(step·μ)`` and ``float32(lr·wd·μ)``. The schedule keeps scaling :attr:`lr`; ``μ`` multiplies whatever it is
+at that step. ``None`` or all ones is off: no table, the launches without it.
 """
 from __future__ import annotations
 
 import contextlib
+import logging
 import math
 import os
-from typing import Callable, Iterable, List, Optional, Tuple
+from typing import Callable, Dict, Iterable, List, Optional, Tuple
 
 import torch
 
 from ..parallel.flat_params import ALIGN, FlatParamStore
+
+logger = logging.getLogger(__name__)
 
 
 class FusedAdam:
@@ -48,7 +59,7 @@ class FusedAdam:
 
     def __init__(self, store: FlatParamStore, lr: float = 1e-3, betas=(0.9, 0.999), eps: Optional[float] = None,
                  weight_decay: float = 0.0, eps_mode: str = "keras", decoupled: bool = True,
-                 max_grad_norm: float = 0.0):
+                 max_grad_norm: float = 0.0, lr_multipliers=None):
         if eps_mode not in ("keras", "torch"):
             raise ValueError(eps_mode)
         if not float(max_grad_norm) >= 0.0:
@@ -77,6 +88,46 @@ class FusedAdam:
         if self.max_grad_norm > 0.0:
             self._clip_out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=store.master.device)
             self._plan_clip([])
+        # per-parameter learning-rate multipliers: fp32, one per segment (None = off), and the device table the kernels
+        # read, built once at an address that stays put (captured graphs replay launches that read it)
+        self._mu = self._resolve_multipliers(lr_multipliers)
+        self._lr_mul: Optional[torch.Tensor] = None
+        self._mu_elem: Optional[torch.Tensor] = None  # CPU path: the multiplier of every element
+        if self._mu is not None:
+            self._build_lr_table()
+
+    # -------------------------------------------------------------------------- per-parameter learning rates
+    def _resolve_multipliers(self, given) -> Optional[torch.Tensor]:
+        """``given`` ({segment name: μ} or a sequence in segment order) as an fp32 tensor [segments]; None when it is
+        None or all ones."""
+        if given is None:
+            return None
+        names = self.store.names
+        if isinstance(given, dict):
+            missing = [n for n in names if n not in given]
+            if missing:
+                raise ValueError(f"lr_multipliers: no multiplier for {len(missing)} segment(s), e.g. {missing[:3]}")
+            vals = [float(given[n]) for n in names]
+        else:
+            vals = [float(x) for x in given]
+            if len(vals) != len(names):
+                raise ValueError(f"lr_multipliers: {len(vals)} values for {len(names)} segments")
+        mu = torch.tensor(vals, dtype=torch.float64).to(torch.float32)  # rounded to fp32 once
+        bad = [n for n, x in zip(names, mu.tolist()) if not (x > 0.0 and math.isfinite(x))]
+        if bad:
+            raise ValueError(f"lr_multipliers must be finite and > 0 in fp32 (freezing is not supported): {bad[:3]}")
+        return None if bool((mu == 1.0).all()) else mu
+
+    def _build_lr_table(self) -> None:
+        """Adam's table: one fp32 entry per 64-element block (alignment padding and the tail hold 1)."""
+        self._lr_mul = self.store.block_table(self._mu.tolist(), ALIGN)
+
+    def _lr_mul_slice(self, st: int, e: int) -> Optional[torch.Tensor]:
+        return self._lr_mul[st // ALIGN:(e + ALIGN - 1) // ALIGN] if self._lr_mul is not None else None
+
+    def lr_multipliers(self) -> Optional[Dict[str, float]]:
+        """``{segment name: μ}`` (the fp32 values the step uses), or None when off."""
+        return dict(zip(self.store.names, self._mu.tolist())) if self._mu is not None else None
 
     # -------------------------------------------------------------------------- global-norm clipping
     @property
@@ -124,7 +175,7 @@ class FusedAdam:
         out, out_lo = s.adam_outputs(0, s.numel)
         hip.adam_step(s.master, self.exp_avg, self.exp_avg_sq, s.grad, out, self._decay_mask, step, eps_eff,
                       self.beta1, self.beta2, gscale, self.lr * self.weight_decay, self._kernel_coef(), out_lo,
-                      zero_grad=zero_grad, clip=self._clip_out[1:2])
+                      zero_grad=zero_grad, clip=self._clip_out[1:2], lr_mul=self._lr_mul)
         s.refresh_transposed()
 
     # --------------------------------------------------------------------------
@@ -132,9 +183,12 @@ class FusedAdam:
         return [self.exp_avg, self.exp_avg_sq]
 
     def state_dict(self) -> dict:
-        return {"step": self.step_count, "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(),
-                "lr": self.lr, "betas": (self.beta1, self.beta2), "eps": self.eps, "eps_mode": self.eps_mode,
-                "weight_decay": self.weight_decay}
+        sd = {"step": self.step_count, "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(),
+              "lr": self.lr, "betas": (self.beta1, self.beta2), "eps": self.eps, "eps_mode": self.eps_mode,
+              "weight_decay": self.weight_decay}
+        if self._mu is not None:
+            sd["lr_multipliers"] = self.lr_multipliers()
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         # states of other optimizers over the same buffers (optim/lamb.py) carry their "kind"; Adam's own carry none
@@ -145,6 +199,13 @@ class FusedAdam:
         self.step_count = int(sd["step"])
         self.exp_avg.copy_(sd["exp_avg"].to(self.exp_avg.device))
         self.exp_avg_sq.copy_(sd["exp_avg_sq"].to(self.exp_avg_sq.device))
+        was = sd.get("lr_multipliers")
+        if was is not None and all(float(x) == 1.0 for x in was.values()):
+            was = None
+        if was != self.lr_multipliers():
+            logger.warning("the checkpoint was written with %s and this optimizer runs with %s: the current "
+                           "--layerwise_lr_decay / --head_lr_multiplier win", _describe_mul(was),
+                           _describe_mul(self.lr_multipliers()))
 
     def _coeffs(self):
         t = self.step_count
@@ -253,7 +314,7 @@ class FusedAdam:
         dm = self._decay_mask[st // ALIGN:(e + ALIGN - 1) // ALIGN] if self._decay_mask is not None else None
         hip.adam_step(s.master[st:e], self.exp_avg[st:e], self.exp_avg_sq[st:e], s.grad[st:e], out, dm, step,
                       eps_eff, self.beta1, self.beta2, gscale, self.lr * self.weight_decay, self._kernel_coef(), out_lo,
-                      zero_grad=getattr(self, "_zero", False))
+                      zero_grad=getattr(self, "_zero", False), lr_mul=self._lr_mul_slice(st, e))
         if self._tsub is not None:
             s.refresh_transposed_subset(self._tsub[b])
         if self._f8sub is not None:
@@ -306,7 +367,8 @@ class FusedAdam:
             out, out_lo = s.adam_outputs(0, s.numel)
             hip.adam_step(s.master, self.exp_avg, self.exp_avg_sq, s.grad, out,
                           self._decay_mask, step, eps_eff, self.beta1, self.beta2, float(grad_scale),
-                          self.lr * self.weight_decay, self._kernel_coef(), out_lo, zero_grad=zero_grad)
+                          self.lr * self.weight_decay, self._kernel_coef(), out_lo, zero_grad=zero_grad,
+                          lr_mul=self._lr_mul)
             s.refresh_transposed()
             return
         # reference path (CPU): identical math on flat buffers
@@ -319,14 +381,34 @@ class FusedAdam:
             self._clip_out[0], self._clip_out[1] = norm, coef
             grad_scale = float(gs32 * self._clip_out[1])
         g = g * grad_scale
+        mu = None
+        if self._mu is not None:
+            # the kernel's rounding: step and lr * wd as fp32 scalars, each times the element's fp32 multiplier
+            if self._mu_elem is None:
+                self._mu_elem = self._lr_mul.repeat_interleave(ALIGN)[: s.numel]
+            mu = self._mu_elem
         if self.weight_decay:
             wd = self._decay_mask.repeat_interleave(ALIGN)[: s.numel].to(torch.float32)
-            s.master.mul_(1.0 - self.lr * self.weight_decay * wd)
+            if mu is None:
+                s.master.mul_(1.0 - self.lr * self.weight_decay * wd)
+            else:
+                s.master.mul_(1.0 - torch.tensor(self.lr * self.weight_decay, dtype=torch.float32) * mu * wd)
         self.exp_avg.mul_(self.beta1).add_(g, alpha=1.0 - self.beta1)
         self.exp_avg_sq.mul_(self.beta2).addcmul_(g, g, value=1.0 - self.beta2)
-        s.master.addcdiv_(self.exp_avg, self.exp_avg_sq.sqrt().add_(eps_eff), value=-step)
+        if mu is None:
+            s.master.addcdiv_(self.exp_avg, self.exp_avg_sq.sqrt().add_(eps_eff), value=-step)
+        else:
+            s.master.sub_((torch.tensor(step, dtype=torch.float32) * mu) * self.exp_avg
+                          / self.exp_avg_sq.sqrt().add_(eps_eff))
         if write_compute:
             s.compute.copy_(s.master)
+
+
+def _describe_mul(mul: Optional[Dict[str, float]]) -> str:
+    if mul is None:
+        return "no learning-rate multipliers"
+    v = list(mul.values())
+    return f"learning-rate multipliers in [{min(v):.6g}, {max(v):.6g}]"
 
 
 def plan_ranges(store: FlatParamStore, bucket_mb: float) -> Tuple[List[Tuple[int, int]], List[int]]:

@@ -18,6 +18,9 @@ the gradient averaged over ranks and accumulation micro-steps (``grad_scale · g
   uses the bias-corrected form above.
 * Tied weights are one parameter, so one segment. The alignment padding between segments is zero in ``master``,
   ``grad``, ``m`` and ``v``; it yields ``u = 0`` and contributes to no norm.
+* Per-parameter learning rates (``lr_multipliers``, as :class:`FusedAdam`'s): ``w ← w − ((lr·μ)·r)·u`` with ``μ``
+  the segment's fp32 multiplier. ``u``, the norms and ``r`` do not depend on ``μ``: the ``(r, Σw², Σu²)`` table a step
+  writes is the same bits with and without multipliers. The kernel reads ``μ`` from an fp32 ``[segments]`` table.
 * The Horovod-style scripts keep multiplying the learning rate by the world size (``train/runner.py``); LAMB does not
   change that rule.
 
@@ -50,9 +53,9 @@ class FusedLamb(FusedAdam):
     kind = "lamb"
 
     def __init__(self, store: FlatParamStore, lr: float = 1e-3, betas=(0.9, 0.999), eps: Optional[float] = None,
-                 weight_decay: float = 0.0, max_grad_norm: float = 0.0):
+                 weight_decay: float = 0.0, max_grad_norm: float = 0.0, lr_multipliers=None):
         super().__init__(store, lr=lr, betas=betas, eps=1e-6 if eps is None else eps, weight_decay=weight_decay,
-                         eps_mode="keras", max_grad_norm=max_grad_norm)
+                         eps_mode="keras", max_grad_norm=max_grad_norm, lr_multipliers=lr_multipliers)
         segs = store.segments
         dev = store.master.device
         self._spans = [(segs[i + 1].offset if i + 1 < len(segs) else (s.offset + s.numel + ALIGN - 1) // ALIGN * ALIGN)
@@ -71,6 +74,10 @@ class FusedLamb(FusedAdam):
             self._plan = hip.lamb_plan([s.offset for s in segs], self._spans, [s.decay for s in segs], store.numel,
                                        store.master)
             self._partials = torch.zeros(2 * self._plan.ntiles, dtype=torch.float32, device=dev)
+
+    def _build_lr_table(self) -> None:
+        """LAMB's table: one fp32 entry per segment (the weight-update kernel knows each tile's segment)."""
+        self._lr_mul = self._mu.to(self.store.master.device)
 
     # -------------------------------------------------------------------------- trust ratios
     @property
@@ -140,7 +147,7 @@ class FusedLamb(FusedAdam):
         out, out_lo = s.adam_outputs(0, s.numel)
         hip.lamb_step(self._plan, seg0, nsegs, s.master, self.exp_avg, self.exp_avg_sq, s.grad, out, out_lo,
                       self._partials, self._ratio, self.lr, ibc1, ibc2, self.eps, self.beta1, self.beta2, gscale,
-                      self.weight_decay, self._kernel_coef(), clip, zero_grad)
+                      self.weight_decay, self._kernel_coef(), clip, zero_grad, lr_mul=self._lr_mul)
 
     @torch.no_grad()
     def step_range(self, b: int) -> None:
@@ -220,6 +227,9 @@ class FusedLamb(FusedAdam):
                 if wn > 0.0 and un > 0.0:  # a NaN norm compares false: r = 1
                     r = wn / un
             self._ratio[i, 0] = r
-            w.sub_(u * float(torch.tensor(self.lr, dtype=torch.float32) * self._ratio[i, 0]))
+            lr = torch.tensor(self.lr, dtype=torch.float32)
+            if self._mu is not None:
+                lr = lr * self._mu[i]  # the kernel's rounding: fp32 lr times the fp32 multiplier, then times r
+            w.sub_(u * float(lr * self._ratio[i, 0]))
         if s.compute is not s.master:
             s.compute.copy_(s.master)

@@ -385,6 +385,19 @@ class FlatParamStore:
                 m[s.offset // block: (s.offset + s.numel + block - 1) // block] = 1
         return m.to(self.device)
 
+    def block_table(self, per_segment_values, block: int = ALIGN) -> torch.Tensor:
+        """fp32 per ``block`` elements: segment ``i``'s blocks hold ``per_segment_values[i]`` (rounded to fp32 once);
+        alignment padding and the tail hold 1.0. The fp32 analogue of :meth:`decay_block_mask` (the optimizers'
+        per-parameter learning-rate multipliers)."""
+        assert block % ALIGN == 0 or ALIGN % block == 0
+        vals = [float(x) for x in per_segment_values]
+        if len(vals) != len(self.segments):
+            raise ValueError(f"block_table: {len(vals)} values for {len(self.segments)} segments")
+        t = torch.ones(self.numel // block, dtype=torch.float32)
+        for s, x in zip(self.segments, vals):
+            t[s.offset // block: (s.offset + s.numel + block - 1) // block] = x
+        return t.to(self.device)
+
     def state_dict(self) -> dict:
         return {"master": self.master.detach().cpu(), "names": list(self.names),
                 "offsets": [s.offset for s in self.segments]}

@@ -25,6 +25,7 @@ from .. import data as hdata
 from .. import ops
 from ..models import from_pretrained, save_pretrained
 from ..optim import FusedAdam, FusedLamb
+from ..optim import groups as lr_groups
 from ..parallel.ddp import resolve_compression
 from ..parallel.flat_params import keep_transposed_weights
 from ..parallel import FlatParamStore, GradBucketer, ShardSampler, backend, broadcast_parameters
@@ -180,6 +181,24 @@ def _label_smoothing(args, task: str, ptype) -> float:
     return eps
 
 
+def _lr_group_flags(args):
+    """``(--layerwise_lr_decay, --head_lr_multiplier)`` of the run, refused outside (0, 1] and finite > 0."""
+    return lr_groups.validate(getattr(args, "layerwise_lr_decay", 1.0), getattr(args, "head_lr_multiplier", 1.0))
+
+
+def _lr_multipliers(args, store, cfg, lr: float):
+    """The run's per-parameter learning-rate multipliers ({segment name: μ}; None = both flags at 1), with the startup
+    table: depth, μ, the learning rate after the world-size rule, parameters."""
+    decay, head = _lr_group_flags(args)
+    mul = lr_groups.lr_multipliers(store.names, cfg.num_hidden_layers, decay, head)
+    if mul is not None:
+        rows = lr_groups.depth_table(store.names, [sg.numel for sg in store.segments], cfg.num_hidden_layers, decay,
+                                     head, lr)
+        logger.info("--layerwise_lr_decay %g --head_lr_multiplier %g: learning rate per depth (base %g)\n%s", decay,
+                    head, lr, lr_groups.format_table(rows))
+    return mul
+
+
 def _conll_tags(args) -> Optional[List[str]]:
     """The tag list of ``--task token-classification --dataset conll`` (read once, kept on ``args``)."""
     if getattr(args, "task", "") != "token-classification" or args.dataset != "conll":
@@ -256,6 +275,10 @@ def _provenance(args, model, rank: int, n_train: int, n_eval: int, batch_plan=No
             info["metric"] += (f"; the loss, in training and in evaluation, is the label-smoothed cross-entropy "
                                f"(eps = {eps:g})")
         logger.info("--label_smoothing_factor %g: training and evaluation report the smoothed cross-entropy", eps)
+    decay, head = _lr_group_flags(args)
+    if decay != 1.0 or head != 1.0:
+        info["layerwise_lr_decay"] = decay
+        info["head_lr_multiplier"] = head
     if batch_plan is not None:
         info["auto_batch"] = batch_plan.as_dict()
     if synthetic or weights == "random-init":
@@ -298,6 +321,7 @@ def build(args, mode: str):
     if ptype in ("regression", "multi_label_classification") and args.dataset in ("imdb", "sst2"):
         raise ValueError(_PTYPE_DATASETS.format(ptype, args.dataset))
     smoothing = _label_smoothing(args, task, ptype)
+    _lr_group_flags(args)
     tags = _conll_tags(args)
     if tags is not None:
         if args.num_labels != len(tags):
@@ -344,16 +368,17 @@ def build(args, mode: str):
                            transposed=keep_transposed_weights(rank_tokens))
     base_lr = float(args.learning_rate)
     lr = base_lr * world if mode == "train" else base_lr  # scripts/train.py:112 vs singe_node_train.py:78
+    lr_mul = _lr_multipliers(args, store, model.cfg, lr)
     if args.optimizer == "lamb":
         # the learning rate keeps the Horovod x world rule above; LAMB always uses its bias-corrected form
         if args.adam_eps_mode != "keras":
             logger.info("--adam_eps_mode %s does not apply to --optimizer lamb (ignored)", args.adam_eps_mode)
         opt = FusedLamb(store, lr=lr, eps=args.adam_epsilon, weight_decay=args.weight_decay,
-                        max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0))
+                        max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0), lr_multipliers=lr_mul)
     else:
         opt = FusedAdam(store, lr=lr, eps=args.adam_epsilon, eps_mode=args.adam_eps_mode,
                         weight_decay=args.weight_decay if args.optimizer == "adamw" else 0.0,
-                        max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0))
+                        max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0), lr_multipliers=lr_mul)
     batch_plan = None
     if args.train_batch_size == "auto":
         # sized on the device before any readiness hook / bucketer exists (the probes are plain fwd + bwd)

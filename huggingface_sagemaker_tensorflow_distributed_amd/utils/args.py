@@ -104,6 +104,14 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
                    help="clip the global gradient norm (over all parameters, after the rank / accumulation average) to "
                         "this value inside the fused optimizer step (tf.clip_by_global_norm / Keras global_clipnorm "
                         "math); 0 (default) = off, as the reference; inf = measure and log the norm, never clip")
+    g.add_argument("--layerwise_lr_decay", type=float, default=1.0,
+                   help="layer-wise learning-rate decay D in (0, 1], inside the fused optimizer step: the head trains "
+                        "at the full rate, encoder layer i of L at lr * D^(L-i) and the embeddings at lr * D^(L+1) "
+                        "(the BEiT / timm convention; ELECTRA's exponents are one larger); 1 (default) = off, as the "
+                        "reference")
+    g.add_argument("--head_lr_multiplier", type=float, default=1.0,
+                   help="learning-rate multiplier M > 0 of the head (pooler, classifier, qa_outputs, MLM transform: "
+                        "everything above the encoder), for a freshly initialised head; 1 (default) = off")
     g.add_argument("--lr_schedule", choices=["constant", "linear"], default="constant",
                    help="constant = Keras Adam(learning_rate) (reference); linear = warmup then linear decay to 0")
     g.add_argument("--lr_warmup_steps", type=int, default=0, help="linear warmup steps of the learning rate")
