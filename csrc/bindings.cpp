@@ -973,8 +973,9 @@ void ln32_fwd(torch::Tensor x, torch::Tensor g, torch::Tensor b, torch::Tensor o
               torch::Tensor rstd, double eps, c10::optional<torch::Tensor> hi, c10::optional<torch::Tensor> lo) {
   check_f32(x, "x"); check_f32(g, "g"); check_f32(b, "b"); check_f32(out, "out"); check_f32(mean, "mean");
   check_f32(rstd, "rstd");
+  TORCH_CHECK(x.dim() == 2, "ln32_fwd: x [R][H]");
   const int64_t R = x.size(0), H = x.size(1);
-  TORCH_CHECK(x.dim() == 2 && H % 4 == 0 && H <= 1024 && g.numel() == H && b.numel() == H && mean.numel() == R &&
+  TORCH_CHECK(H % 4 == 0 && H <= 1024 && g.numel() == H && b.numel() == H && mean.numel() == R &&
               rstd.numel() == R && out.sizes() == x.sizes(), "ln32_fwd shapes");
   check_halves(hi, lo, x.numel());
   hsd::launch_ln32_fwd(x.data_ptr<float>(), g.data_ptr<float>(), b.data_ptr<float>(), out.data_ptr<float>(),
@@ -986,22 +987,33 @@ void ln32_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor mean, torch::Tens
               torch::Tensor dx, torch::Tensor dg, torch::Tensor db) {
   check_f32(dy, "dy"); check_f32(x, "x"); check_f32(mean, "mean"); check_f32(rstd, "rstd"); check_f32(g, "g");
   check_f32(dx, "dx"); check_f32(dg, "dg"); check_f32(db, "db");
+  TORCH_CHECK(x.dim() == 2, "ln32_bwd: x [R][H]");
   const int64_t R = x.size(0), H = x.size(1);
-  TORCH_CHECK(dy.sizes() == x.sizes() && dx.sizes() == x.sizes() && H % 4 == 0 && H <= 1024 && dg.numel() == H &&
-              db.numel() == H && mean.numel() == R, "ln32_bwd shapes");
+  TORCH_CHECK(dy.sizes() == x.sizes() && dx.sizes() == x.sizes() && H % 4 == 0 && H <= 1024 && g.numel() == H &&
+              dg.numel() == H && db.numel() == H && mean.numel() == R && rstd.numel() == R, "ln32_bwd shapes");
   hsd::launch_ln32_bwd(dy.data_ptr<float>(), x.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
                        g.data_ptr<float>(), dx.data_ptr<float>(), dg.data_ptr<float>(), db.data_ptr<float>(), (int)R,
                        (int)H, cur_stream());
 }
 
+// int64 id tensor of the fp32 kernels: on the GPU, contiguous, n elements
+static void check_ids(const torch::Tensor& t, int64_t n, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kInt64 && t.numel() == n, name,
+              " must be a contiguous int64 GPU tensor with one id per row");
+}
+
 void embed32_gather(torch::Tensor ids, torch::Tensor pids, c10::optional<torch::Tensor> tids, torch::Tensor word,
                     torch::Tensor pos, c10::optional<torch::Tensor> type, torch::Tensor x) {
-  CHECK_DTYPE(ids, torch::kInt64); CHECK_DTYPE(pids, torch::kInt64); CHECK_CONTIG(ids); CHECK_CONTIG(pids);
   check_f32(word, "word"); check_f32(pos, "pos"); check_f32(x, "x");
+  TORCH_CHECK(word.dim() == 2 && pos.dim() == 2 && x.dim() == 2, "embed32_gather: word, pos and x are 2-D");
   const int64_t R = ids.numel(), H = word.size(1);
-  TORCH_CHECK(pids.numel() == R && x.size(0) == R && x.size(1) == H && pos.size(1) == H && H % 4 == 0, "embed32 shapes");
-  if (tids.has_value()) { CHECK_DTYPE(*tids, torch::kInt64); CHECK_CONTIG(*tids); TORCH_CHECK(tids->numel() == R, "tids"); }
-  if (type.has_value()) check_f32(*type, "type");
+  check_ids(ids, R, "ids"); check_ids(pids, R, "pids");
+  TORCH_CHECK(x.size(0) == R && x.size(1) == H && pos.size(1) == H && H % 4 == 0, "embed32 shapes");
+  if (tids.has_value()) check_ids(*tids, R, "tids");
+  if (type.has_value()) {
+    check_f32(*type, "type");
+    TORCH_CHECK(type->dim() == 2 && type->size(0) >= 1 && type->size(1) == H, "embed32_gather: type [rows][H]");
+  }
   hsd::launch_embed32_gather(ids.data_ptr<int64_t>(), pids.data_ptr<int64_t>(), OPT_I64(tids), word.data_ptr<float>(),
                              pos.data_ptr<float>(), OPT_F(type), x.data_ptr<float>(), (int)R, (int)H, cur_stream());
 }
@@ -1009,11 +1021,19 @@ void embed32_gather(torch::Tensor ids, torch::Tensor pids, c10::optional<torch::
 void embed32_scatter(torch::Tensor dx, torch::Tensor ids, torch::Tensor pids, c10::optional<torch::Tensor> tids,
                      torch::Tensor gword, c10::optional<torch::Tensor> gpos, c10::optional<torch::Tensor> gtype) {
   check_f32(dx, "dx"); check_f32(gword, "gword");
-  CHECK_DTYPE(ids, torch::kInt64); CHECK_DTYPE(pids, torch::kInt64);
+  TORCH_CHECK(dx.dim() == 2 && gword.dim() == 2, "embed32_scatter: dx and gword are 2-D");
   const int64_t R = ids.numel(), H = dx.size(1);
+  check_ids(ids, R, "ids"); check_ids(pids, R, "pids");
   TORCH_CHECK(dx.size(0) == R && gword.size(1) == H, "embed32_scatter shapes");
-  if (gpos.has_value()) check_f32(*gpos, "gpos");
-  if (gtype.has_value()) check_f32(*gtype, "gtype");
+  if (tids.has_value()) check_ids(*tids, R, "tids");
+  if (gpos.has_value()) {
+    check_f32(*gpos, "gpos");
+    TORCH_CHECK(gpos->dim() == 2 && gpos->size(1) == H, "embed32_scatter: gpos [rows][H]");
+  }
+  if (gtype.has_value()) {
+    check_f32(*gtype, "gtype");
+    TORCH_CHECK(gtype->dim() == 2 && gtype->size(0) >= 1 && gtype->size(1) == H, "embed32_scatter: gtype [rows][H]");
+  }
   hsd::launch_embed32_scatter(dx.data_ptr<float>(), ids.data_ptr<int64_t>(), pids.data_ptr<int64_t>(), OPT_I64(tids),
                               gword.data_ptr<float>(), OPT_F(gpos), OPT_F(gtype), (int)R, (int)H, cur_stream());
 }
@@ -1021,6 +1041,7 @@ void embed32_scatter(torch::Tensor dx, torch::Tensor ids, torch::Tensor pids, c1
 void attn32_fwd(torch::Tensor qkv, c10::optional<torch::Tensor> mask, torch::Tensor out, torch::Tensor lse, int64_t B,
                 int64_t S, int64_t heads, double p, int64_t seed) {
   check_f32(qkv, "qkv"); check_f32(out, "out"); check_f32(lse, "lse");
+  TORCH_CHECK(qkv.dim() == 2 && out.dim() == 2 && B >= 1 && S >= 2 && heads >= 1, "attn32_fwd: qkv [B S][3H], out [B S][H]");
   TORCH_CHECK(qkv.size(0) == B * S && qkv.size(1) == 3 * heads * 64 && out.size(0) == B * S &&
               out.size(1) == heads * 64 && lse.numel() == B * heads * S && S % 2 == 0, "attn32_fwd shapes (head dim 64)");
   if (mask.has_value()) { check_f32(*mask, "mask"); TORCH_CHECK(mask->numel() == B * S, "mask"); }
@@ -1033,8 +1054,11 @@ void attn32_bwd(torch::Tensor qkv, c10::optional<torch::Tensor> mask, torch::Ten
                 int64_t seed) {
   check_f32(qkv, "qkv"); check_f32(o, "o"); check_f32(dout, "dout"); check_f32(lse, "lse"); check_f32(dqkv, "dqkv");
   check_f32(delta, "delta");
-  TORCH_CHECK(qkv.sizes() == dqkv.sizes() && o.sizes() == dout.sizes() && o.size(0) == B * S &&
-              o.size(1) == heads * 64 && lse.numel() == B * heads * S && delta.numel() >= B * heads * S, "attn32_bwd shapes");
+  TORCH_CHECK(qkv.dim() == 2 && o.dim() == 2 && B >= 1 && S >= 2 && heads >= 1, "attn32_bwd: qkv [B S][3H], o [B S][H]");
+  TORCH_CHECK(qkv.sizes() == dqkv.sizes() && qkv.size(0) == B * S && qkv.size(1) == 3 * heads * 64 &&
+              o.sizes() == dout.sizes() && o.size(0) == B * S && o.size(1) == heads * 64 &&
+              lse.numel() == B * heads * S && delta.numel() >= B * heads * S && S % 2 == 0,
+              "attn32_bwd shapes (head dim 64, even S)");
   if (mask.has_value()) { check_f32(*mask, "mask"); TORCH_CHECK(mask->numel() == B * S, "mask"); }
   hsd::launch_attn32_bwd(qkv.data_ptr<float>(), OPT_F(mask), o.data_ptr<float>(), dout.data_ptr<float>(),
                          lse.data_ptr<float>(), dqkv.data_ptr<float>(), delta.data_ptr<float>(), (int)B, (int)S,
@@ -1079,9 +1103,11 @@ void attn32m_bwd(torch::Tensor qh, torch::Tensor ql, torch::Tensor doh, torch::T
 void cls32_fwd(torch::Tensor pre, torch::Tensor W2, torch::Tensor b2, torch::Tensor labels, torch::Tensor t_out,
                torch::Tensor logits, torch::Tensor stats, int64_t act, double p, int64_t seed) {
   check_f32(pre, "pre"); check_f32(W2, "W2"); check_f32(b2, "b2"); check_f32(t_out, "t_out"); check_f32(logits, "logits");
-  check_f32(stats, "stats"); CHECK_DTYPE(labels, torch::kInt64); CHECK_CONTIG(labels);
+  check_f32(stats, "stats");
+  TORCH_CHECK(pre.dim() == 2 && W2.dim() == 2 && logits.dim() == 2, "cls32_fwd: pre, W2 and logits are 2-D");
   const int64_t R = pre.size(0), H = pre.size(1), C = W2.size(0);
-  TORCH_CHECK(W2.size(1) == H && b2.numel() == C && C <= 8 && labels.numel() == R && t_out.sizes() == pre.sizes() &&
+  check_ids(labels, R, "labels");
+  TORCH_CHECK(W2.size(1) == H && b2.numel() == C && C >= 1 && C <= 8 && t_out.sizes() == pre.sizes() &&
               logits.size(0) == R && logits.size(1) == C && stats.numel() >= 2 && H % 2 == 0, "cls32_fwd shapes");
   hsd::launch_cls32_fwd(pre.data_ptr<float>(), W2.data_ptr<float>(), b2.data_ptr<float>(), labels.data_ptr<int64_t>(),
                         t_out.data_ptr<float>(), logits.data_ptr<float>(), stats.data_ptr<float>(), (int)R, (int)H,
@@ -1093,8 +1119,12 @@ void cls32_bwd(torch::Tensor pre, torch::Tensor t, torch::Tensor W2, torch::Tens
                int64_t seed) {
   check_f32(pre, "pre"); check_f32(t, "t"); check_f32(W2, "W2"); check_f32(logits, "logits"); check_f32(dloss, "dloss");
   check_f32(dpre, "dpre"); check_f32(dW2, "dW2"); check_f32(db2, "db2");
+  TORCH_CHECK(pre.dim() == 2 && W2.dim() == 2 && logits.dim() == 2, "cls32_bwd: pre, W2 and logits are 2-D");
   const int64_t R = pre.size(0), H = pre.size(1), C = W2.size(0);
-  TORCH_CHECK(dpre.sizes() == pre.sizes() && dW2.sizes() == W2.sizes() && db2.numel() == C && C <= 8, "cls32_bwd shapes");
+  check_ids(labels, R, "labels");
+  TORCH_CHECK(t.sizes() == pre.sizes() && dpre.sizes() == pre.sizes() && W2.size(1) == H && dW2.sizes() == W2.sizes() &&
+              db2.numel() == C && C >= 1 && C <= 8 && logits.size(0) == R && logits.size(1) == C &&
+              dloss.numel() >= 1 && H % 2 == 0, "cls32_bwd shapes");
   hsd::launch_cls32_bwd(pre.data_ptr<float>(), t.data_ptr<float>(), W2.data_ptr<float>(), logits.data_ptr<float>(),
                         labels.data_ptr<int64_t>(), dloss.data_ptr<float>(), dpre.data_ptr<float>(),
                         dW2.data_ptr<float>(), db2.data_ptr<float>(), (int)R, (int)H, (int)C, (int)act, p,
