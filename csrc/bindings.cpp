@@ -1,6 +1,7 @@
 // Python bindings for the gfx950 kernels: argument validation + current-HIP-stream launch.
 // Compiled into huggingface_sagemaker_tensorflow_distributed_amd/_C.so by _build.py (hipcc).
 #include <torch/extension.h>
+#include <cmath>
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 
@@ -48,10 +49,28 @@ void stream_wait(int64_t dst_ptr, int64_t src_ptr) {
 #define BF(x) reinterpret_cast<hsd::bf16_t*>((x).data_ptr())
 #define CBF(x) reinterpret_cast<const hsd::bf16_t*>((x).data_ptr())
 
+// The weight average of adam_step / lamb_step (--ema_decay): fp32, contiguous, on p's GPU, p's size, 16-B aligned, and
+// sharing no storage with a buffer the same launch reads or writes (the kernels take it as __restrict__); the weight
+// `omd` = 1 - decay is finite and in [0, 1]. Raises before anything is launched; returns the device pointer.
+float* check_ema(const torch::Tensor& ema, double omd, const torch::Tensor& p, const torch::Tensor& m,
+                 const torch::Tensor& v, const torch::Tensor& g) {
+  TORCH_CHECK(ema.is_cuda() && ema.device() == p.device(), "ema must be on the GPU of p");
+  TORCH_CHECK(ema.scalar_type() == torch::kFloat32, "ema must be fp32");
+  TORCH_CHECK(ema.is_contiguous(), "ema must be contiguous");
+  TORCH_CHECK(ema.numel() == p.numel(), "ema: ", ema.numel(), " elements, p has ", p.numel());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(ema.data_ptr()) % 16 == 0, "ema must start 16-B aligned");
+  for (const torch::Tensor* t : {&p, &m, &v, &g})
+    TORCH_CHECK(!ema.is_alias_of(*t), "ema must not share storage with p, m, v or the gradient");
+  TORCH_CHECK(std::isfinite(omd) && omd >= 0.0 && omd <= 1.0, "ema_omd = 1 - decay must be finite and in [0, 1]: ",
+              omd);
+  return ema.data_ptr<float>();
+}
+
 void adam_step(torch::Tensor p, torch::Tensor m, torch::Tensor v, torch::Tensor g, c10::optional<torch::Tensor> out,
                c10::optional<torch::Tensor> decay, double step, double eps, double b1, double b2, double gscale,
                double lr_wd, c10::optional<torch::Tensor> coef, c10::optional<torch::Tensor> out_lo, bool zero_grad,
-               c10::optional<torch::Tensor> clip, c10::optional<torch::Tensor> lr_mul) {
+               c10::optional<torch::Tensor> clip, c10::optional<torch::Tensor> lr_mul,
+               c10::optional<torch::Tensor> ema, double ema_omd) {
   CHECK_CUDA(p); CHECK_CONTIG(p); CHECK_DTYPE(p, torch::kFloat32);
   TORCH_CHECK(!zero_grad || g.is_contiguous(), "adam zero_grad: contiguous gradient");
   CHECK_DTYPE(m, torch::kFloat32); CHECK_DTYPE(v, torch::kFloat32);
@@ -74,6 +93,8 @@ void adam_step(torch::Tensor p, torch::Tensor m, torch::Tensor v, torch::Tensor 
   if (coef.has_value()) {
     CHECK_CUDA(*coef); CHECK_DTYPE(*coef, torch::kFloat32);
     TORCH_CHECK(coef->numel() >= 4, "coef: fp32 [4]");
+    // with the weight average: fp32 [8], slot 4 = 1 - decay of this step
+    TORCH_CHECK(!ema.has_value() || coef->numel() >= 8, "coef with ema: fp32 [8]");
     dcoef = coef->data_ptr<float>();
   }
   hsd::bf16_t* lo = nullptr;  // fp32 compute: `out` / `out_lo` = the bf16 hi / lo halves of the updated weights
@@ -98,9 +119,10 @@ void adam_step(torch::Tensor p, torch::Tensor m, torch::Tensor v, torch::Tensor 
                 p.numel() / 64, " needed");
     dmul = lr_mul->data_ptr<float>();
   }
+  float* dema = ema.has_value() ? check_ema(*ema, ema_omd, p, m, v, g) : nullptr;
   hsd::launch_adam(p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), g.data_ptr(), gbf, o, dm,
                    p.numel(), (float)step, (float)eps, (float)b1, (float)b2, (float)gscale, (float)lr_wd,
-                   dcoef, cur_stream(), lo, zero_grad, dclip, dmul);
+                   dcoef, cur_stream(), lo, zero_grad, dclip, dmul, dema, (float)ema_omd);
 }
 
 // Sum of squares of the gradient slice `g` (a contiguous, 64-aligned view into the flat gradient buffer): one fp32
@@ -192,7 +214,8 @@ void lamb_step(const LambPlan& plan, int64_t seg0, int64_t nsegs, torch::Tensor 
                torch::Tensor g, c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> out_lo,
                torch::Tensor partials, torch::Tensor ratio, double lr, double ibc1, double ibc2, double eps, double b1,
                double b2, double gscale, double wd, c10::optional<torch::Tensor> coef,
-               c10::optional<torch::Tensor> clip, bool zero_grad, c10::optional<torch::Tensor> lr_mul) {
+               c10::optional<torch::Tensor> clip, bool zero_grad, c10::optional<torch::Tensor> lr_mul,
+               c10::optional<torch::Tensor> ema, double ema_omd) {
   auto flat = [&](const torch::Tensor& t, const char* name) {
     TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.device() == plan.tiles.device(), name,
                 ": contiguous tensor on the plan's GPU");
@@ -243,11 +266,13 @@ void lamb_step(const LambPlan& plan, int64_t seg0, int64_t nsegs, torch::Tensor 
                 plan.nsegs(), " needed");
     dmul = lr_mul->data_ptr<float>();
   }
+  float* dema = ema.has_value() ? check_ema(*ema, ema_omd, p, m, v, g) : nullptr;
   const int64_t t0 = plan.first_tile[seg0], t1 = plan.first_tile[seg0 + nsegs];
   hsd::launch_lamb(p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), g.data_ptr(), gbf, o, lo,
                    plan.tiles.data_ptr<int64_t>(), plan.segs.data_ptr<int64_t>(), t0, t1 - t0, seg0, nsegs,
                    partials.data_ptr<float>(), ratio.data_ptr<float>(), (float)lr, (float)ibc1, (float)ibc2, (float)eps,
-                   (float)b1, (float)b2, (float)gscale, (float)wd, dcoef, dclip, zero_grad, cur_stream(), dmul);
+                   (float)b1, (float)b2, (float)gscale, (float)wd, dcoef, dclip, zero_grad, cur_stream(), dmul, dema,
+                   (float)ema_omd);
 }
 
 #define OPT_BF(o) ((o).has_value() ? reinterpret_cast<hsd::bf16_t*>((o)->data_ptr()) : nullptr)
@@ -1606,7 +1631,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_step", &adam_step, py::arg("p"), py::arg("m"), py::arg("v"), py::arg("g"), py::arg("out"),
         py::arg("decay"), py::arg("step"), py::arg("eps"), py::arg("b1"), py::arg("b2"), py::arg("gscale"),
         py::arg("lr_wd"), py::arg("coef") = py::none(), py::arg("out_lo") = py::none(), py::arg("zero_grad") = false,
-        py::arg("clip") = py::none(), py::arg("lr_mul") = py::none());
+        py::arg("clip") = py::none(), py::arg("lr_mul") = py::none(), py::arg("ema") = py::none(),
+        py::arg("ema_omd") = 0.0);
   m.def("grad_sumsq", &grad_sumsq, py::arg("g"), py::arg("partials"), py::arg("slot_base") = 0);
   m.def("grad_sumsq_blocks", [](int64_t n, bool bf16) { return (int64_t)hsd::grad_sumsq_blocks(n, bf16); });
   m.def("grad_clip_finalize", &grad_clip_finalize, py::arg("partials"), py::arg("nparts"), py::arg("gscale"),
@@ -1626,7 +1652,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v"), py::arg("g"), py::arg("out"), py::arg("out_lo"), py::arg("partials"), py::arg("ratio"),
         py::arg("lr"), py::arg("ibc1"), py::arg("ibc2"), py::arg("eps"), py::arg("b1"), py::arg("b2"),
         py::arg("gscale"), py::arg("wd"), py::arg("coef") = py::none(), py::arg("clip") = py::none(),
-        py::arg("zero_grad") = false, py::arg("lr_mul") = py::none());
+        py::arg("zero_grad") = false, py::arg("lr_mul") = py::none(), py::arg("ema") = py::none(),
+        py::arg("ema_omd") = 0.0);
   m.def("ln_fwd_q8", &ln_fwd_q8);
   m.def("stream_wait", &stream_wait);
   m.def("gemm2_on", &gemm2_on);

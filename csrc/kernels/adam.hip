@@ -48,7 +48,14 @@ __device__ __forceinline__ float lr_scaled(float s, float mu) {
 // follows), so a segment gets the bits the kernel without the table gives it when launched on that segment alone with
 // the host scalars float32(step * mu), float32(lr_wd * mu), and a table of ones gives the bits of no table. An
 // instantiation of its own for kClip's reason: the kernels without the table keep the code they had.
-template <bool kGradBf16, bool kWriteBf16, int U, bool kLo = false, bool kClip = false, bool kLrMul = false>
+// kEma (launched when `ema` is given; --ema_decay): the exponential moving average of the weights, one fp32 buffer laid
+// out as `p`. Its chunk is loaded with the other U loads and updated from the weight the kernel is about to store,
+// ema += w·(θ - ema) with w = float32(1 - decay) (ema_lerp: three rounded operations), and stored next to `p`: one more
+// 16-B load and store per chunk instead of a second pass over weights that were in registers a moment earlier. Nothing
+// else reads it: p, m, v, the outputs and the cleared gradient are the bits of the launch without it. `ema_w` is a
+// kernel argument; captured steps read it from coef[4]. An instantiation of its own for kClip's reason.
+template <bool kGradBf16, bool kWriteBf16, int U, bool kLo = false, bool kClip = false, bool kLrMul = false,
+          bool kEma = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ m,
                                                    float* __restrict__ v, void* __restrict__ g_,
                                                    bf16_t* __restrict__ out, const uint8_t* __restrict__ decay,
@@ -56,19 +63,21 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
                                                    float gscale, float lr_wd, const float* __restrict__ coef,
                                                    bf16_t* __restrict__ out_lo, int zero_g,
                                                    const float* __restrict__ clip,
-                                                   const float* __restrict__ lr_mul) {
+                                                   const float* __restrict__ lr_mul,
+                                                   float* __restrict__ ema, float ema_w) {
   if (coef != nullptr) {  // HIP-graph replays: this step's scalars live on the device (train/graph.py)
     step = coef[0];
     eps = coef[1];
     gscale = coef[2];
     lr_wd = coef[3];
+    if constexpr (kEma) ema_w = coef[4];
   }
   // global-norm clipping (gradnorm.hip): the step's clip coefficient, computed on the device, folded into the
   // gradient scale by ONE fp32 multiply (a host replay with float32(gscale) * float32(coef) gives the same bits)
   if constexpr (kClip) gscale *= clip[0];
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += stride * U) {
-    f32x4 g[U], pp[U], mm[U], vv[U];
+    f32x4 g[U], pp[U], mm[U], vv[U], ee[U];
     float mu[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -79,6 +88,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
         pp[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + i);
         mm[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m) + i);
         vv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v) + i);
+        if constexpr (kEma) ee[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ema) + i);
       }
     }
 #pragma unroll
@@ -119,22 +129,40 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
         }
       }
     }
+    // the average, from the weights stored above, in a loop of its own: in the loop above the compiler made other
+    // contraction choices for the weight update with this code beside it, and p would not be the bits of the kernel
+    // without kEma
+    if constexpr (kEma) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = i0 + u * stride;
+        if (i >= n4) break;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ee[u][k] = ema_lerp(ee[u][k], ema_w, pp[u][k]);
+        __builtin_nontemporal_store(ee[u], reinterpret_cast<f32x4*>(ema) + i);
+      }
+    }
   }
 }
 
 void launch_adam(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* out_bf16,
                  const uint8_t* decay, int64_t n, float step, float eps, float b1, float b2, float gscale,
                  float lr_wd, const float* coef, hipStream_t stream, bf16_t* out_lo, bool zero_grad,
-                 const float* clip, const float* lr_mul) {
+                 const float* clip, const float* lr_mul, float* ema, float ema_w) {
   const int zg = zero_grad ? 1 : 0;
   int64_t n4 = n / 4;  // n is a multiple of 1024 (FlatParamStore)
   int threads = 256;
   int64_t blocks = (n4 + threads - 1) / threads;
   if (blocks > 256 * 8) blocks = 256 * 8;  // grid-stride: 8 blocks (32 waves) per CU over 256 CUs
   // two 16-B chunks per thread per trip (1 and 4 measured slower: profiles/bench_adam_r2.json)
+#define HSD_ADAM_E(GB, WB, LO, CL, LM, EM)                                                                          \
+  hipLaunchKernelGGL((adam_kernel<GB, WB, 2, LO, CL, LM, EM>), dim3((unsigned)blocks), dim3(threads), 0, stream, p, \
+                     m, v, g, out_bf16, decay, n4, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zg, clip, lr_mul, \
+                     ema, ema_w)
 #define HSD_ADAM_K(GB, WB, LO, CL, LM)                                                                              \
-  hipLaunchKernelGGL((adam_kernel<GB, WB, 2, LO, CL, LM>), dim3((unsigned)blocks), dim3(threads), 0, stream, p, m, \
-                     v, g, out_bf16, decay, n4, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zg, clip, lr_mul)
+  do {                                                                                                              \
+    if (ema != nullptr) HSD_ADAM_E(GB, WB, LO, CL, LM, true); else HSD_ADAM_E(GB, WB, LO, CL, LM, false);          \
+  } while (0)
 #define HSD_ADAM_C(GB, WB, LO, LM)                                                                                  \
   do {                                                                                                              \
     if (clip != nullptr) HSD_ADAM_K(GB, WB, LO, true, LM); else HSD_ADAM_K(GB, WB, LO, false, LM);                 \
@@ -157,6 +185,7 @@ void launch_adam(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* 
 #undef HSD_ADAM
 #undef HSD_ADAM_C
 #undef HSD_ADAM_K
+#undef HSD_ADAM_E
   HSD_CHECK_LAUNCH();
 }
 

@@ -57,6 +57,16 @@ __device__ __forceinline__ void store_halves4(bf16_t* hi, bf16_t* lo, int64_t i,
   reinterpret_cast<u32x2*>(lo)[i] = l;
 }
 
+// One element of the weight average (--ema_decay; adam_kernel's and lamb_stage2_kernel's kEma): e + w·(p - e) as three
+// separately rounded fp32 operations, never contracted into an FMA -- the rounding is the definition, so a torch fp32
+// replay `e + w * (p - e)` gives the same bits from either kernel.
+__device__ __forceinline__ float ema_lerp(float e, float w, float p) {
+#pragma clang fp contract(off)
+  const float d = p - e;
+  const float s = w * d;
+  return e + s;
+}
+
 // ---- lane exchanges inside 8-lane groups on DPP (one VALU op each; __shfl_xor is a ds_bpermute: an LDS round trip
 // whose lgkmcnt wait serialises dependent chains, e.g. the attention backward's per-key-pair dropout hash exchange)
 __device__ __forceinline__ uint32_t dpp_xor1(uint32_t v) {  // lane l <- lane l^1 (quad_perm [1,0,3,2])

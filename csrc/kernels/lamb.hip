@@ -30,7 +30,7 @@ constexpr int kLambRatioThreads = 256;
 int lamb_tile() { return kLambTileElems; }
 
 // Per-step scalars of a captured step, fp32 [8] on the device (LAMB's own layout, optim/lamb.py):
-//   [0] lr  [1] 1/(1-b1ᵗ)  [2] 1/(1-b2ᵗ)  [3] eps  [4] grad_scale  [5] wd  [6], [7] unused
+//   [0] lr  [1] 1/(1-b1ᵗ)  [2] 1/(1-b2ᵗ)  [3] eps  [4] grad_scale  [5] wd  [6] 1 - ema decay (kEma)  [7] unused
 struct LambScalars {
   float lr, ibc1, ibc2, eps, gscale, wd;
 };
@@ -186,13 +186,19 @@ __global__ __launch_bounds__(kLambRatioThreads) void lamb_ratio_kernel(const flo
 // takes the learning rate lr * lr_mul[seg], ONE fp32 multiply ahead of the existing lr * r -- the bits of a launch
 // without the table on that segment alone with the host scalar float32(lr * mu). u, the norms and r do not see it. An
 // instantiation of its own (adam_kernel's kClip): the kernels without the table keep the code they had.
-template <bool kWriteBf16, bool kLo, bool kLrMul = false>
+// kEma (launched when `ema` is given; --ema_decay): the weight average, exactly as adam_kernel's kEma -- the tile's
+// chunk of `ema` (indexed base4 + i, as p) loaded with the other loads, updated by ema_lerp from the weight about to be
+// stored, stored next to it. Captured steps read w from coef[6]. u, the norms, r and every other output do not see it.
+template <bool kWriteBf16, bool kLo, bool kLrMul = false, bool kEma = false>
 __global__ __launch_bounds__(kLambThreads) void lamb_stage2_kernel(
     float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v, bf16_t* __restrict__ out,
     bf16_t* __restrict__ out_lo, const int64_t* __restrict__ tiles, const int64_t* __restrict__ segs, int64_t tile0,
     const float* __restrict__ ratio, LambScalars s, const float* __restrict__ coef,
-    const float* __restrict__ lr_mul) {
+    const float* __restrict__ lr_mul, float* __restrict__ ema, float ema_w) {
   s = lamb_scalars(s, coef);
+  if constexpr (kEma) {
+    if (coef != nullptr) ema_w = coef[6];
+  }
   const int64_t t = tile0 + blockIdx.x;
   const int64_t base4 = tiles[t * 3] >> 2;
   const int n4 = (int)(tiles[t * 3 + 1] >> 2);
@@ -202,7 +208,7 @@ __global__ __launch_bounds__(kLambThreads) void lamb_stage2_kernel(
   if constexpr (kLrMul) lr *= lr_mul[seg];
   const float step = lr * ratio[seg * 3];
   for (int i0 = threadIdx.x; i0 < n4; i0 += kLambThreads * kLambU) {
-    f32x4 pp[kLambU], mm[kLambU], vv[kLambU];
+    f32x4 pp[kLambU], mm[kLambU], vv[kLambU], ee[kLambU];
 #pragma unroll
     for (int u = 0; u < kLambU; ++u) {
       const int i = i0 + u * kLambThreads;
@@ -210,6 +216,7 @@ __global__ __launch_bounds__(kLambThreads) void lamb_stage2_kernel(
         pp[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + base4 + i);
         mm[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m) + base4 + i);
         vv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v) + base4 + i);
+        if constexpr (kEma) ee[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ema) + base4 + i);
       }
     }
 #pragma unroll
@@ -235,6 +242,17 @@ __global__ __launch_bounds__(kLambThreads) void lamb_stage2_kernel(
         }
       }
     }
+    // the average, from the weights stored above, in a loop of its own (adam_kernel's reason)
+    if constexpr (kEma) {
+#pragma unroll
+      for (int u = 0; u < kLambU; ++u) {
+        const int i = i0 + u * kLambThreads;
+        if (i >= n4) break;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ee[u][k] = ema_lerp(ee[u][k], ema_w, pp[u][k]);
+        __builtin_nontemporal_store(ee[u], reinterpret_cast<f32x4*>(ema) + base4 + i);
+      }
+    }
   }
 }
 
@@ -242,7 +260,7 @@ void launch_lamb(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* 
                  const int64_t* tiles, const int64_t* segs, int64_t tile0, int64_t ntiles, int64_t seg0, int64_t nsegs,
                  float* partials, float* ratio, float lr, float ibc1, float ibc2, float eps, float b1, float b2,
                  float gscale, float wd, const float* coef, const float* clip, bool zero_grad, hipStream_t stream,
-                 const float* lr_mul) {
+                 const float* lr_mul, float* ema, float ema_w) {
   if (ntiles <= 0 || nsegs <= 0) return;
   if (out_lo != nullptr && out_bf16 == nullptr) abort();
   const LambScalars s{lr, ibc1, ibc2, eps, gscale, wd};
@@ -261,9 +279,13 @@ void launch_lamb(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* 
   hipLaunchKernelGGL(lamb_ratio_kernel, dim3((unsigned)nsegs), dim3(kLambRatioThreads), 0, stream, partials, segs,
                      seg0, ratio);
   HSD_CHECK_LAUNCH();
+#define HSD_LAMB2_E(WB, LO, LM, EM)                                                                                   \
+  hipLaunchKernelGGL((lamb_stage2_kernel<WB, LO, LM, EM>), grid, block, 0, stream, p, m, v, out_bf16, out_lo, tiles, \
+                     segs, tile0, ratio, s, coef, lr_mul, ema, ema_w)
 #define HSD_LAMB2_K(WB, LO, LM)                                                                                   \
-  hipLaunchKernelGGL((lamb_stage2_kernel<WB, LO, LM>), grid, block, 0, stream, p, m, v, out_bf16, out_lo, tiles, \
-                     segs, tile0, ratio, s, coef, lr_mul)
+  do {                                                                                                            \
+    if (ema != nullptr) HSD_LAMB2_E(WB, LO, LM, true); else HSD_LAMB2_E(WB, LO, LM, false);                      \
+  } while (0)
 #define HSD_LAMB2(WB, LO)                                                                                         \
   do {                                                                                                            \
     if (lr_mul != nullptr) HSD_LAMB2_K(WB, LO, true); else HSD_LAMB2_K(WB, LO, false);                           \
@@ -273,6 +295,7 @@ void launch_lamb(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* 
   else HSD_LAMB2(false, false);
 #undef HSD_LAMB2
 #undef HSD_LAMB2_K
+#undef HSD_LAMB2_E
   HSD_CHECK_LAUNCH();
 }
 

@@ -15,7 +15,10 @@ void launch_adam(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* 
                  const uint8_t* decay, int64_t n, float step, float eps, float b1, float b2, float gscale,
                  float lr_wd, const float* coef, hipStream_t stream,
                  bf16_t* out_lo = nullptr, bool zero_grad = false, const float* clip = nullptr,
-                 const float* lr_mul = nullptr);  // fp32 [n / 64]: learning-rate multiplier per 64-element block
+                 const float* lr_mul = nullptr,  // fp32 [n / 64]: learning-rate multiplier per 64-element block
+                 // fp32 [n]: the weight average, ema += ema_w·(p_new - ema) in the same pass (coef[4] replaces ema_w;
+                 // coef is then fp32 [8])
+                 float* ema = nullptr, float ema_w = 0.0f);
 
 // gradnorm.hip: global-norm gradient clipping. grad_sumsq writes grad_sumsq_blocks(n, bf16) fp32 partials (one per
 // block, no atomics) for n gradients (a multiple of 64, 16-B aligned); finalize turns `nparts` partials into
@@ -31,14 +34,15 @@ void launch_grad_clip_finalize(const float* partials, int64_t nparts, float gsca
 // tile, tiles, adapt / decay flag); a tile is at most lamb_tile() elements and never straddles two segments. Three
 // launches: moments + per-tile (Σw², Σu²) into partials[2 tile ...], per-segment (r, Σw², Σu²) into ratio[3 seg ...],
 // then the weight update (with the bf16 copy, or the hi / lo halves). coef: fp32 [8] on the device (lr, 1/(1-b1ᵗ),
-// 1/(1-b2ᵗ), eps, grad_scale, wd, -, -) overriding the scalars; clip: fp32 [1] multiplied into grad_scale; lr_mul:
-// fp32 [segments], each segment's learning-rate multiplier (indexed by global segment id; the weight update only).
+// 1/(1-b2ᵗ), eps, grad_scale, wd, ema_w, -) overriding the scalars; clip: fp32 [1] multiplied into grad_scale; lr_mul:
+// fp32 [segments], each segment's learning-rate multiplier (indexed by global segment id; the weight update only);
+// ema: fp32, laid out as p, the weight average ema += ema_w·(p_new - ema) written by the weight update.
 int lamb_tile();
 void launch_lamb(float* p, float* m, float* v, void* g, bool grad_bf16, bf16_t* out_bf16, bf16_t* out_lo,
                  const int64_t* tiles, const int64_t* segs, int64_t tile0, int64_t ntiles, int64_t seg0, int64_t nsegs,
                  float* partials, float* ratio, float lr, float ibc1, float ibc2, float eps, float b1, float b2,
                  float gscale, float wd, const float* coef, const float* clip, bool zero_grad, hipStream_t stream,
-                 const float* lr_mul = nullptr);
+                 const float* lr_mul = nullptr, float* ema = nullptr, float ema_w = 0.0f);
 
 }  // namespace hsd
 

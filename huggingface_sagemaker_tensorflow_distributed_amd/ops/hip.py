@@ -274,15 +274,20 @@ def _empty(shape, like, dtype=None):
 
 # ------------------------------------------------------------------------------------------ optimizer
 def adam_step(p, m, v, g, out, decay, step, eps, b1, b2, gscale, lr_wd, coef=None, out_lo=None, zero_grad=False,
-              clip=None, lr_mul=None):
+              clip=None, lr_mul=None, ema=None, ema_omd=0.0):
     """``coef``: optional fp32 [4] device tensor (step, eps, grad_scale, lr*wd) read by the kernel instead of the
     host scalars (captured HIP-graph steps, train/graph.py). ``out_lo``: with ``out``, the kernel writes the updated
     weights' bf16 hi / lo halves (fp32 compute: the split-product GEMMs' operands, ops/hip32.py). ``zero_grad``: the
     kernel also clears ``g`` after reading it. ``clip``: optional fp32 [1] device tensor, the step's global-norm
     clip coefficient (:func:`grad_clip_finalize`), multiplied into the gradient scale by the kernel. ``lr_mul``:
     optional fp32 ``[numel / 64]`` device tensor, the learning-rate multiplier of each 64-element block of the slice
-    passed (:meth:`FlatParamStore.block_table`): the kernel scales ``step`` and ``lr_wd`` by it."""
-    if lr_mul is not None:
+    passed (:meth:`FlatParamStore.block_table`): the kernel scales ``step`` and ``lr_wd`` by it. ``ema``: optional fp32
+    buffer laid out as ``p``, the weight average: the kernel also writes ``ema += ema_omd·(p_new - ema)`` with
+    ``ema_omd = float32(1 - decay)`` (three rounded fp32 operations); ``coef`` is then fp32 [8] with it in slot 4."""
+    if ema is not None:
+        _C.adam_step(p, m, v, g, out, decay, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zero_grad, clip, lr_mul,
+                     ema, float(ema_omd))
+    elif lr_mul is not None:
         _C.adam_step(p, m, v, g, out, decay, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zero_grad, clip, lr_mul)
     elif clip is None:
         _C.adam_step(p, m, v, g, out, decay, step, eps, b1, b2, gscale, lr_wd, coef, out_lo, zero_grad)
@@ -323,16 +328,19 @@ def lamb_plan(offsets, spans, adapt, numel: int, like):
 
 
 def lamb_step(plan, seg0, nsegs, p, m, v, g, out, out_lo, partials, ratio, lr, ibc1, ibc2, eps, b1, b2, gscale, wd,
-              coef=None, clip=None, zero_grad=False, lr_mul=None):
+              coef=None, clip=None, zero_grad=False, lr_mul=None, ema=None, ema_omd=0.0):
     """Fused LAMB on segments ``[seg0, seg0 + nsegs)`` of the whole flat buffers (three launches on the current
     stream, nothing returns to the host). ``partials``: fp32 ``[2 x plan.ntiles]`` (Σw², Σu² per tile); ``ratio``: fp32
     ``[3 x plan.nsegs]`` (r, Σw², Σu² per segment). ``ibc1`` / ``ibc2`` = ``1 / (1 - βᵗ)``. ``coef``: optional fp32 [8]
     device tensor ``(lr, ibc1, ibc2, eps, grad_scale, wd, -, -)`` read instead of the host scalars (captured steps);
     ``clip`` / ``out`` / ``out_lo`` / ``zero_grad`` as :func:`adam_step`. ``lr_mul``: optional fp32 ``[plan.nsegs]``
-    device tensor, each segment's learning-rate multiplier (the weight update only: ``ratio`` does not depend on it)."""
+    device tensor, each segment's learning-rate multiplier (the weight update only: ``ratio`` does not depend on it).
+    ``ema`` / ``ema_omd``: the weight average, as :func:`adam_step` (the whole buffer; ``coef`` slot 6)."""
     args = (plan, int(seg0), int(nsegs), p, m, v, g, out, out_lo, partials, ratio, float(lr), float(ibc1),
             float(ibc2), float(eps), float(b1), float(b2), float(gscale), float(wd), coef, clip, bool(zero_grad))
-    if lr_mul is None:
+    if ema is not None:
+        _C.lamb_step(*args, lr_mul, ema, float(ema_omd))
+    elif lr_mul is None:
         _C.lamb_step(*args)
     else:
         _C.lamb_step(*args, lr_mul)

@@ -36,6 +36,20 @@ the kernel scales ``step`` and ``lrÂ·wd`` by ONE fp32 multiply each, reading ``Î
 64-element block (:meth:`FlatParamStore.block_table`), so a segment gets the bits of a step on that segment alone with
 ``float32(stepÂ·Î¼)`` and ``float32(lrÂ·wdÂ·Î¼)``. The schedule keeps scaling :attr:`lr`; ``Î¼`` multiplies whatever it is
 at that step. ``None`` or all ones is off: no table, the launches without it.
+
+Weight averaging (``ema_decay=d``, ``0 < d < 1``; ``--ema_decay`` / ``--ema_warmup``; Keras ``use_ema``, timm's
+``ModelEmaV2``): one more fp32 buffer :attr:`ema`, laid out as ``store.master`` and starting as a bit copy of it. After
+optimizer step ``t`` (0 for the first update; one per optimizer step, not per accumulation micro-step), with ``Î¸`` the
+weight that step wrote, ``ema â† ema + Ï‰_tÂ·(Î¸ âˆ’ ema)`` as three separately rounded fp32 operations (subtract, multiply,
+add: never an FMA -- a torch fp32 replay ``e + w * (p - e)`` gives the same bits). ``Ï‰_t = float32(1 âˆ’ d_t)`` with
+``d_t = d``, or with ``ema_warmup`` ``d_t = min(d, (1 + t)/(10 + t))`` (``tf.train.ExponentialMovingAverage``'s
+``num_updates`` rule), both formed in Python floats and rounded once. The update kernel does it in the pass that writes
+``Î¸`` (one more 16-B load and store per chunk), so it rides every launch path the step has: slices under the backward,
+the clipped whole-buffer pass, captured steps (``Ï‰`` in :attr:`dcoef` slot 4). Nothing else reads :attr:`ema`: a step
+with averaging on writes the bits of a step without it everywhere else. Ranks need no collective: the average is a
+function of weights that are identical on every rank. :meth:`FusedAdam.ema_weights` exchanges the average into the
+store for evaluation and saving. In fp32 the average stops moving where ``Ï‰Â·(Î¸ âˆ’ ema)`` falls under half an ulp of
+``ema``, as every fp32 EMA does. 0 is off: nothing is allocated, the launches without it.
 """
 from __future__ import annotations
 
@@ -59,7 +73,7 @@ class FusedAdam:
 
     def __init__(self, store: FlatParamStore, lr: float = 1e-3, betas=(0.9, 0.999), eps: Optional[float] = None,
                  weight_decay: float = 0.0, eps_mode: str = "keras", decoupled: bool = True,
-                 max_grad_norm: float = 0.0, lr_multipliers=None):
+                 max_grad_norm: float = 0.0, lr_multipliers=None, ema_decay: float = 0.0, ema_warmup: bool = False):
         if eps_mode not in ("keras", "torch"):
             raise ValueError(eps_mode)
         if not float(max_grad_norm) >= 0.0:
@@ -95,6 +109,110 @@ class FusedAdam:
         self._mu_elem: Optional[torch.Tensor] = None  # CPU path: the multiplier of every element
         if self._mu is not None:
             self._build_lr_table()
+        # weight averaging: the decay (0 = off), the warm-up rule, and the average itself, allocated once at an address
+        # that stays put (captured graphs replay launches that write it; ema_weights exchanges contents, never tensors)
+        self.ema_decay = float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        if self.ema_decay != 0.0 and not (0.0 < self.ema_decay < 1.0):  # NaN and inf fail the comparison
+            raise ValueError(f"ema_decay must be 0 (off) or finite with 0 < d < 1: {ema_decay!r}")
+        if self.ema_warmup and self.ema_decay == 0.0:
+            raise ValueError("ema_warmup needs ema_decay > 0")
+        self.ema: Optional[torch.Tensor] = None
+        self._ema_w = 0.0  # this step's 1 - d_t (begin_step / step / prepare_device_step fix it)
+        self._ema_swapped = False
+        if self.ema_decay > 0.0:
+            self.ema = torch.empty_like(store.master)
+            self.reset_ema()
+
+    # -------------------------------------------------------------------------- weight averaging
+    def ema_decay_at(self, t: int) -> float:
+        """``d_t`` of optimizer step ``t`` (0 = the first update): ``d``, or ``min(d, (1 + t)/(10 + t))`` with
+        warm-up. A Python float; the step uses ``float32(1 - d_t)``."""
+        d = self.ema_decay
+        if self.ema_warmup:
+            d = min(d, (1.0 + t) / (10.0 + t))
+        return d
+
+    def _fix_ema_w(self) -> None:
+        """This step's ``Ï‰`` (call after :attr:`step_count` advanced: step ``t = step_count - 1``)."""
+        if self.ema is not None:
+            self._ema_w = 1.0 - self.ema_decay_at(self.step_count - 1)
+
+    def _ema_kw(self, st: Optional[int] = None, e: Optional[int] = None) -> dict:
+        """The ``ema`` / ``ema_omd`` keywords of a launch on slice ``[st, e)`` (the whole buffer by default); empty
+        when off, so the launch is the one made without the feature."""
+        if self.ema is None:
+            return {}
+        return {"ema": self.ema if st is None else self.ema[st:e], "ema_omd": self._ema_w}
+
+    def _ema_cpu_update(self) -> None:
+        """CPU path: the kernel's three rounded fp32 operations after the weight update."""
+        if self.ema is not None:
+            d = self.store.master - self.ema
+            d.mul_(torch.tensor(self._ema_w, dtype=torch.float32))
+            self.ema.add_(d)
+
+    @torch.no_grad()
+    def reset_ema(self) -> None:
+        """Restart the average from the current master weights (a bit copy): at construction, after the start-up
+        broadcast of a fresh run, and on a resume from a checkpoint that carries no average."""
+        if self.ema is not None:
+            self.ema.copy_(self.store.master)
+
+    def ema_state(self) -> Optional[Dict[str, torch.Tensor]]:
+        """``{segment name: view of the average}`` shaped as the parameters; None when off."""
+        if self.ema is None:
+            return None
+        return {sg.name: self.ema[sg.offset:sg.offset + sg.numel].view(sg.shape) for sg in self.store.segments}
+
+    def _no_step_in_swap(self) -> None:
+        if self._ema_swapped:
+            raise RuntimeError("a training step inside ema_weights(): the store holds the averaged weights; leave the "
+                               "context first")
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Scope in which the store holds the averaged weights (evaluation, saving): the CONTENTS of ``master`` and
+        :attr:`ema` are exchanged in place -- no tensor is rebound, captured eval graphs and parameter views point at
+        these addresses -- and the bf16 copy, the Wáµ€ / fp8 copies and the hi / lo halves are refreshed from them. On
+        exit the contents are exchanged back and the copies restored, every buffer to the bits it held on entry (the
+        fp8 copies, their scales and the activation amax history from a snapshot: re-quantising rolls that history).
+        ``m``, ``v`` and the step count are never touched. A training step inside the scope raises."""
+        if self.ema is None:
+            raise RuntimeError("ema_weights(): construct the optimizer with ema_decay > 0")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() is already active")
+        if getattr(self, "_began", False):
+            raise RuntimeError("ema_weights() inside an optimizer step (between begin_step and step)")
+        s = self.store
+        fp8 = [getattr(s, n) for n in ("fp8_w", "fp8_wt", "fp8_amax", "fp8_sinv", "fp8_act")] \
+            if getattr(s, "_fp8_desc", None) is not None else []
+        snap = [t.clone() for t in fp8]
+        self._exchange_ema()
+        s.sync_compute_from_master()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swapped = False
+            self._exchange_ema()
+            s.sync_compute_from_master()
+            for t, c in zip(fp8, snap):
+                t.copy_(c)
+
+    _EXCHANGE_CHUNK = 1 << 24  # elements per chunk of the in-place exchange: a 64 MB temporary, whatever the model
+
+    @torch.no_grad()
+    def _exchange_ema(self) -> None:
+        """Exchange the contents of ``master`` and :attr:`ema` in place, chunk by chunk through one small temporary."""
+        a, b = self.store.master, self.ema
+        tmp = torch.empty(min(self._EXCHANGE_CHUNK, a.numel()), dtype=a.dtype, device=a.device)
+        for st in range(0, a.numel(), tmp.numel()):
+            e = min(st + tmp.numel(), a.numel())
+            t = tmp[:e - st]
+            t.copy_(a[st:e])
+            a[st:e].copy_(b[st:e])
+            b[st:e].copy_(t)
 
     # -------------------------------------------------------------------------- per-parameter learning rates
     def _resolve_multipliers(self, given) -> Optional[torch.Tensor]:
@@ -175,12 +293,12 @@ class FusedAdam:
         out, out_lo = s.adam_outputs(0, s.numel)
         hip.adam_step(s.master, self.exp_avg, self.exp_avg_sq, s.grad, out, self._decay_mask, step, eps_eff,
                       self.beta1, self.beta2, gscale, self.lr * self.weight_decay, self._kernel_coef(), out_lo,
-                      zero_grad=zero_grad, clip=self._clip_out[1:2], lr_mul=self._lr_mul)
+                      zero_grad=zero_grad, clip=self._clip_out[1:2], lr_mul=self._lr_mul, **self._ema_kw())
         s.refresh_transposed()
 
     # --------------------------------------------------------------------------
     def state_tensors(self) -> List[torch.Tensor]:
-        return [self.exp_avg, self.exp_avg_sq]
+        return [self.exp_avg, self.exp_avg_sq] + ([self.ema] if self.ema is not None else [])
 
     def state_dict(self) -> dict:
         sd = {"step": self.step_count, "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(),
@@ -188,6 +306,10 @@ class FusedAdam:
               "weight_decay": self.weight_decay}
         if self._mu is not None:
             sd["lr_multipliers"] = self.lr_multipliers()
+        if self.ema is not None:
+            sd["ema"] = self.ema.cpu()
+            sd["ema_decay"] = self.ema_decay
+            sd["ema_warmup"] = self.ema_warmup
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -206,6 +328,18 @@ class FusedAdam:
             logger.warning("the checkpoint was written with %s and this optimizer runs with %s: the current "
                            "--layerwise_lr_decay / --head_lr_multiplier win", _describe_mul(was),
                            _describe_mul(self.lr_multipliers()))
+        was_ema = (float(sd.get("ema_decay", 0.0)), bool(sd.get("ema_warmup", False)))
+        if was_ema != (self.ema_decay, self.ema_warmup):
+            logger.warning("the checkpoint was written with %s and this optimizer runs with %s: the current "
+                           "--ema_decay / --ema_warmup win", _describe_ema(*was_ema),
+                           _describe_ema(self.ema_decay, self.ema_warmup))
+        if self.ema is not None:
+            if sd.get("ema") is not None:
+                self.ema.copy_(sd["ema"].to(self.ema.device))
+            else:
+                logger.warning("the checkpoint carries no weight average: the average restarts from the loaded "
+                               "weights")
+                self.reset_ema()
 
     def _coeffs(self):
         t = self.step_count
@@ -217,12 +351,13 @@ class FusedAdam:
 
     # -------------------------------------------------------------------------- device-side coefficients
     def use_device_coef(self) -> torch.Tensor:
-        """The fp32 [4] device tensor (step, eps, grad_scale, lr*wd) that Adam launches CAPTURED into a HIP graph of
-        the whole training step read instead of kernel arguments, so replays run with each step's bias correction
-        and learning rate (train/graph.py). :meth:`prepare_device_step` fills it before a replay. Only launches
-        issued inside :meth:`capturing` read it; eager steps always pass their own scalars."""
+        """The fp32 [8] device tensor (step, eps, grad_scale, lr*wd, 1 - ema decay, -, -, -) that Adam launches
+        CAPTURED into a HIP graph of the whole training step read instead of kernel arguments, so replays run with
+        each step's bias correction, learning rate and averaging weight (train/graph.py). :meth:`prepare_device_step`
+        fills it before a replay. Only launches issued inside :meth:`capturing` read it; eager steps always pass their
+        own scalars."""
         if self.dcoef is None:
-            self.dcoef = torch.zeros(4, dtype=torch.float32, device=self.store.master.device)
+            self.dcoef = torch.zeros(8, dtype=torch.float32, device=self.store.master.device)
         return self.dcoef
 
     @contextlib.contextmanager
@@ -241,10 +376,12 @@ class FusedAdam:
     def prepare_device_step(self, grad_scale: float) -> None:
         """Advance the step count and write this step's scalars to :attr:`dcoef` (stream-ordered H2D copy of a
         fresh host tensor: the host may move on at once)."""
+        self._no_step_in_swap()
         self.step_count += 1
         step, eps_eff = self._coeffs()
-        self.dcoef.copy_(torch.tensor([step, eps_eff, float(grad_scale), self.lr * self.weight_decay],
-                                      dtype=torch.float32), non_blocking=True)
+        self._fix_ema_w()
+        self.dcoef.copy_(torch.tensor([step, eps_eff, float(grad_scale), self.lr * self.weight_decay, self._ema_w,
+                                       0.0, 0.0, 0.0], dtype=torch.float32), non_blocking=True)
 
     # -------------------------------------------------------------------------- overlap with backward
     def enable_overlap(self, ranges: List[Tuple[int, int]], on_ready: Optional[Callable] = None) -> None:
@@ -279,8 +416,10 @@ class FusedAdam:
     def begin_step(self, grad_scale: float, zero_grad: bool = False) -> None:
         """Fix this step's coefficients before backward (the slices are stepped during it). ``zero_grad``: each slice's
         Adam also clears the gradients it read (:meth:`step`)."""
+        self._no_step_in_swap()
         self.step_count += 1
         step, eps_eff = self._coeffs()
+        self._fix_ema_w()
         self._coef = (step, eps_eff, float(grad_scale))
         self._zero = bool(zero_grad) and self.store.grad.is_cuda
         self._done = [False] * len(self._ranges)
@@ -314,7 +453,7 @@ class FusedAdam:
         dm = self._decay_mask[st // ALIGN:(e + ALIGN - 1) // ALIGN] if self._decay_mask is not None else None
         hip.adam_step(s.master[st:e], self.exp_avg[st:e], self.exp_avg_sq[st:e], s.grad[st:e], out, dm, step,
                       eps_eff, self.beta1, self.beta2, gscale, self.lr * self.weight_decay, self._kernel_coef(), out_lo,
-                      zero_grad=getattr(self, "_zero", False), lr_mul=self._lr_mul_slice(st, e))
+                      zero_grad=getattr(self, "_zero", False), lr_mul=self._lr_mul_slice(st, e), **self._ema_kw(st, e))
         if self._tsub is not None:
             s.refresh_transposed_subset(self._tsub[b])
         if self._f8sub is not None:
@@ -352,8 +491,10 @@ class FusedAdam:
         if getattr(self, "_began", False):
             self._finish_overlapped(grad_scale)
             return
+        self._no_step_in_swap()
         self.step_count += 1
         step, eps_eff = self._coeffs()
+        self._fix_ema_w()
         s = self.store
         write_compute = s.compute is not s.master
         if s.master.is_cuda:
@@ -368,7 +509,7 @@ class FusedAdam:
             hip.adam_step(s.master, self.exp_avg, self.exp_avg_sq, s.grad, out,
                           self._decay_mask, step, eps_eff, self.beta1, self.beta2, float(grad_scale),
                           self.lr * self.weight_decay, self._kernel_coef(), out_lo, zero_grad=zero_grad,
-                          lr_mul=self._lr_mul)
+                          lr_mul=self._lr_mul, **self._ema_kw())
             s.refresh_transposed()
             return
         # reference path (CPU): identical math on flat buffers
@@ -400,6 +541,7 @@ class FusedAdam:
         else:
             s.master.sub_((torch.tensor(step, dtype=torch.float32) * mu) * self.exp_avg
                           / self.exp_avg_sq.sqrt().add_(eps_eff))
+        self._ema_cpu_update()
         if write_compute:
             s.compute.copy_(s.master)
 
@@ -409,6 +551,10 @@ def _describe_mul(mul: Optional[Dict[str, float]]) -> str:
         return "no learning-rate multipliers"
     v = list(mul.values())
     return f"learning-rate multipliers in [{min(v):.6g}, {max(v):.6g}]"
+
+
+def _describe_ema(decay: float, warmup: bool) -> str:
+    return f"weight averaging at decay {decay:g}{' with warm-up' if warmup else ''}" if decay else "no weight averaging"
 
 
 def plan_ranges(store: FlatParamStore, bucket_mb: float) -> Tuple[List[Tuple[int, int]], List[int]]:

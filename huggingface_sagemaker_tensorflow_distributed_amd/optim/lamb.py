@@ -21,6 +21,9 @@ the gradient averaged over ranks and accumulation micro-steps (``grad_scale · g
 * Per-parameter learning rates (``lr_multipliers``, as :class:`FusedAdam`'s): ``w ← w − ((lr·μ)·r)·u`` with ``μ``
   the segment's fp32 multiplier. ``u``, the norms and ``r`` do not depend on ``μ``: the ``(r, Σw², Σu²)`` table a step
   writes is the same bits with and without multipliers. The kernel reads ``μ`` from an fp32 ``[segments]`` table.
+* Weight averaging (``ema_decay``, as :class:`FusedAdam`'s): the weight-update kernel also writes
+  ``ema ← ema + ω·(w_new − ema)``; ``u``, the norms, ``r`` and every other output do not see it. Captured steps read
+  ``ω`` from :attr:`dcoef` slot 6.
 * The Horovod-style scripts keep multiplying the learning rate by the world size (``train/runner.py``); LAMB does not
   change that rule.
 
@@ -30,7 +33,7 @@ run's hi / lo halves) in the same pass. No atomics and a fixed combine order: tw
 against a whole-buffer one, give the same bits. The norms are per segment, so -- unlike global-norm clipping -- the
 slices stay overlapped with the backward (:meth:`FusedAdam.enable_overlap`). Nothing returns to the host: every launch
 captures into the whole-step HIP graph, where the per-step scalars come from :attr:`dcoef`, fp32 ``[8]`` =
-``(lr, 1/(1-β1ᵗ), 1/(1-β2ᵗ), ε, grad_scale, wd, -, -)``.
+``(lr, 1/(1-β1ᵗ), 1/(1-β2ᵗ), ε, grad_scale, wd, 1 - ema decay, -)``.
 
 With ``max_grad_norm > 0`` the clip structure of :class:`FusedAdam` is kept: the hooks run ``grad_sumsq`` per slice
 under the backward, and :meth:`step` finishes the norm and runs LAMB over the whole buffer with the device-side
@@ -53,9 +56,11 @@ class FusedLamb(FusedAdam):
     kind = "lamb"
 
     def __init__(self, store: FlatParamStore, lr: float = 1e-3, betas=(0.9, 0.999), eps: Optional[float] = None,
-                 weight_decay: float = 0.0, max_grad_norm: float = 0.0, lr_multipliers=None):
+                 weight_decay: float = 0.0, max_grad_norm: float = 0.0, lr_multipliers=None,
+                 ema_decay: float = 0.0, ema_warmup: bool = False):
         super().__init__(store, lr=lr, betas=betas, eps=1e-6 if eps is None else eps, weight_decay=weight_decay,
-                         eps_mode="keras", max_grad_norm=max_grad_norm, lr_multipliers=lr_multipliers)
+                         eps_mode="keras", max_grad_norm=max_grad_norm, lr_multipliers=lr_multipliers,
+                         ema_decay=ema_decay, ema_warmup=ema_warmup)
         segs = store.segments
         dev = store.master.device
         self._spans = [(segs[i + 1].offset if i + 1 < len(segs) else (s.offset + s.numel + ALIGN - 1) // ALIGN * ALIGN)
@@ -109,9 +114,9 @@ class FusedLamb(FusedAdam):
 
     # -------------------------------------------------------------------------- device-side coefficients
     def use_device_coef(self) -> torch.Tensor:
-        """The fp32 [8] device tensor ``(lr, 1/(1-β1ᵗ), 1/(1-β2ᵗ), ε, grad_scale, wd, -, -)`` that LAMB launches
-        captured into a whole-step graph read instead of kernel arguments. (The clip finalize kernel reads the gradient
-        scale from slot 2 of a [4] tensor of its own, filled by the same copy.)"""
+        """The fp32 [8] device tensor ``(lr, 1/(1-β1ᵗ), 1/(1-β2ᵗ), ε, grad_scale, wd, 1 - ema decay, -)`` that LAMB
+        launches captured into a whole-step graph read instead of kernel arguments. (The clip finalize kernel reads the
+        gradient scale from slot 2 of a [4] tensor of its own, filled by the same copy.)"""
         if self.dcoef is None:
             both = torch.zeros(12, dtype=torch.float32, device=self.store.master.device)
             self.dcoef, self._dclip = both[:8], both[8:]
@@ -119,10 +124,12 @@ class FusedLamb(FusedAdam):
         return self.dcoef
 
     def prepare_device_step(self, grad_scale: float) -> None:
+        self._no_step_in_swap()
         self.step_count += 1
         ibc1, ibc2 = self._coeffs()
+        self._fix_ema_w()
         gs = float(grad_scale)
-        self._dboth.copy_(torch.tensor([self.lr, ibc1, ibc2, self.eps, gs, self.weight_decay, 0.0, 0.0,
+        self._dboth.copy_(torch.tensor([self.lr, ibc1, ibc2, self.eps, gs, self.weight_decay, self._ema_w, 0.0,
                                         0.0, 0.0, gs, 0.0], dtype=torch.float32), non_blocking=True)
 
     # -------------------------------------------------------------------------- overlap with backward
@@ -147,7 +154,7 @@ class FusedLamb(FusedAdam):
         out, out_lo = s.adam_outputs(0, s.numel)
         hip.lamb_step(self._plan, seg0, nsegs, s.master, self.exp_avg, self.exp_avg_sq, s.grad, out, out_lo,
                       self._partials, self._ratio, self.lr, ibc1, ibc2, self.eps, self.beta1, self.beta2, gscale,
-                      self.weight_decay, self._kernel_coef(), clip, zero_grad, lr_mul=self._lr_mul)
+                      self.weight_decay, self._kernel_coef(), clip, zero_grad, lr_mul=self._lr_mul, **self._ema_kw())
 
     @torch.no_grad()
     def step_range(self, b: int) -> None:
@@ -185,8 +192,10 @@ class FusedLamb(FusedAdam):
         if getattr(self, "_began", False):
             self._finish_overlapped(grad_scale)
             return
+        self._no_step_in_swap()
         self.step_count += 1
         ibc1, ibc2 = self._coeffs()
+        self._fix_ema_w()
         s = self.store
         if s.master.is_cuda:
             from ..ops import hip
@@ -231,5 +240,6 @@ class FusedLamb(FusedAdam):
             if self._mu is not None:
                 lr = lr * self._mu[i]  # the kernel's rounding: fp32 lr times the fp32 multiplier, then times r
             w.sub_(u * float(lr * self._ratio[i, 0]))
+        self._ema_cpu_update()
         if s.compute is not s.master:
             s.compute.copy_(s.master)

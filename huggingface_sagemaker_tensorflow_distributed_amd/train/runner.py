@@ -13,6 +13,7 @@ step 1, Q5 rank-0-only save + barrier, Q6 global metrics.
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import logging
 import os
@@ -199,6 +200,17 @@ def _lr_multipliers(args, store, cfg, lr: float):
     return mul
 
 
+def _ema_flags(args):
+    """``(--ema_decay, --ema_warmup)`` of the run: the decay is 0 (off) or finite in (0, 1); warm-up needs a decay."""
+    d = float(getattr(args, "ema_decay", 0.0) or 0.0)
+    warm = bool(getattr(args, "ema_warmup", False))
+    if d != 0.0 and not (0.0 < d < 1.0):  # NaN and inf fail the comparison
+        raise ValueError(f"--ema_decay {d} must be 0 (off) or finite with 0 < D < 1")
+    if warm and d == 0.0:
+        raise ValueError("--ema_warmup true needs --ema_decay D with 0 < D < 1")
+    return d, warm
+
+
 def _conll_tags(args) -> Optional[List[str]]:
     """The tag list of ``--task token-classification --dataset conll`` (read once, kept on ``args``)."""
     if getattr(args, "task", "") != "token-classification" or args.dataset != "conll":
@@ -279,6 +291,10 @@ def _provenance(args, model, rank: int, n_train: int, n_eval: int, batch_plan=No
     if decay != 1.0 or head != 1.0:
         info["layerwise_lr_decay"] = decay
         info["head_lr_multiplier"] = head
+    ema_d, ema_warm = _ema_flags(args)
+    if ema_d:
+        info["ema_decay"] = ema_d
+        info["ema_warmup"] = ema_warm
     if batch_plan is not None:
         info["auto_batch"] = batch_plan.as_dict()
     if synthetic or weights == "random-init":
@@ -322,6 +338,7 @@ def build(args, mode: str):
         raise ValueError(_PTYPE_DATASETS.format(ptype, args.dataset))
     smoothing = _label_smoothing(args, task, ptype)
     _lr_group_flags(args)
+    ema_d, ema_warm = _ema_flags(args)
     tags = _conll_tags(args)
     if tags is not None:
         if args.num_labels != len(tags):
@@ -374,11 +391,17 @@ def build(args, mode: str):
         if args.adam_eps_mode != "keras":
             logger.info("--adam_eps_mode %s does not apply to --optimizer lamb (ignored)", args.adam_eps_mode)
         opt = FusedLamb(store, lr=lr, eps=args.adam_epsilon, weight_decay=args.weight_decay,
-                        max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0), lr_multipliers=lr_mul)
+                        max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0), lr_multipliers=lr_mul,
+                        ema_decay=ema_d, ema_warmup=ema_warm)
     else:
         opt = FusedAdam(store, lr=lr, eps=args.adam_epsilon, eps_mode=args.adam_eps_mode,
                         weight_decay=args.weight_decay if args.optimizer == "adamw" else 0.0,
-                        max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0), lr_multipliers=lr_mul)
+                        max_grad_norm=float(getattr(args, "max_grad_norm", 0.0) or 0.0), lr_multipliers=lr_mul,
+                        ema_decay=ema_d, ema_warmup=ema_warm)
+    if ema_d:
+        logger.info("--ema_decay %g --ema_warmup %s: the fused %s step keeps an fp32 average of the weights (%.1f MB "
+                    "more on the device); the final evaluation and the saved model are those of the averaged weights",
+                    ema_d, "true" if ema_warm else "false", args.optimizer, opt.ema.numel() * 4 / 2**20)
     batch_plan = None
     if args.train_batch_size == "auto":
         # sized on the device before any readiness hook / bucketer exists (the probes are plain fwd + bwd)
@@ -414,6 +437,8 @@ def build(args, mode: str):
     if args.resume_from:
         initial_epoch = int(load_checkpoint(args.resume_from, trainer).get("epoch", 0))
     broadcast_parameters(store, opt if args.resume_from else None)
+    if not args.resume_from:
+        opt.reset_ema()  # the average starts from the weights every rank now holds
     return {"initial_epoch": initial_epoch, "tokenizer": tokenizer, "max_len": max_len, "batch_plan": batch_plan,
             "model": model, "store": store, "optimizer": opt, "bucketer": bucketer, "trainer": trainer,
             "device": dev, "world": world, "rank": rank, "lr": lr, "dtype": dtype_name}
@@ -517,7 +542,9 @@ def run(argv: Optional[Sequence[str]] = None, mode: str = "train") -> dict:
     if args.do_eval:
         logger.info("*** Evaluate ***")
         start = time.time()
-        result = trainer.evaluate(test_loader)  # the meter's global all-reduce syncs the device
+        # with --ema_decay the final scores are those of the averaged weights (Keras' finalize_variable_values at the end
+        # of fit); the meter's global all-reduce syncs the device
+        result = trainer.evaluate(test_loader, weights="ema" if parts["optimizer"].ema is not None else None)
         eval_runtime = round(time.time() - start, 4)
         # not in eval_results.txt (the reference's writer holds the metrics only, scripts/train.py:172-179): the log line
         # and run_provenance-style JSON beside it time the reference's other measured phase, model.evaluate (:170)
@@ -535,7 +562,11 @@ def run(argv: Optional[Sequence[str]] = None, mode: str = "train") -> dict:
 
     # Q5: rank-0-only save, then barrier
     if rank == 0:
-        save_pretrained(model, args.model_dir, state_dict=master_state_dict(model, parts["store"]))
+        # with --ema_decay the saved model is the averaged one (checkpoint-* directories keep the raw weights, with the
+        # average in optimizer.pt, so a resume continues both)
+        averaged = parts["optimizer"].ema_weights() if parts["optimizer"].ema is not None else contextlib.nullcontext()
+        with averaged:
+            save_pretrained(model, args.model_dir, state_dict=master_state_dict(model, parts["store"]))
         tokenizer.save_pretrained(args.model_dir)
     backend.barrier()
     out["global_step"] = trainer.global_step

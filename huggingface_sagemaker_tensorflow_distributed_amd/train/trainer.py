@@ -265,6 +265,10 @@ class Trainer:
         ``FusedAdam(max_grad_norm=...)`` computes the global norm of the averaged gradient on the device inside the
         step, ``optimizer.grad_norm()`` reads it (a device sync: call it when logging), and ``--max_grad_norm inf``
         reports the norm without ever clipping."""
+        if getattr(self.optimizer, "_ema_swapped", False):
+            # before anything is queued: the store holds the averaged weights (optimizer.ema_weights())
+            raise RuntimeError("train_step inside optimizer.ema_weights(): the store holds the averaged weights; "
+                               "leave the context first")
         self.model.train()
         if self._seed is not None and self._graph_replay and self._full_graph and len(micro_batches) == 1:
             return self._graph_step(micro_batches[0], meter)
@@ -498,7 +502,15 @@ class Trainer:
         return loss, logits, False
 
     @torch.no_grad()
-    def evaluate(self, loader, max_steps: Optional[int] = None) -> Dict[str, float]:
+    def evaluate(self, loader, max_steps: Optional[int] = None, weights: Optional[str] = None) -> Dict[str, float]:
+        """``weights="ema"``: score the averaged weights (``--ema_decay``; the evaluation runs inside
+        :meth:`FusedAdam.ema_weights`, which puts every buffer back afterwards). The default scores the weights the
+        store holds."""
+        if weights == "ema":
+            with self.optimizer.ema_weights():
+                return self.evaluate(loader, max_steps)
+        if weights is not None:
+            raise ValueError(f"evaluate(weights={weights!r}): None or 'ema'")
         self.model.eval()
         self.eval_graph_active = False
         meter = _Meter(self.device)

@@ -112,6 +112,15 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
     g.add_argument("--head_lr_multiplier", type=float, default=1.0,
                    help="learning-rate multiplier M > 0 of the head (pooler, classifier, qa_outputs, MLM transform: "
                         "everything above the encoder), for a freshly initialised head; 1 (default) = off")
+    g.add_argument("--ema_decay", type=float, default=0.0,
+                   help="exponential moving average of the weights, decay 0 < D < 1 (Keras Adam(use_ema=True, "
+                        "ema_momentum=D), timm ModelEmaV2), kept by the fused optimizer step itself; the final "
+                        "evaluation and the saved model are those of the averaged weights; 0 (default) = off, as the "
+                        "reference")
+    g.add_argument("--ema_warmup", type=str2bool, default=False,
+                   help="with --ema_decay: step t averages with min(D, (1 + t) / (10 + t)) "
+                        "(tf.train.ExponentialMovingAverage's num_updates rule), so a short run does not mostly "
+                        "average its initial weights")
     g.add_argument("--lr_schedule", choices=["constant", "linear"], default="constant",
                    help="constant = Keras Adam(learning_rate) (reference); linear = warmup then linear decay to 0")
     g.add_argument("--lr_warmup_steps", type=int, default=0, help="linear warmup steps of the learning rate")
