@@ -594,6 +594,51 @@ void attn_varlen_bwd(torch::Tensor qkv, torch::Tensor cu_seqlens, torch::Tensor 
                               (int)B, (int)max_seqlen, (int)heads, p, (uint64_t)seed, cur_stream());
 }
 
+// head-dim-32 attention, an even number of heads (attention_d32.hip). cu_seqlens given: packed qkv [T, 3H], S =
+// max_seqlen, lse2 [heads, T], dead rows come back as zeros. cu_seqlens None: padded qkv [B*S, 3H], even S, mask =
+// optional additive fp32 key bias [B, S], lse2 [B, heads, S]. Returns the row count T.
+static int64_t check_d32(const torch::Tensor& qkv, const c10::optional<torch::Tensor>& cu,
+                         const c10::optional<torch::Tensor>& mask, int64_t B, int64_t S, int64_t heads) {
+  check_bf16(qkv, "qkv");
+  TORCH_CHECK(heads >= 2 && heads % 2 == 0, "attn_d32 works on pairs of heads: an even number of heads");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == 3 * heads * 32, "attn_d32 requires qkv [rows, 3H] with head_dim 32");
+  TORCH_CHECK(!(cu.has_value() && mask.has_value()), "attn_d32: a packed batch (cu_seqlens) takes no mask");
+  const int64_t T = qkv.size(0);
+  TORCH_CHECK(B >= 1 && S >= 1 && T >= 1 && B * (heads / 2) <= 65535 && T * heads < (int64_t(1) << 31),
+              "attn_d32 sizes");
+  if (cu.has_value()) {
+    CHECK_CUDA(*cu); CHECK_CONTIG(*cu); CHECK_DTYPE(*cu, torch::kInt32);
+    TORCH_CHECK(cu->numel() == B + 1, "cu_seqlens holds B + 1 offsets");
+  } else {
+    TORCH_CHECK(S % 2 == 0, "sequence length must be even");
+    TORCH_CHECK(T == B * S, "attn_d32 padded shapes");
+    if (mask.has_value()) { check_f32(*mask, "mask"); TORCH_CHECK(mask->numel() == B * S, "mask shape"); }
+  }
+  return T;
+}
+
+void attn_d32_fwd(torch::Tensor qkv, c10::optional<torch::Tensor> cu_seqlens, c10::optional<torch::Tensor> mask,
+                  torch::Tensor out, torch::Tensor lse2, int64_t B, int64_t S, int64_t heads, double p, int64_t seed) {
+  const int64_t T = check_d32(qkv, cu_seqlens, mask, B, S, heads);
+  check_bf16(out, "out"); check_f32(lse2, "lse2");
+  TORCH_CHECK(out.numel() == T * heads * 32 && lse2.numel() == heads * T, "attn_d32_fwd shapes");
+  hsd::launch_attn_d32_fwd(CBF(qkv), cu_seqlens.has_value() ? cu_seqlens->data_ptr<int32_t>() : nullptr, OPT_F(mask),
+                           BF(out), lse2.data_ptr<float>(), (int)T, (int)B, (int)S, (int)heads, p, (uint64_t)seed,
+                           cur_stream());
+}
+
+void attn_d32_bwd(torch::Tensor qkv, c10::optional<torch::Tensor> cu_seqlens, c10::optional<torch::Tensor> mask,
+                  torch::Tensor o, torch::Tensor dout, torch::Tensor lse2, torch::Tensor dqkv, int64_t B, int64_t S,
+                  int64_t heads, double p, int64_t seed) {
+  const int64_t T = check_d32(qkv, cu_seqlens, mask, B, S, heads);
+  check_bf16(o, "o"); check_bf16(dout, "dout"); check_bf16(dqkv, "dqkv"); check_f32(lse2, "lse2");
+  TORCH_CHECK(dqkv.numel() == qkv.numel() && o.numel() == T * heads * 32 && dout.numel() == o.numel() &&
+                  lse2.numel() == heads * T, "attn_d32_bwd shapes");
+  hsd::launch_attn_d32_bwd(CBF(qkv), cu_seqlens.has_value() ? cu_seqlens->data_ptr<int32_t>() : nullptr, OPT_F(mask),
+                           CBF(o), CBF(dout), lse2.data_ptr<float>(), BF(dqkv), (int)T, (int)B, (int)S, (int)heads, p,
+                           (uint64_t)seed, cur_stream());
+}
+
 // attention + fp8 copy of its output (forward: e4m3 of the context; backward: dqkv in format qfmt), S > 128 streaming
 // kernels only (attn_q8_supported); amax_in / sinv / amax_track: fp32 [1] delayed-scaling site slots
 static void check_q8(const torch::Tensor& q8, int64_t numel, const torch::Tensor& a, const torch::Tensor& s,
@@ -1752,6 +1797,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_varlen_bwd", &attn_varlen_bwd, py::arg("qkv"), py::arg("cu_seqlens"), py::arg("o"), py::arg("dout"),
         py::arg("lse2"), py::arg("dqkv"), py::arg("B"), py::arg("max_seqlen"), py::arg("heads"), py::arg("p"),
         py::arg("seed"), py::arg("dbias") = py::none());
+  m.def("attn_d32_fwd", &attn_d32_fwd, py::arg("qkv"), py::arg("cu_seqlens"), py::arg("mask"), py::arg("out"),
+        py::arg("lse2"), py::arg("B"), py::arg("S"), py::arg("heads"), py::arg("p"), py::arg("seed"));
+  m.def("attn_d32_bwd", &attn_d32_bwd, py::arg("qkv"), py::arg("cu_seqlens"), py::arg("mask"), py::arg("o"),
+        py::arg("dout"), py::arg("lse2"), py::arg("dqkv"), py::arg("B"), py::arg("S"), py::arg("heads"), py::arg("p"),
+        py::arg("seed"));
+  m.def("attn_d32_supported", [](int64_t heads, int64_t head_dim, int64_t S) {
+    return hsd::attn_d32_supported((int)heads, (int)head_dim, (int)S);
+  });
   m.def("gemm", &gemm, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("la"), py::arg("lb"), py::arg("epi"),
         py::arg("bias"), py::arg("aux"), py::arg("C2"), py::arg("p"), py::arg("seed"), py::arg("splits"),
         py::arg("row_mul") = 1);

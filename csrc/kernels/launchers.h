@@ -213,6 +213,16 @@ void launch_attn_varlen_fwd(const bf16_t* qkv, const int* cu_seqlens, bf16_t* ou
 void launch_attn_varlen_bwd(const bf16_t* qkv, const int* cu_seqlens, const bf16_t* o, const bf16_t* dout,
                             const float* lse2, bf16_t* dqkv, float* dbias, int T, int B, int max_seqlen, int heads,
                             double p, uint64_t seed, hipStream_t st);
+// attention_d32.hip: head_dim 32, an even number of heads (one workgroup per pair of adjacent heads), bf16.
+// cu_seqlens given: the packed form of attention_varlen.hip (qkv [T, 3H], S = max_seqlen, lse2 [heads, T], dead rows
+// zeroed, mask must be null). cu_seqlens null: the padded form (qkv [B*S, 3H], T = B*S, even S, mask = optional additive
+// fp32 key bias [B, S], lse2 [B, heads, S]). The backward writes every dqkv element once (no atomics, no workspace).
+bool attn_d32_supported(int heads, int head_dim, int S);
+void launch_attn_d32_fwd(const bf16_t* qkv, const int* cu_seqlens, const float* mask, bf16_t* out, float* lse2, int T,
+                         int B, int S, int heads, double p, uint64_t seed, hipStream_t st);
+void launch_attn_d32_bwd(const bf16_t* qkv, const int* cu_seqlens, const float* mask, const bf16_t* o,
+                         const bf16_t* dout, const float* lse2, bf16_t* dqkv, int T, int B, int S, int heads, double p,
+                         uint64_t seed, hipStream_t st);
 }  // namespace hsd
 
 namespace hsd {

@@ -641,6 +641,58 @@ def attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed):
     return _AttentionVarlen.apply(qkv, cu_seqlens.contiguous(), max_seqlen, heads, p, seed)
 
 
+# ---- head dim 32 (csrc/kernels/attention_d32.hip): explicit ops. :func:`attention` and :func:`attention_varlen` do not
+# dispatch to them, so no model or trainer path reaches these kernels (README, "Head dim 32").
+def attention_d32_ok(qkv, seq, heads) -> bool:
+    """What :func:`attention_d32` takes: head dim 32, an even number of heads (one workgroup works on a pair of
+    adjacent heads), an even sequence length."""
+    return heads % 2 == 0 and qkv.shape[-1] == 3 * heads * 32 and seq % 2 == 0 and seq > 0
+
+
+class _AttentionD32(torch.autograd.Function):
+    """Head-dim-32 attention, padded (``cu_seqlens`` None, ``S`` = the sequence length, optional key bias) or packed
+    (``S`` = max_seqlen)."""
+
+    @staticmethod
+    def forward(ctx, qkv, cu_seqlens, mask_bias, B, S, heads, p, seed):
+        qkv = qkv.contiguous()
+        T, H = qkv.shape[0], qkv.shape[-1] // 3
+        out = torch.empty((T, H), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty(heads * T, dtype=torch.float32, device=qkv.device)
+        mb = mask_bias.contiguous().float() if mask_bias is not None else None
+        _C.attn_d32_fwd(qkv, cu_seqlens, mb, out, lse, B, S, heads, float(p), _s64(seed))
+        ctx.save_for_backward(qkv, out, lse, mb, cu_seqlens)
+        ctx.B, ctx.S, ctx.heads, ctx.p, ctx.seed = B, S, heads, float(p), seed
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, mb, cu = ctx.saved_tensors
+        dqkv = torch.empty_like(qkv)
+        _C.attn_d32_bwd(qkv, cu, mb, out, dout.contiguous(), lse, dqkv, ctx.B, ctx.S, ctx.heads, ctx.p, _s64(ctx.seed))
+        return dqkv, None, None, None, None, None, None, None
+
+
+def attention_d32(qkv, mask_bias, batch, seq, heads, p, seed):
+    """:func:`attention` for head dim 32: ``qkv [B*S, 3H]`` bf16, optional additive fp32 key bias ``[B, S]``. An
+    unsupported shape (:func:`attention_d32_ok`) is an error, not a fall-back."""
+    if not attention_d32_ok(qkv, seq, heads):
+        raise ValueError(f"attention_d32: qkv {tuple(qkv.shape)}, S = {seq}: head dim 32, an even number of heads "
+                         f"({heads}) and an even S only")
+    return _AttentionD32.apply(qkv.reshape(batch * seq, -1), None, mask_bias, batch, seq, heads, p, seed)
+
+
+def attention_d32_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed):
+    """:func:`attention_varlen` for head dim 32 with an even number of heads."""
+    if qkv.dim() != 2 or heads % 2 or qkv.shape[-1] != 3 * heads * 32:
+        raise ValueError(f"attention_d32_varlen: qkv {tuple(qkv.shape)} is not [T, 3 * {heads} * 32] with an even "
+                         f"number of heads")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.device != qkv.device:
+        raise ValueError("attention_d32_varlen: cu_seqlens must be an int32 tensor on qkv's device")
+    return _AttentionD32.apply(qkv, cu_seqlens.contiguous(), None, cu_seqlens.numel() - 1, int(max_seqlen), heads, p,
+                               seed)
+
+
 # ------------------------------------------------------------------------------------------ GEMM helpers
 EPI_STORE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_RES, EPI_DGELU, EPI_F32_ATOMIC = range(7)
 EPI_F32_SLAB, EPI_BIAS_GELU_D, EPI_MUL, EPI_STORE_RDOT = 7, 8, 9, 10  # gemm2 only
