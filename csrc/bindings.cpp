@@ -1563,6 +1563,68 @@ void token_head_bwd_given(torch::Tensor h, torch::Tensor W, torch::Tensor g0, to
                                    db.data_ptr<float>(), (int)R, (int)H, (int)C, p, (uint64_t)seed, cur_stream());
 }
 
+// the same head for 17 <= classes <= 64 (token_head_wide.hip): the arguments of token_head_fwd / token_head_bwd;
+// partials fp32 [token_head_wide_fwd_blocks(R)][4], part fp32 >= token_head_wide_bwd_blocks(R, H) · (C·H + C)
+static void token_head_wide_check(const torch::Tensor& h, const torch::Tensor& W, const torch::Tensor& logits) {
+  TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() && h.scalar_type() == torch::kBFloat16,
+              "token_head_wide h");
+  const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
+  TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 16 && H % 8 == 0 && H >= 8 && H <= 1024 && C >= 17 && C <= 64,
+              "token_head_wide: 1 <= rows < 2^31, H % 8 == 0, H <= 1024, 17 <= classes <= 64");
+  check_bf16_2d(W, C, H, "token_head_wide W");
+  check_bf16_2d(logits, R, C, "token_head_wide logits");
+}
+
+void token_head_wide_fwd(torch::Tensor h, torch::Tensor W, torch::Tensor b, c10::optional<torch::Tensor> labels,
+                         torch::Tensor logits, torch::Tensor partials, torch::Tensor stats, double p, int64_t seed,
+                         double label_smoothing) {
+  const float eps = check_smoothing(label_smoothing, "token_head_wide");
+  token_head_wide_check(h, W, logits);
+  const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
+  check_bf16_vec(b, C, "token_head_wide b");
+  check_f32(partials, "partials");
+  check_f32(stats, "stats");
+  TORCH_CHECK(partials.numel() >= 4 * (int64_t)hsd::token_head_wide_fwd_blocks((int)R) && stats.numel() >= 4,
+              "token_head_wide stats");
+  int lds_max = 0;  // the W image is dynamic LDS, up to 132 KB: a device that cannot give it is refused here
+  TORCH_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, h.get_device()) == hipSuccess &&
+              hsd::token_head_wide_fwd_lds((int)H, (int)C) <= lds_max,
+              "token_head_wide: the W image needs ", hsd::token_head_wide_fwd_lds((int)H, (int)C),
+              " B of LDS per workgroup, the device allows ", lds_max);
+  hsd::launch_token_head_wide_fwd(CBF(h), CBF(W), CBF(b), head_labels(labels, R), BF(logits),
+                                  partials.data_ptr<float>(), stats.data_ptr<float>(), (int)R, (int)H, (int)C, p,
+                                  (uint64_t)seed, cur_stream(), eps);
+}
+
+void token_head_wide_bwd(torch::Tensor h, torch::Tensor W, torch::Tensor logits, torch::Tensor labels,
+                         torch::Tensor stats, torch::Tensor dloss, c10::optional<torch::Tensor> dh, torch::Tensor part,
+                         torch::Tensor dW, torch::Tensor db, double p, int64_t seed, double label_smoothing) {
+  const float eps = check_smoothing(label_smoothing, "token_head_wide");
+  token_head_wide_check(h, W, logits);
+  const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
+  const int64_t* lab = head_labels(labels, R);
+  check_f32(stats, "stats");
+  check_f32(dloss, "dloss");
+  check_f32(part, "part");
+  check_f32(dW, "dW");
+  check_f32(db, "db");
+  TORCH_CHECK(stats.numel() >= 4 && dloss.numel() >= 1, "token_head_wide stats / dloss");
+  TORCH_CHECK(part.numel() >= (int64_t)hsd::token_head_wide_bwd_blocks((int)R, (int)H) * (C * H + C),
+              "token_head_wide workspace");
+  TORCH_CHECK(dW.numel() == C * H && db.numel() == C, "token_head_wide grads");
+  hsd::bf16_t* dhp = nullptr;
+  if (dh.has_value()) {
+    check_bf16_2d(*dh, R, H, "dh");
+    dhp = BF(*dh);
+  }
+  hsd::launch_token_head_wide_bwd(CBF(h), CBF(W), CBF(logits), lab, stats.data_ptr<float>(), dloss.data_ptr<float>(),
+                                  dhp, part.data_ptr<float>(), dW.data_ptr<float>(), db.data_ptr<float>(), (int)R,
+                                  (int)H, (int)C, p, (uint64_t)seed, cur_stream(), eps);
+}
+
+int64_t token_head_wide_fwd_blocks(int64_t R) { return hsd::token_head_wide_fwd_blocks((int)R); }
+int64_t token_head_wide_bwd_blocks(int64_t R, int64_t H) { return hsd::token_head_wide_bwd_blocks((int)R, (int)H); }
+
 // span-extraction loss (qa_head.hip). logits [R][2] bf16; cu int32 [B+1]; mask int64 [R] or none; pos int64 [B][2] or
 // none (pred only); rec fp32 [B][8], pred int32 [B][2], g0 fp32 [R][2], stats fp32 [8]
 void span_ce(torch::Tensor logits, torch::Tensor cu, c10::optional<torch::Tensor> mask,
@@ -1851,6 +1913,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed"), py::arg("label_smoothing") = 0.0);
   m.def("token_head_bwd_given", &token_head_bwd_given);
   m.def("span_ce", &span_ce);
+  m.def("token_head_wide_fwd", &token_head_wide_fwd, py::arg("h"), py::arg("W"), py::arg("b"), py::arg("labels"),
+        py::arg("logits"), py::arg("partials"), py::arg("stats"), py::arg("p"), py::arg("seed"),
+        py::arg("label_smoothing") = 0.0);
+  m.def("token_head_wide_bwd", &token_head_wide_bwd, py::arg("h"), py::arg("W"), py::arg("logits"), py::arg("labels"),
+        py::arg("stats"), py::arg("dloss"), py::arg("dh"), py::arg("part"), py::arg("dW"), py::arg("db"), py::arg("p"),
+        py::arg("seed"), py::arg("label_smoothing") = 0.0);
+  m.def("token_head_wide_fwd_blocks", &token_head_wide_fwd_blocks);
+  m.def("token_head_wide_bwd_blocks", &token_head_wide_bwd_blocks);
   m.def("token_head_fwd_blocks", &token_head_fwd_blocks);
   m.def("token_head_bwd_blocks", &token_head_bwd_blocks);
   m.def("memset0", &memset0);

@@ -172,6 +172,19 @@ void launch_token_head_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* logit
 void launch_token_head_bwd_given(const bf16_t* h, const bf16_t* W, const float* g0, const float* cnt, float gmul,
                                  const float* dloss, bf16_t* dh, float* part, float* dW, float* db, int R, int H,
                                  int C, double p, uint64_t seed, hipStream_t st);
+// token_head_wide.hip: the same head for 17 <= C <= 64 (same arguments and semantics; no given-gradient entry). The
+// forward takes token_head_wide_fwd_lds(H, C) bytes of dynamic LDS (up to 132 KB: the device must allow it per
+// workgroup); the backward writes token_head_wide_bwd_blocks(R, H) slabs of C·H + C.
+int token_head_wide_fwd_blocks(int R);
+int token_head_wide_bwd_blocks(int R, int H);
+int64_t token_head_wide_fwd_lds(int H, int C);
+void launch_token_head_wide_fwd(const bf16_t* h, const bf16_t* W, const bf16_t* b, const int64_t* labels,
+                                bf16_t* logits, float* partials, float* stats, int R, int H, int C, double p,
+                                uint64_t seed, hipStream_t st, float label_smoothing = 0.0f);
+void launch_token_head_wide_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* logits, const int64_t* labels,
+                                const float* stats, const float* dloss, bf16_t* dh, float* part, float* dW, float* db,
+                                int R, int H, int C, double p, uint64_t seed, hipStream_t st,
+                                float label_smoothing = 0.0f);
 // qa_head.hip: span-extraction loss of --task question-answering on logits [R][2] bf16. One workgroup per sequence
 // (rows cu[b] .. cu[b+1]-1, at most 1,024; mask int64 [R] optional), then the stats reducer. pos int64 [B][2] may be
 // null (pred only: rec, g0 and stats untouched). rec fp32 [B][8], pred int32 [B][2], g0 fp32 [R][2], stats fp32 [8].

@@ -5,7 +5,7 @@
 //       logits = classifier(dropout(sequence_output)), CrossEntropyLoss over the rows whose label is not -100.
 //
 //   forward   d       = bf16(h · keep · 1/(1-p))      the hash dropout of ops/rng.py, element (row, col) of [R, H]
-//             logits  = bf16(d·Wᵀ + b)                [R, C], 2 <= C <= 16
+//             logits  = bf16(d·Wᵀ + b)                [R, C], 2 <= C <= 16 (17 .. 64: token_head_wide.hip)
 //             per valid row: logsumexp(logits) - logits[label], first-maximum argmax hit (from the rounded logits)
 //             per-block partial sums -> head_stats_kernel (head_stats.hip) -> stats = {mean loss, hits, n_valid,
 //             loss sum}

@@ -40,7 +40,8 @@ COMMON_FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wno-un
 # kernel files keep their fp32 math on the single-lane forms (the older files are left as they were measured). Its
 # only effect on the compiled file: the forward kernel takes 200 VGPRs (2 waves/SIMD) instead of 221 (1 wave/SIMD); the
 # backward kernels and scratch (0) are the same either way.
-FILE_FLAGS = {"attention_d32.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"attention_d32.hip": NO_PACKED_FP32, "token_head_wide.hip": NO_PACKED_FP32}
 
 
 def _torch_flags():

@@ -344,8 +344,9 @@ def token_head(h2d, w, b, labels, p: float, seed: int, label_smoothing: float = 
     on the host).
 
     bf16 GPU tensors within ``hip.token_head_ok`` (H % 8 == 0, H <= 1024, 2 <= C <= 16) run the fused kernels of
-    csrc/kernels/token_head.hip, unless ``HSD_TOKEN_HEAD=composed``. Everything else (CPU tensors, fp32 GPU tensors,
-    ``HSD_OPS=torch``, other shapes) runs the composed ``dropout -> linear -> cross_entropy`` with the same seed and
+    csrc/kernels/token_head.hip, and the same tensors with 17 <= C <= 64 (``hip.token_head_wide_ok``) those of
+    csrc/kernels/token_head_wide.hip, unless ``HSD_TOKEN_HEAD=composed``. Everything else (CPU tensors, fp32 GPU
+    tensors, ``HSD_OPS=torch``, C > 64, H > 1024, other shapes) runs the composed ``dropout -> linear -> cross_entropy`` with the same seed and
     so the same mask; the all-torch form of it is ``reference.token_head``, the kernels' oracle.
 
     ``label_smoothing`` ε > 0: the smoothed CE on every path (the fused kernels' smoothed instantiations, ``_sum_ce``,
@@ -353,11 +354,18 @@ def token_head(h2d, w, b, labels, p: float, seed: int, label_smoothing: float = 
     eps = _smoothing(label_smoothing)
     lab = labels.reshape(-1) if labels is not None else None
     needs_grad = torch.is_grad_enabled() and (h2d.requires_grad or w.requires_grad or b.requires_grad)
-    if _hip(h2d) and TOKEN_HEAD_FUSED and _hipmod().token_head_ok(h2d, w) and not (lab is None and needs_grad):
-        if lab is None:  # inference: the fused forward alone (differentiable logits take the composed ops below)
-            return _hipmod().token_head_logits(h2d, w, b, p, seed)
-        loss, logits, stats = _hipmod().token_head(h2d, w, b, lab, p, seed, eps)
-        return _with_stats(loss, stats), logits
+    if _hip(h2d) and TOKEN_HEAD_FUSED and not (lab is None and needs_grad):
+        hip = _hipmod()
+        if hip.token_head_ok(h2d, w):
+            if lab is None:  # inference: the fused forward alone (differentiable logits take the composed ops below)
+                return hip.token_head_logits(h2d, w, b, p, seed)
+            loss, logits, stats = hip.token_head(h2d, w, b, lab, p, seed, eps)
+            return _with_stats(loss, stats), logits
+        if hip.token_head_wide_ok(h2d, w):  # 17 .. 64 classes: the kernels of token_head_wide.hip
+            if lab is None:
+                return hip.token_head_wide_logits(h2d, w, b, p, seed)
+            loss, logits, stats = hip.token_head_wide(h2d, w, b, lab, p, seed, eps)
+            return _with_stats(loss, stats), logits
     if _hip(h2d) or (_hip32(h2d) and w.shape[0] % 4 == 0):  # (the fp32 GEMM epilogue takes whole groups of 4 columns)
         logits = linear(dropout(h2d, p, seed), w, b)
         return logits if lab is None else (_sum_ce(logits, lab.long(), None, eps), logits)

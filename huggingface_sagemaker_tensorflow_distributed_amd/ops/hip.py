@@ -1631,6 +1631,64 @@ def token_head_logits(h2d, w, b, p, seed):
     return _token_logits(h2d.detach().contiguous(), w.detach().contiguous(), b.detach().contiguous(), p, seed)
 
 
+def token_head_wide_ok(h2d, w) -> bool:
+    """What csrc/kernels/token_head_wide.hip takes: the rows of ``token_head_ok`` with 17 <= C <= 64."""
+    if h2d.dim() != 2 or w.dim() != 2:
+        return False
+    R, H = h2d.shape
+    return (h2d.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and 1 <= R < (1 << 31) - 16 and H % 8 == 0
+            and 8 <= H <= 1024 and 17 <= w.shape[0] <= 64 and w.shape[1] == H)
+
+
+def _token_wide_fwd(x, wc, bc, lab, p, seed, smooth=0.0):
+    """tokw_fwd_kernel (+ the stats reducer with labels): (logits, stats); stats is scratch without labels."""
+    logits = torch.empty((x.shape[0], wc.shape[0]), dtype=x.dtype, device=x.device)
+    scratch = torch.empty(_C.token_head_wide_fwd_blocks(x.shape[0]) * 4 + 4, dtype=torch.float32, device=x.device)
+    _C.token_head_wide_fwd(x, wc, bc, lab, logits, scratch[4:], scratch[:4], float(p), _s64(seed), smooth)
+    return logits, scratch[:4]
+
+
+class _TokenHeadWide(torch.autograd.Function):
+    """``_TokenHead`` on the kernels of token_head_wide.hip (17 .. 64 classes): one forward kernel + the stats
+    reducer; backward one kernel over (row blocks x 256-column ranges) with per-row-block fp32 dW / db slabs in the
+    shared workspace + the slab reducer that adds into main_grad."""
+
+    @staticmethod
+    def forward(ctx, h2d, w, b, labels, p, seed, smooth):
+        x = h2d.contiguous()
+        lab = labels.contiguous().long()
+        logits, stats = _token_wide_fwd(x, w.contiguous(), b.contiguous(), lab, p, seed, smooth)
+        ctx.save_for_backward(x, w, b, logits, lab, stats)
+        ctx.cfg = (float(p), seed, smooth)
+        ctx.mark_non_differentiable(logits, stats)
+        ctx.set_materialize_grads(False)
+        return stats[0], logits, stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits, _dstats):
+        x, w, b, logits, lab, stats = ctx.saved_tensors
+        p, seed, smooth = ctx.cfg
+        R, H = x.shape
+        C = w.shape[0]
+        g_w, g_b = _Grad(w), _Grad(b)
+        dh = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        part = _workspace(_C.token_head_wide_bwd_blocks(R, H) * (C * H + C), x.device)
+        _C.token_head_wide_bwd(x, w.contiguous(), logits, lab, stats, _dloss1(dloss, x.device), dh, part,
+                               g_w.buf.view(-1), g_b.buf.view(-1), p, _s64(seed), smooth)
+        return dh, g_w.done(), g_b.done(), None, None, None, None
+
+
+def token_head_wide(h2d, w, b, labels, p, seed, label_smoothing: float = 0.0):
+    """``token_head`` for 17 .. 64 classes: (loss, logits, stats), the same contract, on token_head_wide.hip."""
+    return _TokenHeadWide.apply(h2d, w, b, labels, p, seed, _smoothing(label_smoothing))
+
+
+def token_head_wide_logits(h2d, w, b, p, seed):
+    """The wide head's logits alone (inference: no labels, no autograd)."""
+    return _token_wide_fwd(h2d.detach().contiguous(), w.detach().contiguous(), b.detach().contiguous(), None, p,
+                           seed)[0]
+
+
 # ------------------------------------------------------------------------------------------ question-answering head
 QA_MAX_SEQLEN = 1024  # rows of one sequence the span kernel holds in LDS (csrc/kernels/qa_head.hip)
 
