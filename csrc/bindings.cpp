@@ -1170,6 +1170,37 @@ void attn32m_bwd(torch::Tensor qh, torch::Tensor ql, torch::Tensor doh, torch::T
                           (uint64_t)seed, cur_stream());
 }
 
+// the same over packed sequences (attention32m_varlen.hip): qkv halves [T, 3H], cu_seqlens int32 [B+1] on the device,
+// out / dqkv fp32, lse2 and delta [heads, T]; rows from cu_seqlens[B] on are dead and come back as zeros
+void attn32m_varlen_fwd(torch::Tensor qh, torch::Tensor ql, torch::Tensor cu_seqlens, torch::Tensor out,
+                        torch::Tensor lse2, int64_t B, int64_t max_seqlen, int64_t heads, double p, int64_t seed) {
+  const int* cu = check_varlen(qh, cu_seqlens, B, max_seqlen, heads);
+  check_bf16(ql, "qkv_lo"); check_f32(out, "out"); check_f32(lse2, "lse2");
+  const int64_t T = qh.size(0);
+  TORCH_CHECK(qh.sizes() == ql.sizes() && out.numel() == T * heads * 64 && lse2.numel() == heads * T,
+              "attn32m_varlen_fwd shapes (head dim 64)");
+  hsd::launch_attn32m_varlen_fwd(CBF(qh), CBF(ql), cu, out.data_ptr<float>(), lse2.data_ptr<float>(), (int)T, (int)B,
+                                 (int)max_seqlen, (int)heads, p, (uint64_t)seed, cur_stream());
+}
+
+void attn32m_varlen_bwd(torch::Tensor qh, torch::Tensor ql, torch::Tensor doh, torch::Tensor dol,
+                        torch::Tensor cu_seqlens, torch::Tensor o, torch::Tensor dout, torch::Tensor lse2,
+                        torch::Tensor dqkv, torch::Tensor delta, int64_t B, int64_t max_seqlen, int64_t heads, double p,
+                        int64_t seed) {
+  const int* cu = check_varlen(qh, cu_seqlens, B, max_seqlen, heads);
+  check_bf16(ql, "qkv_lo"); check_bf16(doh, "dout_hi"); check_bf16(dol, "dout_lo");
+  check_f32(o, "o"); check_f32(dout, "dout"); check_f32(lse2, "lse2"); check_f32(dqkv, "dqkv"); check_f32(delta, "delta");
+  const int64_t T = qh.size(0);
+  TORCH_CHECK(qh.sizes() == ql.sizes() && dqkv.numel() == qh.numel() && doh.sizes() == dol.sizes() &&
+              doh.numel() == T * heads * 64 && o.numel() == doh.numel() && dout.numel() == doh.numel() &&
+              lse2.numel() == heads * T && delta.numel() >= heads * T, "attn32m_varlen_bwd shapes");
+  hsd::launch_attn32_delta(o.data_ptr<float>(), dout.data_ptr<float>(), delta.data_ptr<float>(), 1, (int)T, (int)heads,
+                           cur_stream());
+  hsd::launch_attn32m_varlen_bwd(CBF(qh), CBF(ql), CBF(doh), CBF(dol), cu, lse2.data_ptr<float>(),
+                                 delta.data_ptr<float>(), dqkv.data_ptr<float>(), (int)T, (int)B, (int)max_seqlen,
+                                 (int)heads, p, (uint64_t)seed, cur_stream());
+}
+
 void cls32_fwd(torch::Tensor pre, torch::Tensor W2, torch::Tensor b2, torch::Tensor labels, torch::Tensor t_out,
                torch::Tensor logits, torch::Tensor stats, int64_t act, double p, int64_t seed) {
   check_f32(pre, "pre"); check_f32(W2, "W2"); check_f32(b2, "b2"); check_f32(t_out, "t_out"); check_f32(logits, "logits");
@@ -1816,6 +1847,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn32m_supported", [](int64_t S) { return hsd::attn32m_supported((int)S, 64); });
   m.def("attn32m_fwd", &attn32m_fwd);
   m.def("attn32m_bwd", &attn32m_bwd);
+  m.def("attn32m_varlen_fwd", &attn32m_varlen_fwd);
+  m.def("attn32m_varlen_bwd", &attn32m_varlen_bwd);
   m.def("cls32_fwd", &cls32_fwd);
   m.def("cls32_bwd", &cls32_bwd);
   m.def("refresh_env", &hsd::refresh_env_knobs, "re-read the HSD_* launch knobs (cached per generation)");

@@ -277,6 +277,15 @@ void launch_attn32m_fwd(const bf16_t* qkv_hi, const bf16_t* qkv_lo, const float*
 void launch_attn32m_bwd(const bf16_t* qkv_hi, const bf16_t* qkv_lo, const bf16_t* do_hi, const bf16_t* do_lo,
                         const float* mask, const float* lse2, const float* delta, float* dqkv, int B, int S, int heads,
                         double p, uint64_t seed, hipStream_t st);
+// attention32m_varlen.hip: the same split products over a packed qkv [T, 3H] (hi + lo halves); sequence b is rows
+// cu_seqlens[b] .. cu_seqlens[b+1]-1 (device int32 [B+1]), rows from cu_seqlens[B] on are dead (written as zeros);
+// out / dqkv fp32, lse2 and delta (launch_attn32_delta with B = 1, S = T) are [heads, T]. No atomics, any max_seqlen.
+void launch_attn32m_varlen_fwd(const bf16_t* qkv_hi, const bf16_t* qkv_lo, const int* cu_seqlens, float* out,
+                               float* lse2, int T, int B, int max_seqlen, int heads, double p, uint64_t seed,
+                               hipStream_t st);
+void launch_attn32m_varlen_bwd(const bf16_t* qkv_hi, const bf16_t* qkv_lo, const bf16_t* do_hi, const bf16_t* do_lo,
+                               const int* cu_seqlens, const float* lse2, const float* delta, float* dqkv, int T, int B,
+                               int max_seqlen, int heads, double p, uint64_t seed, hipStream_t st);
 void launch_cls32_fwd(const float* pre, const float* W2, const float* b2, const int64_t* labels, float* t_out,
                       float* logits, float* stats, int R, int H, int C, int act, double p, uint64_t seed,
                       hipStream_t st);

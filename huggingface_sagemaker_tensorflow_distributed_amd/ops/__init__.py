@@ -202,10 +202,12 @@ def attention(qkv, mask_bias, batch, seq, heads, p, seed):
 
 
 def attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed):
-    """Attention over packed sequences (``--pack_sequences``): bf16 GPU tensors run the varlen HIP kernels,
-    everything else the reference op."""
+    """Attention over packed sequences (``--pack_sequences``): bf16 GPU tensors run the varlen HIP kernels, fp32 GPU
+    tensors with head dim 64 their split-product fp32 form (ops/hip32.py), everything else the reference op."""
     if _hip(qkv) and qkv.dtype == torch.bfloat16:
         return _hipmod().attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed)
+    if _hip32(qkv) and _hip32mod().attention_varlen_ok(qkv, heads):
+        return _hip32mod().attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed)
     return _ref.attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed, p > 0)
 
 

@@ -514,6 +514,47 @@ def attention(qkv, mask_bias, batch, seq, heads, p, seed):
     return _Attention32.apply(qkv, mask_bias, batch, seq, heads, p, seed)
 
 
+class _Attention32MVarlen(torch.autograd.Function):
+    """:class:`_Attention32M` over packed sequences (attention32m_varlen.hip): qkv ``[T, 3H]``, sequence ``b`` in rows
+    ``cu_seqlens[b] .. cu_seqlens[b+1]-1``, any ``max_seqlen``; the dead rows of out and dqkv come back as zeros."""
+
+    @staticmethod
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, heads, p, seed):
+        T, H = qkv.shape[0], qkv.shape[-1] // 3
+        B = cu_seqlens.numel() - 1
+        qh, ql = _split2(qkv)
+        out = torch.empty((T, H), dtype=torch.float32, device=qkv.device)
+        lse = torch.empty(heads * T, dtype=torch.float32, device=qkv.device)
+        _C.attn32m_varlen_fwd(qh, ql, cu_seqlens, out, lse, B, int(max_seqlen), heads, float(p), _s64(seed))
+        ctx.save_for_backward(qh, ql, out, lse, cu_seqlens)
+        ctx.cfg = (B, int(max_seqlen), heads, float(p), seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qh, ql, out, lse, cu = ctx.saved_tensors
+        B, max_seqlen, heads, p, seed = ctx.cfg
+        dout = dout.contiguous()
+        dh, dl = _split2(dout)
+        dqkv = torch.empty(qh.shape, dtype=torch.float32, device=qh.device)
+        delta = torch.empty(lse.numel(), dtype=torch.float32, device=qh.device)
+        _C.attn32m_varlen_bwd(qh, ql, dh, dl, cu, out, dout, lse, dqkv, delta, B, max_seqlen, heads, p, _s64(seed))
+        return dqkv, None, None, None, None, None
+
+
+def attention_varlen_ok(qkv, heads) -> bool:
+    return qkv.dim() == 2 and qkv.shape[-1] == 3 * heads * 64 and qkv.dtype == torch.float32 and qkv.is_contiguous()
+
+
+def attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed):
+    """``qkv [T, 3H]`` fp32 (:func:`attention_varlen_ok`), ``cu_seqlens`` int32 [B+1] on the device (data/packing.py)."""
+    if not attention_varlen_ok(qkv, heads):
+        raise ValueError(f"attention_varlen: qkv {tuple(qkv.shape)} is not a contiguous fp32 [T, 3 * {heads} * 64]")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.device != qkv.device:
+        raise ValueError("attention_varlen: cu_seqlens must be an int32 tensor on qkv's device")
+    return _Attention32MVarlen.apply(qkv, cu_seqlens.contiguous(), max_seqlen, heads, p, seed)
+
+
 # ------------------------------------------------------------------------------------------ fused encoder blocks
 # The post-LN residual of a block, LN(dropout(f(h) Wᵀ + b) + h), gives h two consumers; as separate autograd ops
 # the two gradients of h are summed by an ATen add (2 per layer, ~0.5 ms of a bert-large B = 8 step). The fused

@@ -319,9 +319,9 @@ def build(args, mode: str):
     dtype_name = args.dtype or ("bf16" if on_gpu else "fp32")
     compute_dtype = _DTYPES[dtype_name]
     pack = bool(getattr(args, "pack_sequences", False))
-    if pack and (dtype_name == "fp8" or (dtype_name == "fp32" and on_gpu)):
-        raise ValueError(f"--pack_sequences true runs in bf16 on the GPU (the variable-length attention kernels are "
-                         f"bf16; CPU fp32 runs the reference ops): --dtype {dtype_name} is not supported with it")
+    if pack and dtype_name == "fp8":
+        raise ValueError("--pack_sequences true is not supported with --dtype fp8 (the variable-length attention "
+                         "kernels are bf16 and fp32)")
     grad_dtype = {"fp32": torch.float32, "bf16": torch.bfloat16}[args.grad_dtype or "fp32"]
     torch.manual_seed(args.seed)
 
