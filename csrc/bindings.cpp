@@ -639,6 +639,59 @@ void attn_d32_bwd(torch::Tensor qkv, c10::optional<torch::Tensor> cu_seqlens, c1
                            (uint64_t)seed, cur_stream());
 }
 
+// relative-position-bias attention, head dim 64 (attention_relbias.hip): rel fp32 [heads, R]; layouts as attn_d32's.
+// Returns the row count T.
+static int64_t check_relbias(const torch::Tensor& qkv, const c10::optional<torch::Tensor>& cu,
+                             const c10::optional<torch::Tensor>& mask, const torch::Tensor& rel, int64_t B, int64_t S,
+                             int64_t heads) {
+  check_bf16(qkv, "qkv"); check_f32(rel, "rel");
+  TORCH_CHECK(heads >= 1 && qkv.dim() == 2 && qkv.size(1) == 3 * heads * 64,
+              "attn_relbias requires qkv [rows, 3H] with head_dim 64");
+  TORCH_CHECK(rel.dim() == 2 && rel.size(0) == heads, "attn_relbias: rel is [heads, R]");
+  TORCH_CHECK(S >= 1 && hsd::attn_relbias_supported(64, (int)S, (int)rel.size(1)),
+              "attn_relbias: S <= 1024 and an odd R >= 2 S - 1");
+  TORCH_CHECK(!(cu.has_value() && mask.has_value()), "attn_relbias: a packed batch (cu_seqlens) takes no mask");
+  const int64_t T = qkv.size(0);
+  TORCH_CHECK(B >= 1 && T >= 1 && B * heads <= 65535 && T * heads < (int64_t(1) << 31), "attn_relbias sizes");
+  if (cu.has_value()) {
+    CHECK_CUDA(*cu); CHECK_CONTIG(*cu); CHECK_DTYPE(*cu, torch::kInt32);
+    TORCH_CHECK(cu->numel() == B + 1, "cu_seqlens holds B + 1 offsets");
+  } else {
+    TORCH_CHECK(S % 2 == 0, "sequence length must be even");
+    TORCH_CHECK(T == B * S, "attn_relbias padded shapes");
+    if (mask.has_value()) { check_f32(*mask, "mask"); TORCH_CHECK(mask->numel() == B * S, "mask shape"); }
+  }
+  return T;
+}
+
+void attn_relbias_fwd(torch::Tensor qkv, c10::optional<torch::Tensor> cu_seqlens, c10::optional<torch::Tensor> mask,
+                      torch::Tensor rel, torch::Tensor out, torch::Tensor lse2, int64_t B, int64_t S, int64_t heads,
+                      double p, int64_t seed) {
+  const int64_t T = check_relbias(qkv, cu_seqlens, mask, rel, B, S, heads);
+  check_bf16(out, "out"); check_f32(lse2, "lse2");
+  TORCH_CHECK(out.numel() == T * heads * 64 && lse2.numel() == heads * T, "attn_relbias_fwd shapes");
+  hsd::launch_attn_relbias_fwd(CBF(qkv), cu_seqlens.has_value() ? cu_seqlens->data_ptr<int32_t>() : nullptr,
+                               OPT_F(mask), rel.data_ptr<float>(), BF(out), lse2.data_ptr<float>(), (int)T, (int)B,
+                               (int)S, (int)heads, (int)rel.size(1), p, (uint64_t)seed, cur_stream());
+}
+
+void attn_relbias_bwd(torch::Tensor qkv, c10::optional<torch::Tensor> cu_seqlens, c10::optional<torch::Tensor> mask,
+                      torch::Tensor rel, torch::Tensor o, torch::Tensor dout, torch::Tensor lse2, torch::Tensor dqkv,
+                      torch::Tensor drel, torch::Tensor slab, int64_t B, int64_t S, int64_t heads, double p,
+                      int64_t seed) {
+  const int64_t T = check_relbias(qkv, cu_seqlens, mask, rel, B, S, heads);
+  check_bf16(o, "o"); check_bf16(dout, "dout"); check_bf16(dqkv, "dqkv"); check_f32(lse2, "lse2");
+  check_f32(drel, "drel"); check_f32(slab, "slab");
+  TORCH_CHECK(dqkv.numel() == qkv.numel() && o.numel() == T * heads * 64 && dout.numel() == o.numel() &&
+                  lse2.numel() == heads * T && drel.numel() == rel.numel(), "attn_relbias_bwd shapes");
+  TORCH_CHECK(slab.numel() >= hsd::attn_relbias_slab_numel((int)B, (int)S, (int)heads, (int)rel.size(1)),
+              "attn_relbias_bwd: the slab is too small");
+  hsd::launch_attn_relbias_bwd(CBF(qkv), cu_seqlens.has_value() ? cu_seqlens->data_ptr<int32_t>() : nullptr,
+                               OPT_F(mask), rel.data_ptr<float>(), CBF(o), CBF(dout), lse2.data_ptr<float>(), BF(dqkv),
+                               drel.data_ptr<float>(), slab.data_ptr<float>(), (int)T, (int)B, (int)S, (int)heads,
+                               (int)rel.size(1), p, (uint64_t)seed, cur_stream());
+}
+
 // attention + fp8 copy of its output (forward: e4m3 of the context; backward: dqkv in format qfmt), S > 128 streaming
 // kernels only (attn_q8_supported); amax_in / sinv / amax_track: fp32 [1] delayed-scaling site slots
 static void check_q8(const torch::Tensor& q8, int64_t numel, const torch::Tensor& a, const torch::Tensor& s,
@@ -1899,6 +1952,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed"));
   m.def("attn_d32_supported", [](int64_t heads, int64_t head_dim, int64_t S) {
     return hsd::attn_d32_supported((int)heads, (int)head_dim, (int)S);
+  });
+  m.def("attn_relbias_fwd", &attn_relbias_fwd, py::arg("qkv"), py::arg("cu_seqlens"), py::arg("mask"), py::arg("rel"),
+        py::arg("out"), py::arg("lse2"), py::arg("B"), py::arg("S"), py::arg("heads"), py::arg("p"), py::arg("seed"));
+  m.def("attn_relbias_bwd", &attn_relbias_bwd, py::arg("qkv"), py::arg("cu_seqlens"), py::arg("mask"), py::arg("rel"),
+        py::arg("o"), py::arg("dout"), py::arg("lse2"), py::arg("dqkv"), py::arg("drel"), py::arg("slab"), py::arg("B"),
+        py::arg("S"), py::arg("heads"), py::arg("p"), py::arg("seed"));
+  m.def("attn_relbias_supported", [](int64_t head_dim, int64_t S, int64_t R) {
+    return S <= 1024 && hsd::attn_relbias_supported((int)head_dim, (int)S, (int)R);
+  });
+  m.def("attn_relbias_slab_numel", [](int64_t B, int64_t S, int64_t heads, int64_t R) {
+    return hsd::attn_relbias_slab_numel((int)B, (int)S, (int)heads, (int)R);
   });
   m.def("gemm", &gemm, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("la"), py::arg("lb"), py::arg("epi"),
         py::arg("bias"), py::arg("aux"), py::arg("C2"), py::arg("p"), py::arg("seed"), py::arg("splits"),

@@ -236,6 +236,20 @@ void launch_attn_d32_fwd(const bf16_t* qkv, const int* cu_seqlens, const float* 
 void launch_attn_d32_bwd(const bf16_t* qkv, const int* cu_seqlens, const float* mask, const bf16_t* o,
                          const bf16_t* dout, const float* lse2, bf16_t* dqkv, int T, int B, int S, int heads, double p,
                          uint64_t seed, hipStream_t st);
+// attention_relbias.hip: head_dim 64 attention with a relative-position bias rel (fp32 [heads, R], R odd, R >= 2S - 1:
+// the score of query i and key j takes rel[h][j - i + (R-1)/2]), bf16, S <= 1024. Layouts as attention_d32.hip's
+// (cu_seqlens given: packed, S = max_seqlen; null: padded, even S, optional key bias `mask`). The backward writes every
+// dqkv element once and drel (fp32 [heads, R], overwritten) through `slab`, attn_relbias_slab_numel fp32 words of
+// workspace; no atomics.
+bool attn_relbias_supported(int head_dim, int S, int R);
+int64_t attn_relbias_slab_numel(int B, int S, int heads, int R);
+void launch_attn_relbias_fwd(const bf16_t* qkv, const int* cu_seqlens, const float* mask, const float* rel, bf16_t* out,
+                             float* lse2, int T, int B, int S, int heads, int R, double p, uint64_t seed,
+                             hipStream_t st);
+void launch_attn_relbias_bwd(const bf16_t* qkv, const int* cu_seqlens, const float* mask, const float* rel,
+                             const bf16_t* o, const bf16_t* dout, const float* lse2, bf16_t* dqkv, float* drel,
+                             float* slab, int T, int B, int S, int heads, int R, double p, uint64_t seed,
+                             hipStream_t st);
 }  // namespace hsd
 
 namespace hsd {

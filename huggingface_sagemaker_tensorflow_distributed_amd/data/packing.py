@@ -99,6 +99,6 @@ def unpack_rows(x: np.ndarray, cu_seqlens: np.ndarray, S: int) -> np.ndarray:
 def position_rule(cfg) -> Dict[str, int]:
     """``pad_id`` / ``pos_base`` / ``pad_pos`` of a model config (models/config.py) for :func:`pack_batch`."""
     pad = int(cfg.pad_token_id)
-    if cfg.model_type == "roberta":
+    if cfg.model_type in ("roberta", "mpnet"):
         return {"pad_id": pad, "pos_base": pad + 1, "pad_pos": pad}
     return {"pad_id": pad, "pos_base": 0, "pad_pos": 0}

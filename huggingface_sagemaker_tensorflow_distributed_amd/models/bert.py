@@ -18,7 +18,7 @@ import torch.nn as nn
 from .. import ops
 from ..ops.rng import DropoutSeeds
 from .config import ModelConfig, check_problem_type
-from .encoder import EncoderLayer, _param, layer_hf_names
+from .encoder import EncoderLayer, _param, bias_by_distance, layer_hf_names
 
 
 class Embeddings(nn.Module):
@@ -31,10 +31,22 @@ class Embeddings(nn.Module):
         self.token_type_embeddings = _param(cfg.type_vocab_size, H) if cfg.type_vocab_size > 0 else None
         self.ln_weight = _param(H)
         self.ln_bias = _param(H)
+        # MPNet: the relative-position bias table of the attention scores, shared by all layers (HF keeps it on the
+        # encoder; here it sits with the other tables that feed every layer: depth 0 of optim/groups.py, weight decay on)
+        self.relative_attention_table = (_param(cfg.relative_attention_num_buckets, cfg.num_attention_heads)
+                                         if cfg.model_type == "mpnet" else None)
+
+    def relative_bias(self, S: int) -> Optional[torch.Tensor]:
+        """fp32 ``[heads, 2 S - 1]`` bias by distance for sequences of at most ``S`` tokens (None off MPNet). Positions
+        count 0 .. L-1 inside a sequence (HF uses ``arange`` here, not the padding-aware ids), so padded and packed
+        batches agree."""
+        if self.relative_attention_table is None:
+            return None
+        return bias_by_distance(self.relative_attention_table, S, self.__dict__.setdefault("_rel_cache", {}))
 
     def position_ids(self, input_ids: torch.Tensor) -> torch.Tensor:
         B, S = input_ids.shape
-        if self.cfg.model_type == "roberta":
+        if self.cfg.roberta_ids:
             # HF create_position_ids_from_input_ids: padding_idx + cumsum over non-pad tokens
             pad = self.cfg.pad_token_id
             m = input_ids.ne(pad).int()
@@ -65,7 +77,7 @@ class Embeddings(nn.Module):
         return ops.embed_ln(input_ids, pos, token_type_ids, self.word_embeddings, self.position_embeddings,
                             self.token_type_embeddings, self.ln_weight, self.ln_bias, c.layer_norm_eps,
                             p, rng.next() if p else 0,
-                            pos_is_arange=c.model_type != "roberta" and position_ids is None, q8_for=q8_for)
+                            pos_is_arange=not c.roberta_ids and position_ids is None, q8_for=q8_for)
 
 
 class Encoder(nn.Module):
@@ -84,7 +96,7 @@ class Encoder(nn.Module):
         The last layer then runs everything after its attention scores on those B rows and the result is
         ``[B, 1, H]`` -- where ``ops.attn_block_cls_ok`` takes the tensors (padded batch, even S, reference ops or
         bf16 HIP ops with fp8 off) and ``HSD_CLS_ROWS_ONLY`` is not 0; otherwise, and always without the flag, all
-        hidden states ``[B, S, H]``."""
+        hidden states ``[B, S, H]``. An MPNet encoder never prunes: the first-token-rows block takes no relative bias."""
         if cu_seqlens is not None:
             return self._forward_packed(input_ids, attention_mask, token_type_ids, rng, training, cu_seqlens,
                                         max_seqlen, position_ids)
@@ -93,11 +105,12 @@ class Encoder(nn.Module):
         h = self.embeddings(input_ids, token_type_ids, rng, training, q8_for=first_qkv).view(B * S, -1)
         mask_bias = ops.key_mask_bias(attention_mask) if attention_mask is not None else None
         n = len(self.layers)
-        prune = bool(first_token_only and n and ops.CLS_ROWS_ONLY
+        rel = self.embeddings.relative_bias(S)
+        prune = bool(first_token_only and n and ops.CLS_ROWS_ONLY and rel is None
                      and ops.attn_block_cls_ok(h, self.layers[-1].qkv_weight, B, S, self.cfg.num_attention_heads))
         for i, layer in enumerate(self.layers):
             h = layer(h, mask_bias, B, S, rng, training, self.layers[i + 1].qkv_weight if i + 1 < n else None,
-                      first_token_only=prune and i == n - 1)
+                      first_token_only=prune and i == n - 1, rel_bias=rel)
         return h.view(B, 1 if prune else S, -1)
 
     def _forward_packed(self, input_ids, attention_mask, token_type_ids, rng, training, cu_seqlens, max_seqlen,
@@ -119,8 +132,9 @@ class Encoder(nn.Module):
         tt = token_type_ids.view(-1, cols) if token_type_ids is not None else None
         h = self.embeddings(input_ids.view(-1, cols), tt, rng, training,
                             position_ids=position_ids.view(-1, cols)).view(T, -1)
+        rel = self.embeddings.relative_bias(int(max_seqlen))
         for layer in self.layers:
-            h = layer(h, None, 1, T, rng, training, None, cu_seqlens=cu, max_seqlen=int(max_seqlen))
+            h = layer(h, None, 1, T, rng, training, None, cu_seqlens=cu, max_seqlen=int(max_seqlen), rel_bias=rel)
         return h
 
 
@@ -145,11 +159,11 @@ def _init_(module: nn.Module, cfg: ModelConfig, generator: Optional[torch.Genera
             e = emb.embeddings
             if 0 <= cfg.pad_token_id < e.word_embeddings.shape[0]:
                 e.word_embeddings[cfg.pad_token_id].zero_()
-            if cfg.model_type == "roberta" and cfg.pad_token_id < e.position_embeddings.shape[0]:
+            if cfg.roberta_ids and cfg.pad_token_id < e.position_embeddings.shape[0]:
                 e.position_embeddings[cfg.pad_token_id].zero_()
 
 
-_FAMILY = {"bert": "Bert", "roberta": "Roberta", "distilbert": "DistilBert"}  # HF's class-name prefix per model_type
+_FAMILY = {"bert": "Bert", "roberta": "Roberta", "distilbert": "DistilBert", "mpnet": "MPNet"}  # HF's class-name prefix per model_type
 
 
 class _Base(nn.Module):
@@ -183,12 +197,15 @@ class _Base(nn.Module):
             yield f"{b}.embeddings.token_type_embeddings.weight", "encoder.embeddings.token_type_embeddings", None, 1
         yield f"{b}.embeddings.LayerNorm.weight", "encoder.embeddings.ln_weight", None, 1
         yield f"{b}.embeddings.LayerNorm.bias", "encoder.embeddings.ln_bias", None, 1
+        if self.encoder.embeddings.relative_attention_table is not None:
+            yield f"{b}.encoder.relative_attention_bias.weight", "encoder.embeddings.relative_attention_table", None, 1
 
     def _layer_hf_names(self):
         distil = self.cfg.model_type == "distilbert"
         mid = "transformer" if distil else "encoder"
         for i in range(self.cfg.num_hidden_layers):
-            yield from layer_hf_names(f"{self.base_prefix}.{mid}.layer.{i}.", f"encoder.layers.{i}.", distil)
+            yield from layer_hf_names(f"{self.base_prefix}.{mid}.layer.{i}.", f"encoder.layers.{i}.",
+                                      self.cfg.model_type)
 
     def _head_hf_names(self):
         return iter(())
@@ -234,7 +251,7 @@ class TransformerForSequenceClassification(_Base):
             yield "bert.pooler.dense.bias", "pooler_bias", None, 1
             yield "classifier.weight", "classifier_weight", None, 1
             yield "classifier.bias", "classifier_bias", None, 1
-        elif mt == "roberta":
+        elif mt in ("roberta", "mpnet"):
             yield "classifier.dense.weight", "head_dense_weight", None, 1
             yield "classifier.dense.bias", "head_dense_bias", None, 1
             yield "classifier.out_proj.weight", "classifier_weight", None, 1
@@ -259,7 +276,7 @@ class TransformerForSequenceClassification(_Base):
         if c.model_type == "bert":
             p = (c.classifier_dropout if c.classifier_dropout is not None else c.hidden_dropout_prob) if training else 0.0
             w1, b1, act, p_in, seed_in = self.pooler_weight, self.pooler_bias, "tanh", 0.0, 0
-        elif c.model_type == "roberta":
+        elif c.model_type in ("roberta", "mpnet"):
             p = (c.classifier_dropout if c.classifier_dropout is not None else c.hidden_dropout_prob) if training else 0.0
             w1, b1, act, p_in = self.head_dense_weight, self.head_dense_bias, "tanh", p
             seed_in = self.rng.next() if p else 0
@@ -522,7 +539,7 @@ def build_model(cfg: ModelConfig, task: str = "sequence-classification", seed: O
         m = TransformerForSequenceClassification(cfg)
     elif task in ("masked-lm", "mlm"):
         if cfg.model_type != "roberta":
-            raise ValueError("masked-lm is provided for roberta configs")
+            raise ValueError(f"masked-lm is provided for roberta configs, not {cfg.model_type}")
         m = RobertaForMaskedLM(cfg)
     elif task in ("token-classification", "token-cls"):
         m = TransformerForTokenClassification(cfg)

@@ -27,7 +27,7 @@ def check_problem_type(problem_type: Optional[str]) -> Optional[str]:
 
 @dataclass
 class ModelConfig:
-    model_type: str = "bert"  # bert | roberta | distilbert
+    model_type: str = "bert"  # bert | roberta | distilbert | mpnet
     vocab_size: int = 30522
     hidden_size: int = 768
     num_hidden_layers: int = 12
@@ -54,6 +54,8 @@ class ModelConfig:
     sinusoidal_pos_embds: bool = False
     seq_classif_dropout: float = 0.2
     qa_dropout: float = 0.1
+    # mpnet-only: rows of the relative-position bias table [buckets, heads] shared by all layers
+    relative_attention_num_buckets: int = 32
     # bookkeeping
     name_or_path: str = ""
     model_max_length: int = 512
@@ -63,6 +65,12 @@ class ModelConfig:
     @property
     def head_dim(self) -> int:
         return self.hidden_size // self.num_attention_heads
+
+    @property
+    def roberta_ids(self) -> bool:
+        """RoBERTa's id conventions (MPNet shares them): <s> / </s> around a text, positions from ``pad_token_id + 1``
+        over the non-padding tokens."""
+        return self.model_type in ("roberta", "mpnet")
 
     def replace(self, **kw) -> "ModelConfig":
         return dataclasses.replace(copy.deepcopy(self), **kw)
@@ -94,6 +102,17 @@ class ModelConfig:
                 "sinusoidal_pos_embds": self.sinusoidal_pos_embds,
                 "seq_classif_dropout": self.seq_classif_dropout,
                 "qa_dropout": self.qa_dropout, "tie_weights_": True,
+            })
+        elif mt == "mpnet":
+            common.update({
+                "hidden_size": self.hidden_size, "num_hidden_layers": self.num_hidden_layers,
+                "num_attention_heads": self.num_attention_heads,
+                "intermediate_size": self.intermediate_size, "hidden_act": self.hidden_act,
+                "hidden_dropout_prob": self.hidden_dropout_prob,
+                "attention_probs_dropout_prob": self.attention_probs_dropout_prob,
+                "max_position_embeddings": self.max_position_embeddings, "layer_norm_eps": self.layer_norm_eps,
+                "relative_attention_num_buckets": self.relative_attention_num_buckets,
+                "bos_token_id": self.bos_token_id, "eos_token_id": self.eos_token_id,
             })
         else:
             common.update({
@@ -132,6 +151,20 @@ class ModelConfig:
                 seq_classif_dropout=d.get("seq_classif_dropout", 0.2), qa_dropout=d.get("qa_dropout", 0.1),
                 id2label=labels, problem_type=check_problem_type(d.get("problem_type")),
             )
+        if mt == "mpnet":  # [dep: transformers/models/mpnet/configuration_mpnet.py] defaults
+            return cls(
+                model_type="mpnet", vocab_size=d.get("vocab_size", 30527), hidden_size=d.get("hidden_size", 768),
+                num_hidden_layers=d.get("num_hidden_layers", 12), num_attention_heads=d.get("num_attention_heads", 12),
+                intermediate_size=d.get("intermediate_size", 3072), hidden_act=d.get("hidden_act", "gelu"),
+                hidden_dropout_prob=d.get("hidden_dropout_prob", 0.1),
+                attention_probs_dropout_prob=d.get("attention_probs_dropout_prob", 0.1),
+                max_position_embeddings=d.get("max_position_embeddings", 512), type_vocab_size=0,
+                initializer_range=d.get("initializer_range", 0.02), layer_norm_eps=d.get("layer_norm_eps", 1e-12),
+                pad_token_id=d.get("pad_token_id", 1), bos_token_id=d.get("bos_token_id", 0),
+                eos_token_id=d.get("eos_token_id", 2),
+                relative_attention_num_buckets=d.get("relative_attention_num_buckets", 32),
+                num_labels=nl, id2label=labels, problem_type=check_problem_type(d.get("problem_type")),
+            )
         return cls(
             model_type=mt, vocab_size=d.get("vocab_size", 30522), hidden_size=d.get("hidden_size", 768),
             num_hidden_layers=d.get("num_hidden_layers", 12),
@@ -156,7 +189,12 @@ _ROBERTA_BASE = ModelConfig(model_type="roberta", vocab_size=50265, max_position
 _ROBERTA_LARGE = _ROBERTA_BASE.replace(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16,
                                        intermediate_size=4096)
 
+_MPNET_BASE = ModelConfig(model_type="mpnet", vocab_size=30527, max_position_embeddings=514, type_vocab_size=0,
+                          layer_norm_eps=1e-5, pad_token_id=1, bos_token_id=0, eos_token_id=2)
+
 REGISTRY: Dict[str, ModelConfig] = {
+    "mpnet-base": _MPNET_BASE,
+    "all-mpnet-base-v2": _MPNET_BASE,
     "bert-base-uncased": _BERT_BASE,
     "bert-base-cased": _BERT_BASE.replace(vocab_size=28996),
     "bert-large-uncased": _BERT_LARGE,
@@ -175,6 +213,10 @@ REGISTRY: Dict[str, ModelConfig] = {
                                     num_attention_heads=4, intermediate_size=128, max_position_embeddings=130,
                                     type_vocab_size=1, layer_norm_eps=1e-5, pad_token_id=1, bos_token_id=0,
                                     eos_token_id=2),
+    "hsd-tiny-mpnet": ModelConfig(model_type="mpnet", vocab_size=1024, hidden_size=64, num_hidden_layers=2,
+                                  num_attention_heads=4, intermediate_size=128, max_position_embeddings=130,
+                                  type_vocab_size=0, layer_norm_eps=1e-5, pad_token_id=1, bos_token_id=0,
+                                  eos_token_id=2),
 }
 for _k in ("distilbert-base-uncased-finetuned-sst-2-english",):
     REGISTRY[_k] = _DISTILBERT

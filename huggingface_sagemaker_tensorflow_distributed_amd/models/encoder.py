@@ -13,6 +13,7 @@ HF key names are produced by :mod:`..models.hf_io` from :meth:`hf_names`.
 """
 from __future__ import annotations
 
+import math
 from typing import Iterator, Optional, Tuple
 
 import torch
@@ -49,12 +50,13 @@ class EncoderLayer(nn.Module):
     def forward(self, h: torch.Tensor, mask_bias: Optional[torch.Tensor], batch: int, seq: int,
                 rng: DropoutSeeds, training: bool, next_qkv: Optional[torch.Tensor] = None, *,
                 cu_seqlens: Optional[torch.Tensor] = None, max_seqlen: int = 0,
-                first_token_only: bool = False) -> torch.Tensor:
+                first_token_only: bool = False, rel_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``next_qkv``: the next layer's QKV weight (fp8 path: this layer's last LayerNorm quantises for it).
         ``cu_seqlens`` / ``max_seqlen``: ``h`` is a packed ``[T, H]`` buffer (data/packing.py).
         ``first_token_only`` (padded batches, the last layer of a classification model): K and V at every position,
         everything after the attention scores on the first-token row of each sequence -> ``[B, H]``; the dropout seeds
-        are drawn in the same order and the first-token rows see the same masks."""
+        are drawn in the same order and the first-token rows see the same masks.
+        ``rel_bias`` (``[heads, R]``, the MPNet family): the bias by distance on the attention scores."""
         c = self.cfg
         p_h = c.hidden_dropout_prob if training else 0.0
         p_a = c.attention_probs_dropout_prob if training else 0.0
@@ -70,7 +72,7 @@ class EncoderLayer(nn.Module):
         h1 = ops.attn_block(h, self.qkv_weight, self.qkv_bias, self.attn_out_weight, self.attn_out_bias,
                             self.ln1_weight, self.ln1_bias, c.layer_norm_eps, mask_bias, batch, seq,
                             c.num_attention_heads, p_a, seed_a, p_h, seed_h1, q8_next=self.ffn1_weight,
-                            cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)
+                            cu_seqlens=cu_seqlens, max_seqlen=max_seqlen, rel_bias=rel_bias)
         seed_h2 = rng.next() if p_h else 0
         return ops.ffn_block(h1, self.ffn1_weight, self.ffn1_bias, self.ffn2_weight, self.ffn2_bias,
                              self.ln2_weight, self.ln2_bias, c.layer_norm_eps, p_h, seed_h2, q8_next=next_qkv)
@@ -107,9 +109,71 @@ _DISTIL_LAYER_NAMES = {
 }
 
 
-def layer_hf_names(layer_prefix: str, internal_prefix: str, distil: bool) -> Iterator[Tuple[str, str, Optional[int], int]]:
-    """Yield ``(hf_key, internal_key, split_index, n_splits)``."""
-    table = _DISTIL_LAYER_NAMES if distil else _BERT_LAYER_NAMES
+# MPNet: BERT's layer with its own names for the attention projections ([dep: transformers/models/mpnet/modeling_mpnet.py])
+_MPNET_LAYER_NAMES = dict(_BERT_LAYER_NAMES, **{
+    "qkv_weight": ("attention.attn.{}.weight", ("q", "k", "v")),
+    "qkv_bias": ("attention.attn.{}.bias", ("q", "k", "v")),
+    "attn_out_weight": ("attention.attn.o.weight", None),
+    "attn_out_bias": ("attention.attn.o.bias", None),
+    "ln1_weight": ("attention.LayerNorm.weight", None),
+    "ln1_bias": ("attention.LayerNorm.bias", None),
+})
+_LAYER_NAMES = {"distilbert": _DISTIL_LAYER_NAMES, "mpnet": _MPNET_LAYER_NAMES}
+
+
+def relative_position_bucket(delta: torch.Tensor, num_buckets: int = 32, max_distance: int = 128) -> torch.Tensor:
+    """HF ``MPNetEncoder.relative_position_bucket`` of ``delta = key position - query position`` (int64, any shape):
+    half of the buckets per sign, the first half of those one distance each, the rest log-spaced up to
+    ``max_distance`` and the last one everything beyond."""
+    n = -delta
+    half = num_buckets // 2
+    ret = (n < 0).to(torch.long) * half
+    n = n.abs()
+    exact = half // 2
+    large = exact + (torch.log(n.float() / exact) / math.log(max_distance / exact) * (half - exact)).to(torch.long)
+    large = torch.min(large, torch.full_like(large, half - 1))
+    return ret + torch.where(n < exact, n, large)
+
+
+class _BiasByDistance(torch.autograd.Function):
+    """``rel[h][x] = table[idx[x]][h]``: the ``[buckets, heads]`` table gathered into a bias by distance ``[heads, R]``.
+    The backward sums, per bucket, the columns that read it through ``seg`` (``[buckets, longest segment]`` column
+    indices, padded with ``R``: a zero column) with one gather and one reduction, so the table's gradient has the
+    same bits from run to run (an index_add would take fp32 atomics)."""
+
+    @staticmethod
+    def forward(ctx, table, idx, seg):
+        ctx.save_for_backward(seg)
+        return table.float().t().index_select(1, idx).contiguous()
+
+    @staticmethod
+    def backward(ctx, drel):
+        (seg,) = ctx.saved_tensors
+        padded = torch.cat([drel.float(), drel.new_zeros((drel.shape[0], 1), dtype=torch.float32)], dim=1)
+        return padded[:, seg].sum(dim=-1).t().contiguous(), None, None
+
+
+def bias_by_distance(table: torch.Tensor, S: int, cache: dict) -> torch.Tensor:
+    """The MPNet attention bias of sequences of at most ``S`` tokens: fp32 ``[heads, 2 S - 1]``, column ``d + S - 1``
+    the bias of ``key - query = d``. The index vectors are built on the host once per ``(S, device)`` and cached."""
+    key = (int(S), table.device)
+    hit = cache.get(key)
+    if hit is None:
+        if len(cache) > 16:
+            cache.clear()
+        nb = table.shape[0]
+        idx = relative_position_bucket(torch.arange(-(S - 1), S), nb)
+        cols = [(idx == b).nonzero().flatten() for b in range(nb)]
+        seg = torch.full((nb, max(1, max(c.numel() for c in cols))), 2 * S - 1, dtype=torch.long)
+        for b, c in enumerate(cols):
+            seg[b, :c.numel()] = c
+        hit = cache[key] = (idx.to(table.device), seg.to(table.device))
+    return _BiasByDistance.apply(table, *hit)
+
+
+def layer_hf_names(layer_prefix: str, internal_prefix: str, family: str) -> Iterator[Tuple[str, str, Optional[int], int]]:
+    """Yield ``(hf_key, internal_key, split_index, n_splits)``. ``family``: the config's ``model_type``."""
+    table = _LAYER_NAMES.get(family, _BERT_LAYER_NAMES)
     for iname, (fmt, parts) in table.items():
         if parts is None:
             yield layer_prefix + fmt, internal_prefix + iname, None, 1

@@ -158,15 +158,25 @@ def attn_block_cls(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, ba
 
 
 def attn_block(h, qkv_w, qkv_b, out_w, out_b, ln_w, ln_b, eps, mask_bias, batch, seq, heads, p_attn, seed_attn,
-               p_hidden, seed_hidden, q8_next=None, *, cu_seqlens=None, max_seqlen=0):
+               p_hidden, seed_hidden, q8_next=None, *, cu_seqlens=None, max_seqlen=0, rel_bias=None):
     """Self-attention sub-block: ``LN(dropout(attn(h Wqkvᵀ + b) Woᵀ + bo) + h)``. ``q8_next``: the weight of the
     GEMM that consumes the output (HIP fp8 path: the LayerNorm writes its fp8 input copy).
 
     ``cu_seqlens`` (with ``max_seqlen``): ``h`` is a packed ``[T, H]`` buffer (data/packing.py) and the block is the
-    three-op composition below around ``attention_varlen``; ``mask_bias`` / ``batch`` / ``seq`` are not read."""
+    three-op composition below around ``attention_varlen``; ``mask_bias`` / ``batch`` / ``seq`` are not read.
+
+    ``rel_bias`` (``[heads, R]``, the MPNet family): a bias by distance on the scores; the block is then the three-op
+    composition around :func:`attention_relbias` / :func:`attention_relbias_varlen`, padded or packed."""
+    if cu_seqlens is not None and mask_bias is not None:
+        raise ValueError("attn_block: a packed batch (cu_seqlens) takes no attention mask")
+    if rel_bias is not None:
+        qkv = linear(h, qkv_w, qkv_b)
+        if cu_seqlens is not None:
+            ctx = attention_relbias_varlen(qkv, rel_bias, cu_seqlens, max_seqlen, heads, p_attn, seed_attn)
+        else:
+            ctx = attention_relbias(qkv, rel_bias, mask_bias, batch, seq, heads, p_attn, seed_attn)
+        return dense_residual_ln(ctx, out_w, out_b, h, ln_w, ln_b, eps, p_hidden, seed_hidden)
     if cu_seqlens is not None:
-        if mask_bias is not None:
-            raise ValueError("attn_block: a packed batch (cu_seqlens) takes no attention mask")
         qkv = linear(h, qkv_w, qkv_b)
         ctx = attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p_attn, seed_attn)
         return dense_residual_ln(ctx, out_w, out_b, h, ln_w, ln_b, eps, p_hidden, seed_hidden)
@@ -209,6 +219,23 @@ def attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed):
     if _hip32(qkv) and _hip32mod().attention_varlen_ok(qkv, heads):
         return _hip32mod().attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed)
     return _ref.attention_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed, p > 0)
+
+
+def attention_relbias(qkv, rel, mask_bias, batch, seq, heads, p, seed):
+    """:func:`attention` with a relative-position bias ``rel [heads, R]`` on the scores (definition:
+    ``reference.attention_relbias``). bf16 GPU tensors with head dim 64, an even ``seq`` <= 1,024 and ``R >= 2 seq - 1``
+    run the kernels of csrc/kernels/attention_relbias.hip; everything else (CPU, fp32 GPU tensors, ``HSD_OPS=torch``,
+    other head dims, odd ``seq``) the reference op."""
+    if _hip(qkv) and _hipmod().attention_relbias_ok(qkv, rel, seq, heads):
+        return _hipmod().attention_relbias(qkv, rel, mask_bias, batch, seq, heads, p, seed)
+    return _ref.attention_relbias(qkv, rel, mask_bias, batch, seq, heads, p, seed, p > 0)
+
+
+def attention_relbias_varlen(qkv, rel, cu_seqlens, max_seqlen, heads, p, seed):
+    """:func:`attention_relbias` over packed sequences; dispatch as above (any lengths)."""
+    if _hip(qkv) and _hipmod().attention_relbias_ok(qkv, rel, int(max_seqlen), heads, padded=False):
+        return _hipmod().attention_relbias_varlen(qkv, rel, cu_seqlens, max_seqlen, heads, p, seed)
+    return _ref.attention_relbias_varlen(qkv, rel, cu_seqlens, max_seqlen, heads, p, seed, p > 0)
 
 
 def hip_active(device) -> bool:

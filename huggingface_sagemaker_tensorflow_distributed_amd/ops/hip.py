@@ -693,6 +693,67 @@ def attention_d32_varlen(qkv, cu_seqlens, max_seqlen, heads, p, seed):
                                seed)
 
 
+# ---- relative-position-bias attention, head dim 64 (csrc/kernels/attention_relbias.hip): the MPNet family
+def attention_relbias_ok(qkv, rel, seq, heads, padded=True) -> bool:
+    """What :func:`attention_relbias` (``padded``) / :func:`attention_relbias_varlen` take: bf16 ``qkv`` of head dim 64,
+    ``rel`` fp32-convertible ``[heads, R]`` with an odd ``R >= 2 * seq - 1``, ``seq`` (the padded or the longest
+    length) at most 1,024, and even when padded."""
+    return (qkv.dtype == torch.bfloat16 and qkv.shape[-1] == 3 * heads * 64 and rel.dim() == 2
+            and rel.shape[0] == heads and seq > 0 and not (padded and seq % 2)
+            and bool(_C.attn_relbias_supported(64, int(seq), int(rel.shape[1]))))
+
+
+class _AttentionRelBias(torch.autograd.Function):
+    """Attention with a bias by distance on the scores, padded (``cu_seqlens`` None, ``S`` = the sequence length,
+    optional key bias) or packed (``S`` = max_seqlen). The backward returns ``(dqkv, drel)``."""
+
+    @staticmethod
+    def forward(ctx, qkv, rel, cu_seqlens, mask_bias, B, S, heads, p, seed):
+        qkv = qkv.contiguous()
+        T, H = qkv.shape[0], qkv.shape[-1] // 3
+        relf = rel.detach().contiguous().float()
+        out = torch.empty((T, H), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty(heads * T, dtype=torch.float32, device=qkv.device)
+        mb = mask_bias.contiguous().float() if mask_bias is not None else None
+        _C.attn_relbias_fwd(qkv, cu_seqlens, mb, relf, out, lse, B, S, heads, float(p), _s64(seed))
+        ctx.save_for_backward(qkv, relf, out, lse, mb, cu_seqlens)
+        ctx.B, ctx.S, ctx.heads, ctx.p, ctx.seed, ctx.rel_dtype = B, S, heads, float(p), seed, rel.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, relf, out, lse, mb, cu = ctx.saved_tensors
+        dqkv = torch.empty_like(qkv)
+        drel = torch.empty_like(relf)
+        # one partial row [R] per workgroup of the dK / dV kernel, summed in a fixed order by the reducer
+        slab = _workspace(_C.attn_relbias_slab_numel(ctx.B, ctx.S, ctx.heads, relf.shape[1]), qkv.device)
+        _C.attn_relbias_bwd(qkv, cu, mb, relf, out, dout.contiguous(), lse, dqkv, drel, slab, ctx.B, ctx.S, ctx.heads,
+                            ctx.p, _s64(ctx.seed))
+        return dqkv, drel.to(ctx.rel_dtype), None, None, None, None, None, None, None
+
+
+def attention_relbias(qkv, rel, mask_bias, batch, seq, heads, p, seed):
+    """:func:`attention` with ``rel[h][j - i + (R-1)/2]`` added to the score of query ``i`` and key ``j``: ``qkv
+    [B*S, 3H]`` bf16, ``rel [heads, R]``, optional additive fp32 key bias ``[B, S]``. An unsupported shape
+    (:func:`attention_relbias_ok`) is an error, not a fall-back."""
+    if not attention_relbias_ok(qkv, rel, seq, heads):
+        raise ValueError(f"attention_relbias: qkv {tuple(qkv.shape)} {qkv.dtype}, rel {tuple(rel.shape)}, S = {seq}: "
+                         f"bf16, head dim 64, an even S <= 1024 and rel [{heads}, odd R >= 2 S - 1] only")
+    return _AttentionRelBias.apply(qkv.reshape(batch * seq, -1), rel, None, mask_bias, batch, seq, heads, p, seed)
+
+
+def attention_relbias_varlen(qkv, rel, cu_seqlens, max_seqlen, heads, p, seed):
+    """:func:`attention_varlen` with the bias of :func:`attention_relbias`; distances count inside each sequence."""
+    if qkv.dim() != 2 or not attention_relbias_ok(qkv, rel, int(max_seqlen), heads, padded=False):
+        raise ValueError(f"attention_relbias_varlen: qkv {tuple(qkv.shape)} {qkv.dtype}, rel {tuple(rel.shape)}, "
+                         f"max_seqlen = {max_seqlen}: bf16 [T, 3 * {heads} * 64], max_seqlen <= 1024 and rel "
+                         f"[{heads}, odd R >= 2 max_seqlen - 1] only")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.device != qkv.device:
+        raise ValueError("attention_relbias_varlen: cu_seqlens must be an int32 tensor on qkv's device")
+    return _AttentionRelBias.apply(qkv, rel, cu_seqlens.contiguous(), None, cu_seqlens.numel() - 1, int(max_seqlen),
+                                   heads, p, seed)
+
+
 # ------------------------------------------------------------------------------------------ GEMM helpers
 EPI_STORE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_RES, EPI_DGELU, EPI_F32_ATOMIC = range(7)
 EPI_F32_SLAB, EPI_BIAS_GELU_D, EPI_MUL, EPI_STORE_RDOT = 7, 8, 9, 10  # gemm2 only

@@ -136,6 +136,67 @@ def attention_varlen(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: in
     return torch.cat(outs, dim=0)
 
 
+def _rel_of_length(rel: torch.Tensor, L: int, dtype) -> torch.Tensor:
+    """``rel [heads, R]`` (a bias by distance, ``R`` odd) -> ``[heads, L, L]`` with ``[h, i, j] = rel[h, j - i + (R-1)/2]``."""
+    R = rel.shape[1]
+    if R % 2 == 0 or R < 2 * L - 1:
+        raise ValueError(f"rel {tuple(rel.shape)}: an odd R >= 2 * {L} - 1")
+    ar = torch.arange(L, device=rel.device)
+    return rel.to(dtype)[:, ar.view(1, L) - ar.view(L, 1) + (R - 1) // 2]
+
+
+def _compute_dtype(qkv: torch.Tensor, compute_dtype):
+    if compute_dtype is not None:
+        return compute_dtype
+    return torch.float64 if qkv.dtype == torch.float64 else torch.float32
+
+
+def attention_relbias(qkv: torch.Tensor, rel: torch.Tensor, mask_bias: Optional[torch.Tensor], batch: int, seq: int,
+                      heads: int, p: float, seed: int, training: bool, compute_dtype=None) -> torch.Tensor:
+    """:func:`attention` with a relative-position bias on the scores (MPNet): ``s[i][j] = q_i.k_j/sqrt(d) +
+    rel[h][j - i + (R-1)/2] + mask_bias[j]``, ``rel [heads, R]`` with ``R`` odd and ``R >= 2*seq - 1``. The dropout site
+    is :func:`attention`'s. Computes in fp32 (fp64 for fp64 ``qkv``) unless ``compute_dtype`` says otherwise."""
+    H = qkv.shape[-1] // 3
+    d = H // heads
+    ct = _compute_dtype(qkv, compute_dtype)
+    x = qkv.view(batch, seq, 3, heads, d).permute(2, 0, 3, 1, 4).to(ct)  # [3,B,h,S,d]
+    s = torch.matmul(x[0], x[1].transpose(-1, -2)) * (1.0 / math.sqrt(d)) + _rel_of_length(rel, seq, ct).unsqueeze(0)
+    if mask_bias is not None:
+        s = s + mask_bias.view(batch, 1, 1, seq).to(ct)
+    pr = dropout(torch.softmax(s, dim=-1), p, seed, training)
+    o = torch.matmul(pr, x[2])  # [B,h,S,d]
+    return o.permute(0, 2, 1, 3).reshape(batch * seq, H).to(qkv.dtype)
+
+
+def attention_relbias_varlen(qkv: torch.Tensor, rel: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int,
+                             heads: int, p: float, seed: int, training: bool, compute_dtype=None) -> torch.Tensor:
+    """:func:`attention_varlen` with the bias of :func:`attention_relbias`; ``i`` and ``j`` count inside the sequence,
+    ``R >= 2*max_seqlen - 1``. The dropout site is :func:`attention_varlen`'s."""
+    T, H3 = qkv.shape
+    H = H3 // 3
+    d = H // heads
+    ct = _compute_dtype(qkv, compute_dtype)
+    cu = [int(c) for c in cu_seqlens.tolist()]
+    keep = None
+    if training and p > 0.0:
+        keep = keep_mask(seed, (heads * T, int(max_seqlen)), p, device=qkv.device).view(heads, T, int(max_seqlen))
+    full = _rel_of_length(rel, int(max_seqlen), ct)
+    outs = []
+    for b in range(len(cu) - 1):
+        s0, s1 = cu[b], cu[b + 1]
+        L = s1 - s0
+        x = qkv[s0:s1].view(1, L, 3, heads, d).permute(2, 0, 3, 1, 4).to(ct)  # [3,1,h,L,d]
+        s = torch.matmul(x[0], x[1].transpose(-1, -2)) * (1.0 / math.sqrt(d)) + full[:, :L, :L].unsqueeze(0)
+        pr = torch.softmax(s, dim=-1)
+        if keep is not None:
+            pr = pr * keep[:, s0:s1, :L].unsqueeze(0).to(pr.dtype) * (1.0 / (1.0 - p))
+        o = torch.matmul(pr, x[2])  # [1,h,L,d]
+        outs.append(o.permute(0, 2, 1, 3).reshape(L, H).to(qkv.dtype))
+    if cu[-1] < T:
+        outs.append(qkv.new_zeros((T - cu[-1], H)))
+    return torch.cat(outs, dim=0)
+
+
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0) -> torch.Tensor:
     """SparseCategoricalCrossentropy(from_logits=True), SUM_OVER_BATCH_SIZE (``scripts/train.py:118``).
 

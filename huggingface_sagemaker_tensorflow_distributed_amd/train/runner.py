@@ -76,7 +76,7 @@ def _datasets(args, cfg, tokenizer, max_len: int):
     if getattr(args, "task", "sequence-classification") == "token-classification":
         if args.dataset == "synthetic":
             kw = {"num_labels": cfg.num_labels, "pad_id": cfg.pad_token_id}
-            if cfg.model_type == "roberta":
+            if cfg.roberta_ids:
                 kw.update(cls_id=cfg.bos_token_id if cfg.bos_token_id is not None else 0,
                           sep_id=cfg.eos_token_id if cfg.eos_token_id is not None else 2)
             tr = hdata.synthetic_token_classification(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed, **kw)
@@ -99,7 +99,7 @@ def _datasets(args, cfg, tokenizer, max_len: int):
         segs = cfg.model_type == "bert"  # segment ids 0 / 1 for BERT; RoBERTa and DistilBERT take none
         if args.dataset == "synthetic":
             kw = {"segment_ids": segs, "pad_id": cfg.pad_token_id}
-            if cfg.model_type == "roberta":
+            if cfg.roberta_ids:
                 kw.update(cls_id=cfg.bos_token_id if cfg.bos_token_id is not None else 0,
                           sep_id=cfg.eos_token_id if cfg.eos_token_id is not None else 2)
             tr = hdata.synthetic_question_answering(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed, **kw)
@@ -130,7 +130,7 @@ def _datasets(args, cfg, tokenizer, max_len: int):
         if args.dataset == "synthetic":
             make = hdata.synthetic_regression if ptype == "regression" else hdata.synthetic_multi_label
             kw = {"num_labels": cfg.num_labels, "pad_id": cfg.pad_token_id}
-            if cfg.model_type == "roberta":
+            if cfg.roberta_ids:
                 kw.update(cls_id=cfg.bos_token_id if cfg.bos_token_id is not None else 0,
                           sep_id=cfg.eos_token_id if cfg.eos_token_id is not None else 2)
             return (make(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed, **kw),
@@ -346,6 +346,9 @@ def build(args, mode: str):
         args.num_labels = len(tags)
     model = from_pretrained(args.model_name_or_path or "bert-base-uncased", task=task, num_labels=args.num_labels,
                             seed=args.seed, problem_type=ptype)
+    if model.cfg.model_type == "mpnet" and dtype_name == "fp8":
+        raise ValueError("--dtype fp8 is not supported for mpnet models (the relative-position-bias attention kernels "
+                         "are bf16; --dtype bf16 or fp32)")
     if task == "sequence-classification":
         tol = float(getattr(args, "regression_tolerance", 0.5))
         if not tol >= 0.0:
