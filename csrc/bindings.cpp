@@ -1746,6 +1746,105 @@ void span_ce(torch::Tensor logits, torch::Tensor cu, c10::optional<torch::Tensor
                       (int)B, cur_stream());
 }
 
+// ---- sentence-embedding head (sent_head.hip). h [R][H] bf16, cu int32 [n+1], mask int64 [R] or none; e fp32 [n][H],
+// aux fp32 [n][2]; ws fp32 / wsc int32 workspaces of n · chunks · H / n · chunks elements, chunks =
+// sent_pool_chunks(max_seqlen)
+static const int* sent_cu(const torch::Tensor& cu, int64_t* n) {
+  TORCH_CHECK(cu.is_cuda() && cu.is_contiguous() && cu.scalar_type() == torch::kInt32 && cu.numel() >= 2,
+              "sent_head cu int32 [n+1]");
+  *n = cu.numel() - 1;
+  TORCH_CHECK(*n < 65535, "sent_head: fewer than 65,535 sequences");
+  return cu.data_ptr<int>();
+}
+static const int64_t* sent_mask(const c10::optional<torch::Tensor>& mask, int64_t R) {
+  if (!mask.has_value()) return nullptr;
+  TORCH_CHECK(mask->is_cuda() && mask->is_contiguous() && mask->scalar_type() == torch::kInt64 && mask->numel() == R,
+              "sent_head mask int64 [R]");
+  return mask->data_ptr<int64_t>();
+}
+static void sent_check_e(const torch::Tensor& e, int64_t n, int64_t H, const char* what) {
+  check_f32(e, what);
+  TORCH_CHECK(e.dim() == 2 && e.size(0) == n && e.size(1) == H && H % 8 == 0 && H >= 8 && H <= 1024, what,
+              ": fp32 [n][H], H % 8 == 0, H <= 1024");
+}
+
+void sent_pool_fwd(torch::Tensor h, torch::Tensor cu, c10::optional<torch::Tensor> mask, torch::Tensor e,
+                   torch::Tensor aux, torch::Tensor ws, torch::Tensor wsc, int64_t max_seqlen) {
+  TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() && h.scalar_type() == torch::kBFloat16,
+              "sent_pool h [R][H] bf16");
+  const int64_t R = h.size(0), H = h.size(1);
+  TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 256, "sent_pool: 1 <= rows < 2^31");
+  int64_t n;
+  const int* cup = sent_cu(cu, &n);
+  const int64_t* mp = sent_mask(mask, R);
+  sent_check_e(e, n, H, "sent_pool e");
+  check_f32(aux, "aux");
+  const int64_t ch = hsd::sent_pool_chunks((int)std::min<int64_t>(std::max<int64_t>(max_seqlen, 1), R));
+  TORCH_CHECK(aux.numel() == 2 * n, "sent_pool aux fp32 [n][2]");
+  float* wsp = nullptr;
+  int* wscp = nullptr;
+  if (ch > 1) {
+    check_f32(ws, "ws");
+    TORCH_CHECK(wsc.is_cuda() && wsc.is_contiguous() && wsc.scalar_type() == torch::kInt32 && wsc.numel() >= n * ch &&
+                ws.numel() >= n * ch * H, "sent_pool workspaces");
+    wsp = ws.data_ptr<float>();
+    wscp = wsc.data_ptr<int>();
+  }
+  hsd::launch_sent_pool_fwd(CBF(h), cup, mp, e.data_ptr<float>(), aux.data_ptr<float>(), wsp, wscp, (int)R, (int)H,
+                            (int)n, (int)ch, cur_stream());
+}
+
+void sent_pool_bwd(torch::Tensor de, torch::Tensor e, torch::Tensor aux, torch::Tensor cu,
+                   c10::optional<torch::Tensor> mask, torch::Tensor dh, int64_t max_seqlen) {
+  TORCH_CHECK(dh.is_cuda() && dh.dim() == 2 && dh.is_contiguous() && dh.scalar_type() == torch::kBFloat16,
+              "sent_pool dh [R][H] bf16");
+  const int64_t R = dh.size(0), H = dh.size(1);
+  TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 256, "sent_pool: 1 <= rows < 2^31");
+  int64_t n;
+  const int* cup = sent_cu(cu, &n);
+  const int64_t* mp = sent_mask(mask, R);
+  sent_check_e(e, n, H, "sent_pool e");
+  sent_check_e(de, n, H, "sent_pool de");
+  check_f32(aux, "aux");
+  TORCH_CHECK(aux.numel() == 2 * n, "sent_pool aux fp32 [n][2]");
+  const int64_t ch = hsd::sent_pool_chunks((int)std::min<int64_t>(std::max<int64_t>(max_seqlen, 1), R));
+  hsd::launch_sent_pool_bwd(de.data_ptr<float>(), e.data_ptr<float>(), aux.data_ptr<float>(), cup, mp, BF(dh), (int)R,
+                            (int)H, (int)n, (int)ch, cur_stream());
+}
+
+static const int* sent_valid(const torch::Tensor& valid, const torch::Tensor& e, int64_t* B) {
+  TORCH_CHECK(valid.is_cuda() && valid.is_contiguous() && valid.scalar_type() == torch::kInt32 && valid.numel() >= 1 &&
+              valid.numel() < ((int64_t)1 << 20), "sent_score valid int32 [B]");
+  *B = valid.numel();
+  sent_check_e(e, 2 * *B, e.dim() == 2 ? e.size(1) : 0, "sent_score e");
+  return valid.data_ptr<int>();
+}
+
+void sent_score_fwd(torch::Tensor e, torch::Tensor valid, double scale, torch::Tensor lse2, torch::Tensor rec,
+                    torch::Tensor stats) {
+  int64_t B;
+  const int* vp = sent_valid(valid, e, &B);
+  check_f32(lse2, "lse2");
+  check_f32(rec, "rec");
+  check_f32(stats, "stats");
+  TORCH_CHECK(lse2.numel() == 2 * B && rec.numel() == 2 * B && stats.numel() >= 4, "sent_score lse2 / rec / stats");
+  hsd::launch_sent_score_fwd(e.data_ptr<float>(), vp, (float)scale, lse2.data_ptr<float>(), rec.data_ptr<float>(),
+                             stats.data_ptr<float>(), (int)B, (int)e.size(1), cur_stream());
+}
+
+void sent_score_bwd(torch::Tensor e, torch::Tensor valid, double scale, torch::Tensor lse2, torch::Tensor stats,
+                    torch::Tensor dloss, torch::Tensor de) {
+  int64_t B;
+  const int* vp = sent_valid(valid, e, &B);
+  check_f32(lse2, "lse2");
+  check_f32(stats, "stats");
+  check_f32(dloss, "dloss");
+  sent_check_e(de, 2 * B, e.size(1), "sent_score de");
+  TORCH_CHECK(lse2.numel() == 2 * B && stats.numel() >= 4 && dloss.numel() == 1, "sent_score lse2 / stats / dloss");
+  hsd::launch_sent_score_bwd(e.data_ptr<float>(), vp, (float)scale, lse2.data_ptr<float>(), stats.data_ptr<float>(),
+                             dloss.data_ptr<float>(), de.data_ptr<float>(), (int)B, (int)e.size(1), cur_stream());
+}
+
 int64_t token_head_fwd_blocks(int64_t R) { return hsd::token_head_fwd_blocks((int)R); }
 int64_t token_head_bwd_blocks(int64_t R) { return hsd::token_head_bwd_blocks((int)R); }
 
@@ -2010,6 +2109,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed"), py::arg("label_smoothing") = 0.0);
   m.def("token_head_bwd_given", &token_head_bwd_given);
   m.def("span_ce", &span_ce);
+  m.def("sent_pool_fwd", &sent_pool_fwd);
+  m.def("sent_pool_bwd", &sent_pool_bwd);
+  m.def("sent_pool_chunks", [](int64_t max_seqlen) { return (int64_t)hsd::sent_pool_chunks((int)max_seqlen); });
+  m.def("sent_score_fwd", &sent_score_fwd);
+  m.def("sent_score_bwd", &sent_score_bwd);
   m.def("token_head_wide_fwd", &token_head_wide_fwd, py::arg("h"), py::arg("W"), py::arg("b"), py::arg("labels"),
         py::arg("logits"), py::arg("partials"), py::arg("stats"), py::arg("p"), py::arg("seed"),
         py::arg("label_smoothing") = 0.0);

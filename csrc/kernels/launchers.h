@@ -190,6 +190,21 @@ void launch_token_head_wide_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* 
 // null (pred only: rec, g0 and stats untouched). rec fp32 [B][8], pred int32 [B][2], g0 fp32 [R][2], stats fp32 [8].
 void launch_span_ce(const bf16_t* logits, const int* cu, const int64_t* mask, const int64_t* pos, int max_answer_length,
                     float* rec, int* pred, float* g0, float* stats, int R, int B, hipStream_t st);
+// sent_head.hip: the head of --task sentence-embedding. h [R][H] bf16 holds n sequences (cu int32 [n+1], mask int64 [R]
+// optional); H % 8 == 0, H <= 1024, n < 65,535. maxch = sent_pool_chunks(longest sequence): rows of a sequence past
+// maxch · 128 are not read (forward) and get zeros (backward). e fp32 [n][H], aux fp32 [n][2] = {1/|mean|, live rows},
+// ws fp32 [n][maxch][H] and wsc int32 [n][maxch] workspaces (read only when maxch > 1). The backward writes every row
+// of dh. Scores: n = 2B, valid int32 [B]; lse2 fp32 [B][2] = {row max, Σ of the other terms}, rec fp32 [B][2],
+// stats fp32 [4] = {mean loss, hits, n_valid, loss sum}; the backward writes every element of de fp32 [2B][H] (dloss fp32 [1] on the device).
+int sent_pool_chunks(int max_seqlen);
+void launch_sent_pool_fwd(const bf16_t* h, const int* cu, const int64_t* mask, float* e, float* aux, float* ws,
+                          int* wsc, int R, int H, int n, int maxch, hipStream_t st);
+void launch_sent_pool_bwd(const float* de, const float* e, const float* aux, const int* cu, const int64_t* mask,
+                          bf16_t* dh, int R, int H, int n, int maxch, hipStream_t st);
+void launch_sent_score_fwd(const float* e, const int* valid, float scale, float* lse2, float* rec, float* stats, int B,
+                           int H, hipStream_t st);
+void launch_sent_score_bwd(const float* e, const int* valid, float scale, const float* lse2, const float* stats,
+                           const float* dloss, float* de, int B, int H, hipStream_t st);
 // attention.hip
 bool attn_streaming(int S);
 // kmask (optional, streaming S > 128 kernels: attn_keep_mask_supported): the forward writes its dropout keep bits

@@ -15,6 +15,7 @@ Offline here, so:
 """
 from __future__ import annotations
 
+import csv
 import glob
 import json
 import os
@@ -35,6 +36,7 @@ class ArrayDataset:
     token_type_ids: Optional[np.ndarray] = None  # [N, S] segment ids (question answering with BERT), else None
     span_labels: bool = False    # labels are [N, 2] (start, end) token positions, not one label per row
     row_targets: bool = False    # labels are fp32 [N, C] row targets (--problem_type regression / multi-label)
+    pairs: bool = False          # input_ids / attention_mask are [N, 2 S]: an anchor's S columns, then its positive's
 
     def __len__(self) -> int:
         return int(self.input_ids.shape[0])
@@ -165,6 +167,60 @@ def _frame(ids: np.ndarray, lengths: np.ndarray, bos_id: int, eos_id: int, pad_i
     mask = np.arange(seq_len)[None, :] < lengths[:, None]
     ids[~mask] = pad_id
     return mask.astype(np.int8)
+
+
+def synthetic_pairs(num_examples: int, seq_len: int, vocab_size: int, seed: int = 0, cls_id: int = 101,
+                    sep_id: int = 102, pad_id: int = 0, noise: float = 0.15, full_length: bool = False) -> ArrayDataset:
+    """``--task sentence-embedding --dataset synthetic``: (anchor, positive) pairs as ``[N, 2 S]`` columns, the anchor's
+    S then the positive's. The anchor is i.i.d. tokens; the positive repeats the anchor's content tokens (cyclically, to
+    its own independently drawn ragged length) with a share ``noise`` of them resampled, so in-batch retrieval is
+    learnable and two different pairs share nothing but chance tokens (no false negatives). ``labels`` is a placeholder
+    0 per pair (-100 marks a pair that takes no part)."""
+    rng = np.random.default_rng(seed)
+    lo = 1000 if vocab_size > 4000 else 4
+    S = seq_len
+    ids = np.empty((num_examples, 2, S), dtype=np.int64)
+    ids[:, 0] = rng.integers(lo, vocab_size, size=(num_examples, S))
+    la, lp = (_ragged_lengths(rng, num_examples, S, full_length) for _ in range(2))
+    content = np.maximum(la - 2, 1)[:, None]
+    ids[:, 1, 1:] = np.take_along_axis(ids[:, 0], 1 + np.arange(S - 1)[None, :] % content, axis=1)
+    swap = rng.random((num_examples, S)) < noise
+    ids[:, 1] = np.where(swap, rng.integers(lo, vocab_size, size=(num_examples, S)), ids[:, 1])
+    mask = np.stack([_frame(ids[:, 0], la, cls_id % vocab_size, sep_id % vocab_size, pad_id),
+                     _frame(ids[:, 1], lp, cls_id % vocab_size, sep_id % vocab_size, pad_id)], axis=1)
+    return ArrayDataset(ids.reshape(num_examples, 2 * S).astype(np.int32), mask.reshape(num_examples, 2 * S),
+                        np.zeros(num_examples, dtype=np.int64), pairs=True)
+
+
+def read_pairs(path: str) -> Tuple[List[str], List[str]]:
+    """A local pair file: tsv (with a header row) or jsonl with two text columns named ``anchor`` / ``positive`` or
+    ``sentence1`` / ``sentence2``."""
+    rows: List[Dict[str, str]] = []
+    with open(path, encoding="utf-8") as f:
+        if path.endswith((".jsonl", ".json")):
+            rows = [json.loads(line) for line in f if line.strip()]
+        else:
+            rows = list(csv.DictReader(f, delimiter="\t"))
+    for a, p in (("anchor", "positive"), ("sentence1", "sentence2")):
+        if rows and a in rows[0] and p in rows[0]:
+            return [str(r[a]) for r in rows], [str(r[p]) for r in rows]
+    raise ValueError(f"{path}: expected two text columns anchor / positive or sentence1 / sentence2")
+
+
+def pairs_split_path(dataset_dir: str, split: str) -> str:
+    for ext in (".tsv", ".jsonl"):
+        p = os.path.join(dataset_dir, split + ext)
+        if os.path.isfile(p):
+            return p
+    raise FileNotFoundError(f"--dataset pairs: no {split}.tsv or {split}.jsonl in {dataset_dir}")
+
+
+def tokenize_pairs(tokenizer, anchors: List[str], positives: List[str], max_length: int) -> ArrayDataset:
+    """Both sides tokenised on their own to ``max_length`` and laid side by side: ``[N, 2 S]``."""
+    a, p = tokenizer.encode_batch(anchors, max_length), tokenizer.encode_batch(positives, max_length)
+    return ArrayDataset(np.concatenate([a["input_ids"], p["input_ids"]], axis=1).astype(np.int32),
+                        np.concatenate([a["attention_mask"], p["attention_mask"]], axis=1).astype(np.int8),
+                        np.zeros(len(anchors), dtype=np.int64), pairs=True)
 
 
 def synthetic_mlm_raw(num_examples: int, seq_len: int, vocab_size: int, seed: int = 0, bos_id: int = 0, eos_id: int = 2,

@@ -68,7 +68,15 @@ class BatchLoader:
                 extra["span_labels"] = True
             if row_targets:
                 extra["row_targets"] = True
-            pk = pack_batch(self.ds.input_ids[ix], self.ds.attention_mask[ix], labels, **self.pack_rule, **extra)
+            ids, mask, plabels = self.ds.input_ids[ix], self.ds.attention_mask[ix], labels
+            if getattr(self.ds, "pairs", False):
+                # [B, 2 S] -> [2 B, S]: anchor i and its positive become sequences 2 i and 2 i + 1 of the packed buffer;
+                # the per-pair labels [B] travel as they are
+                ids, mask = ids.reshape(2 * len(ix), -1), mask.reshape(2 * len(ix), -1)
+                plabels = np.zeros(2 * len(ix), dtype=np.int64)
+            pk = pack_batch(ids, mask, plabels, **self.pack_rule, **extra)
+            if getattr(self.ds, "pairs", False):
+                pk["labels"] = labels
             ints = {k: pk.pop(k) for k in ("max_seqlen", "real_tokens")}
             b = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in pk.items()}
         else:

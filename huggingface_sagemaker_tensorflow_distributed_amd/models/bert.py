@@ -396,6 +396,65 @@ class TransformerForQuestionAnswering(_Base):
         return loss, logits.view(shape)
 
 
+class TransformerForSentenceEmbedding(_Base):
+    """A sentence-embedding encoder (sentence-transformers ``Transformer -> Pooling(mean) -> Normalize``, the layout of
+    ``all-mpnet-base-v2``) trained on (anchor, positive) pairs with the in-batch-negatives contrastive loss
+    (``MultipleNegativesRankingLoss``, ``ops.sentence_head``). No head parameters: the checkpoint is the base model's
+    (``architectures = ["MPNetModel"]``, ``["BertModel"]``, ...), which ``transformers.AutoModel`` loads.
+
+    Inputs: padded ``input_ids`` / ``attention_mask`` ``[B, 2S]``, the anchor's S columns then the positive's, viewed
+    as ``[2B, S]`` (sequence ``2i`` = anchor i, ``2i+1`` = its positive); or a packed ``[1, T]`` buffer of ``2B``
+    sequences in that order with ``cu_seqlens``. ``labels [B]``: -100 marks a pair that takes no part (shard padding),
+    anything else a valid pair. Returns ``(loss, e)`` with ``e [2B, H]`` the normalised embeddings (fp32), or ``e``
+    without labels. ``loss._hsd_stats`` = {mean loss, hits, n_valid, loss sum}; hits / n_valid is the in-batch
+    retrieval accuracy. The negatives are the local batch's: with data parallelism every rank contrasts within its own
+    pairs. An MPNet encoder passes its relative bias as always; the first-token-rows last layer never engages. Nothing
+    reads a device value on the host (``graph_safe``)."""
+
+    graph_safe = True
+    contrastive_scale = 20.0  # --contrastive_scale (sentence-transformers' default): a training argument
+    bare_checkpoint = True    # models/hf_io.py writes the base model's own key names (no "bert." / "mpnet." prefix)
+
+    def architecture(self) -> str:
+        return _FAMILY[self.cfg.model_type] + "Model"
+
+    def _hidden(self, input_ids, attention_mask, token_type_ids, cu_seqlens, max_seqlen, position_ids):
+        """-> (h2d [R, H], cu int32 [n+1], row_mask [R] or None, longest sequence as a host int)"""
+        if cu_seqlens is not None:
+            h = self._encode(input_ids, None, token_type_ids, cu_seqlens, max_seqlen, position_ids)
+            return h, cu_seqlens, None, int(max_seqlen)
+        n, S = input_ids.shape
+        h = self._encode(input_ids, attention_mask, token_type_ids, None, None, None)
+        cu = self.encoder.embeddings._cached(
+            "cu", input_ids, lambda: torch.arange(n + 1, device=input_ids.device, dtype=torch.int32) * S)
+        return h.reshape(n * S, -1), cu, attention_mask.reshape(-1) if attention_mask is not None else None, S
+
+    def encode(self, input_ids, attention_mask=None, token_type_ids=None, *, cu_seqlens=None, max_seqlen=None,
+               position_ids=None):
+        """Normalised embeddings ``[n, H]`` (fp32) of ``n`` sequences: padded ``[n, S]`` ids with mask, or a packed
+        buffer."""
+        h, cu, row_mask, longest = self._hidden(input_ids, attention_mask, token_type_ids, cu_seqlens, max_seqlen,
+                                                position_ids)
+        return ops.pool_normalize(h, cu, row_mask, max_seqlen=longest)
+
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, *, cu_seqlens=None,
+                max_seqlen=None, position_ids=None):
+        if cu_seqlens is None:
+            B, S2 = input_ids.shape
+            if S2 % 2:
+                raise ValueError(f"a pair batch holds [B, 2 S] columns (anchor then positive), got {S2}")
+            pair = lambda x: x.reshape(2 * B, S2 // 2) if x is not None else None  # noqa: E731
+            input_ids, attention_mask, token_type_ids = pair(input_ids), pair(attention_mask), pair(token_type_ids)
+        elif (cu_seqlens.numel() - 1) % 2:
+            raise ValueError("a packed pair batch holds an even number of sequences (anchor, positive, anchor, ...)")
+        h, cu, row_mask, longest = self._hidden(input_ids, attention_mask, token_type_ids, cu_seqlens, max_seqlen,
+                                                position_ids)
+        if labels is None:
+            return ops.pool_normalize(h, cu, row_mask, max_seqlen=longest)
+        valid = labels.reshape(-1).ne(-100).to(torch.int32)
+        return ops.sentence_head(h, cu, row_mask, valid, self.contrastive_scale, max_seqlen=longest)
+
+
 class RobertaForMaskedLM(_Base):
     """RoBERTa MLM (decoder tied to the word embeddings), for the roberta-large pretraining config."""
 
@@ -548,6 +607,8 @@ def build_model(cfg: ModelConfig, task: str = "sequence-classification", seed: O
         # itself keeps refusing the string "question-answering", which tests/test_token_classification.py pins as its
         # example of a task this function does not know.
         m = TransformerForQuestionAnswering(cfg)
+    elif task == "sentence-embedding":
+        m = TransformerForSentenceEmbedding(cfg)
     else:
         raise ValueError(task)
     g = None

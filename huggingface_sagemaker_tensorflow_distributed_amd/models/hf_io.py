@@ -28,7 +28,10 @@ def hf_state_dict(model: _Base, dtype: Optional[torch.dtype] = torch.float32) ->
     params = dict(model.named_parameters())
     padded = model.padded_rows() if hasattr(model, "padded_rows") else {}
     out: Dict[str, torch.Tensor] = {}
+    base = model.base_prefix + "."
     for hf_key, ikey, split, nsplit in model.hf_names():
+        if getattr(model, "bare_checkpoint", False) and hf_key.startswith(base):
+            hf_key = hf_key[len(base):]  # a base-model checkpoint (sentence-embedding): HF's *Model key names
         t = params[ikey].detach()
         if ikey in padded:
             t = t[:padded[ikey]]  # drop the zero vocabulary padding rows

@@ -41,6 +41,9 @@ QA_HEAD_FUSED = os.environ.get("HSD_QA_HEAD", "fused").strip().lower() != "compo
 # HSD_SEQ_HEAD=composed: the sequence-level head of --problem_type (and of single-label heads with 5..64 classes) as
 # composed ops + reference.seq_loss instead of the fused kernels of csrc/kernels/seq_head.hip (A/B measurements)
 SEQ_HEAD_FUSED = os.environ.get("HSD_SEQ_HEAD", "fused").strip().lower() != "composed"
+# HSD_SENT_HEAD=composed: the sentence-embedding head (pooling, normalisation, in-batch contrastive loss) as the composed
+# reference ops instead of the fused kernels of csrc/kernels/sent_head.hip (A/B measurements)
+SENT_HEAD_FUSED = os.environ.get("HSD_SENT_HEAD", "fused").strip().lower() != "composed"
 
 
 def _hip(x: torch.Tensor) -> bool:
@@ -437,6 +440,51 @@ def qa_head(h2d, w, b, positions, cu, row_mask, p: float, seed: int, max_answer_
             return out
         loss, logits, stats, pred = out
     return _with_stats(loss, stats, pred), logits
+
+
+def _sent_fused(h2d, cu) -> bool:
+    return _hip(h2d) and SENT_HEAD_FUSED and _hipmod().sent_head_ok(h2d, cu)
+
+
+def pool_normalize(h2d, cu, row_mask, max_seqlen=None):
+    """Masked mean pooling + L2 normalisation of the ``n`` sequences of the flat ``h2d [R, H]`` -> ``e [n, H]`` fp32
+    (definition: ``reference.pool_normalize``; ``cu`` / ``row_mask`` as in :func:`qa_head`). bf16 GPU tensors with
+    H % 8 == 0 and H <= 1024 run the pooling kernels of csrc/kernels/sent_head.hip (one read of ``h2d``, one write of
+    its gradient), unless ``HSD_SENT_HEAD=composed``; everything else the reference op. ``max_seqlen``: the longest
+    sequence as a host int, if the caller knows it (it sizes the kernels' grid)."""
+    if _sent_fused(h2d, cu):
+        return _hipmod().pool_normalize(h2d, cu, row_mask, max_seqlen)
+    return _ref.pool_normalize(h2d, cu, row_mask)
+
+
+def contrastive_loss(e, valid, scale: float):
+    """In-batch-negatives contrastive loss of the normalised embeddings ``e [2B, H]`` (row ``2i`` anchor, ``2i+1`` its
+    positive; definition: ``reference.contrastive_loss``) with {mean loss, hits, n_valid, loss sum} on
+    ``loss._hsd_stats`` and the retrieval hits on ``loss._hsd_correct``. fp32 GPU embeddings with H % 8 == 0 and
+    H <= 1024 run the streamed fp32-MFMA score kernels of csrc/kernels/sent_head.hip (no ``B x B`` tensor), unless
+    ``HSD_SENT_HEAD=composed`` or ``HSD_OPS=torch``; everything else the reference op.
+
+    The negatives are the local batch's: under data parallelism every rank contrasts within its own pairs and the
+    gradients are averaged as always."""
+    if (e.is_cuda and not _FORCE_TORCH and SENT_HEAD_FUSED and e.dtype == torch.float32 and e.dim() == 2
+            and e.shape[0] == 2 * valid.numel() and e.shape[1] % 8 == 0 and 8 <= e.shape[1] <= 1024
+            and 1 <= valid.numel() < (1 << 20) and valid.is_cuda):
+        loss, stats = _hipmod().contrastive_loss(e, valid, scale)
+    else:
+        loss, stats = _ref.contrastive_loss(e, valid, scale)
+    return _with_stats(loss, stats)
+
+
+def sentence_head(h2d, cu, row_mask, valid, scale: float, max_seqlen=None):
+    """The head of ``--task sentence-embedding``: :func:`pool_normalize` then :func:`contrastive_loss`. Returns
+    ``(loss, e)``. bf16 GPU tensors within the kernels' limits run csrc/kernels/sent_head.hip end to end; everything
+    else (CPU, fp32 GPU tensors, ``HSD_OPS=torch``, other shapes, ``HSD_SENT_HEAD=composed``) the composed reference
+    ops."""
+    if _sent_fused(h2d, cu):
+        e = _hipmod().pool_normalize(h2d, cu, row_mask, max_seqlen)
+        return contrastive_loss(e, valid, scale), e
+    loss, e, stats = _ref.sentence_head(h2d, cu, row_mask, valid, scale)
+    return _with_stats(loss, stats), e
 
 
 def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps, wemb, bias, vocab, label_smoothing: float = 0.0):

@@ -1825,6 +1825,90 @@ def qa_head_logits(h2d, w, b, cu, row_mask, p, seed, max_answer_length):
     return logits, pred
 
 
+# ------------------------------------------------------------------------------------------ sentence-embedding head
+def sent_head_ok(h2d, cu) -> bool:
+    """What csrc/kernels/sent_head.hip takes: bf16 rows ``[R, H]`` with H % 8 == 0 and H <= 1024, offsets on the
+    device, fewer than 65,535 sequences (any sequence length)."""
+    return (h2d.is_cuda and h2d.dtype == torch.bfloat16 and h2d.dim() == 2 and h2d.shape[1] % 8 == 0
+            and 8 <= h2d.shape[1] <= 1024 and 1 <= h2d.shape[0] < (1 << 31) - 256 and cu.is_cuda
+            and 2 <= cu.numel() <= 65535)
+
+
+class _PoolNormalize(torch.autograd.Function):
+    """pool_fwd_kernel (+ pool_finalize_kernel beyond 128 rows) -> e; backward pool_bwd_kernel writes all of dh once."""
+
+    @staticmethod
+    def forward(ctx, h2d, cu, row_mask, max_seqlen):
+        x = h2d.contiguous()
+        R, H = x.shape
+        n = cu.numel() - 1
+        cu32, mask = _span_args(x, cu, row_mask)
+        longest = R if max_seqlen is None else max(1, min(int(max_seqlen), R))
+        ch = _C.sent_pool_chunks(longest)
+        e = torch.empty((n, H), dtype=torch.float32, device=x.device)
+        aux = torch.empty((n, 2), dtype=torch.float32, device=x.device)
+        ws = torch.empty(n * ch * H if ch > 1 else 0, dtype=torch.float32, device=x.device)
+        wsc = torch.empty(n * ch if ch > 1 else 0, dtype=torch.int32, device=x.device)
+        _C.sent_pool_fwd(x, cu32, mask, e, aux, ws, wsc, longest)
+        ctx.save_for_backward(e, aux, cu32, mask)
+        ctx.cfg = (R, longest)
+        return e
+
+    @staticmethod
+    def backward(ctx, de):
+        e, aux, cu32, mask = ctx.saved_tensors
+        R, longest = ctx.cfg
+        dh = torch.empty((R, e.shape[1]), dtype=torch.bfloat16, device=e.device)
+        _C.sent_pool_bwd(de.contiguous().float(), e, aux, cu32, mask, dh, longest)
+        return dh, None, None, None
+
+
+class _ContrastiveLoss(torch.autograd.Function):
+    """score_kernel<0> + score_stats_kernel -> (loss, stats); backward score_kernel<1> twice (anchors, positives)."""
+
+    @staticmethod
+    def forward(ctx, e, valid, scale):
+        ec = e.contiguous()
+        B = ec.shape[0] // 2
+        v32 = (valid if valid.dtype == torch.int32 else valid.ne(0).to(torch.int32)).reshape(-1).contiguous()
+        lse2 = torch.empty((B, 2), dtype=torch.float32, device=ec.device)  # {row max, sum of the other terms}
+        rec = torch.empty((B, 2), dtype=torch.float32, device=ec.device)
+        stats = torch.empty(4, dtype=torch.float32, device=ec.device)
+        _C.sent_score_fwd(ec, v32, float(scale), lse2, rec, stats)
+        ctx.save_for_backward(ec, v32, lse2, stats)
+        ctx.scale = float(scale)
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)
+        return stats[0], stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats):
+        ec, v32, lse2, stats = ctx.saved_tensors
+        de = torch.empty_like(ec)
+        dl = dloss.detach().reshape(1).float().contiguous()
+        _C.sent_score_bwd(ec, v32, ctx.scale, lse2, stats, dl, de)
+        return de, None, None
+
+
+def pool_normalize(h2d, cu, row_mask, max_seqlen=None):
+    """e fp32 [n, H] of the fused pooling kernels. ``max_seqlen``: the longest sequence as a host int (sizes the grid;
+    the whole buffer's row count when it is not given)."""
+    return _PoolNormalize.apply(h2d, cu, row_mask, max_seqlen)
+
+
+def contrastive_loss(e, valid, scale):
+    """(loss, stats) of the streamed score kernels on e fp32 [2B, H]; stats = fp32 {mean loss, hits, n_valid, loss
+    sum}."""
+    return _ContrastiveLoss.apply(e, valid, scale)
+
+
+def sentence_head(h2d, cu, row_mask, valid, scale, max_seqlen=None):
+    """(loss, e, stats): the two fused ops composed."""
+    e = pool_normalize(h2d, cu, row_mask, max_seqlen)
+    loss, stats = contrastive_loss(e, valid, scale)
+    return loss, e, stats
+
+
 # ------------------------------------------------------------------------------------------ masked-LM head
 def mlm_head_ok(h2d, w1, wemb) -> bool:
     T, H = h2d.shape

@@ -396,6 +396,54 @@ def qa_head(h2d, w, b, positions, cu, row_mask, p: float, seed: int, max_answer_
     return loss, logits, stats, pred
 
 
+def pool_normalize(h2d, cu, row_mask):
+    """Masked mean pooling + L2 normalisation of the ``n = cu.numel() - 1`` sequences of the flat ``h2d [R, H]``
+    (sentence-transformers ``Pooling(mean)`` + ``Normalize``): ``m_s = Σ_r w_r h_r / max(Σ_r w_r, 1)`` over the rows
+    ``cu[s] .. cu[s+1]-1`` with ``w_r = row_mask[r] != 0`` (1 without a mask), ``e_s = m_s / max(|m_s|, 1e-12)``.
+    Returns ``e [n, H]`` in fp32 (fp64 for fp64 input). A sequence without a live row gives ``e_s = 0`` and no
+    gradient; masked rows and rows outside every sequence get an exactly zero gradient. No host read."""
+    n = cu.numel() - 1
+    seg, _, real = span_segments(cu, h2d.shape[0], row_mask)
+    x = h2d if h2d.dtype == torch.float64 else h2d.float()
+    x = torch.where(real[:, None], x, torch.zeros((), dtype=x.dtype, device=x.device))
+    idx = seg.clamp(max=n)
+    tot = torch.zeros((n + 1, x.shape[1]), dtype=x.dtype, device=x.device).index_add(0, idx, x)[:n]
+    cnt = torch.zeros(n + 1, dtype=x.dtype, device=x.device).index_add(0, idx, real.to(x.dtype))[:n]
+    m = tot / cnt.clamp(min=1.0)[:, None]
+    return m / m.norm(dim=1, keepdim=True).clamp(min=1e-12)
+
+
+def contrastive_loss(e, valid, scale: float):
+    """In-batch-negatives contrastive loss (sentence-transformers ``MultipleNegativesRankingLoss``) of the normalised
+    embeddings ``e [2B, H]``: row ``2i`` is anchor ``a_i``, row ``2i+1`` its positive ``p_i``; pair ``i`` takes part iff
+    ``valid[i] != 0``. ``s_ij = scale <a_i, p_j>``,
+    ``loss = Σ_{i valid} (logsumexp_{j valid} s_ij - s_ii) / max(n_valid, 1)`` (0 when no pair is valid).
+    Returns ``(loss, stats)``: ``stats`` fp32 [4] = {mean loss, hits, n_valid, loss sum}; ``hits`` counts the valid
+    ``i`` whose first argmax over the valid ``j`` is ``i`` (in-batch retrieval accuracy). No host read."""
+    B = valid.numel()
+    ok = valid.reshape(-1).ne(0)
+    ev = e.view(B, 2, -1)
+    s = float(scale) * (ev[:, 0] @ ev[:, 1].t())
+    s = s.masked_fill(~ok[None, :], float("-inf"))
+    # an invalid anchor's row would be all -inf once every pair is invalid: give it a finite stand-in, it is dropped
+    s = torch.where(ok[:, None], s, torch.zeros((), dtype=s.dtype, device=s.device))
+    terms = torch.where(ok, torch.logsumexp(s, dim=1) - s.diagonal(), torch.zeros((), dtype=s.dtype, device=s.device))
+    nv = ok.sum().to(s.dtype)
+    lsum = terms.sum()
+    loss = lsum / nv.clamp(min=1.0)
+    with torch.no_grad():
+        hits = ((s.argmax(dim=1) == torch.arange(B, device=s.device)) & ok).sum()
+        stats = torch.stack([loss.detach().float(), hits.float(), nv.float(), lsum.detach().float()])
+    return loss, stats
+
+
+def sentence_head(h2d, cu, row_mask, valid, scale: float):
+    """``contrastive_loss(pool_normalize(h2d, cu, row_mask), valid, scale)`` -> ``(loss, e, stats)``."""
+    e = pool_normalize(h2d, cu, row_mask)
+    loss, stats = contrastive_loss(e, valid, scale)
+    return loss, e, stats
+
+
 def mlm_head(h2d, labels, w1, b1, ln_w, ln_b, eps: float, wemb, bias, vocab: int, label_smoothing: float = 0.0):
     """RoBERTa LM head on the masked positions (labels != -100) of ``h2d`` [T, H]: ``LN(gelu(x W1ᵀ + b1))`` ->
     tied decoder (``wemb[:vocab]``, ``bias[:vocab]``) -> mean CE (``label_smoothing`` as in :func:`cross_entropy`,

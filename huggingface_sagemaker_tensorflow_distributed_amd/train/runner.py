@@ -16,6 +16,7 @@ from __future__ import annotations
 import contextlib
 import json
 import logging
+import math
 import os
 import time
 from typing import List, Optional, Sequence
@@ -119,6 +120,22 @@ def _datasets(args, cfg, tokenizer, max_len: int):
                                                 segment_ids=segs))
             return out[0], out[1]
         raise ValueError(_QA_DATASETS.format(args.dataset))
+    if getattr(args, "task", "sequence-classification") == "sentence-embedding":
+        check_sentence_embedding(args)
+        if args.dataset == "synthetic":
+            kw = {"pad_id": cfg.pad_token_id}
+            if cfg.roberta_ids or cfg.model_type == "mpnet":
+                kw.update(cls_id=cfg.bos_token_id if cfg.bos_token_id is not None else 0,
+                          sep_id=cfg.eos_token_id if cfg.eos_token_id is not None else 2)
+            return (hdata.synthetic_pairs(n_train or 2048, max_len, cfg.vocab_size, seed=args.seed, **kw),
+                    hdata.synthetic_pairs(n_eval or 512, max_len, cfg.vocab_size, seed=args.seed + 1, **kw))
+        out = []
+        for split, n in (("train", n_train), ("test", n_eval)):
+            a, p = hdata.read_pairs(hdata.pairs_split_path(args.dataset_dir, split))
+            out.append(hdata.tokenize_pairs(tokenizer, a[:n] if n else a, p[:n] if n else p, max_len))
+        return out[0], out[1]
+    if args.dataset == "pairs":
+        raise ValueError("--dataset pairs holds (anchor, positive) text pairs (--task sentence-embedding)")
     if args.dataset == "squad":
         raise ValueError("--dataset squad holds answer spans (--task question-answering)")
     if args.dataset == "conll":
@@ -166,6 +183,27 @@ _PTYPE_DATASETS = ("--problem_type {} needs float targets: --dataset synthetic o
                    "(--dataset_dir); --dataset {} holds one class per text")
 _QA_DATASETS = ("--task question-answering trains on --dataset synthetic or squad (start / end positions); "
                 "--dataset {} holds no answer spans")
+
+
+def check_sentence_embedding(args) -> float:
+    """What ``--task sentence-embedding`` refuses when the run is built; returns ``--contrastive_scale``."""
+    scale = float(getattr(args, "contrastive_scale", 20.0))
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"--contrastive_scale {scale} must be finite and > 0")
+    if float(getattr(args, "label_smoothing_factor", 0.0) or 0.0) != 0.0:
+        raise ValueError("--label_smoothing_factor smooths a single-label cross-entropy; --task sentence-embedding "
+                         "trains a contrastive loss")
+    if getattr(args, "problem_type", None) is not None:
+        raise ValueError(f"--problem_type {args.problem_type} is valid only with --task sequence-classification")
+    if getattr(args, "mlm_masking", "static") != "static" or float(getattr(args, "mlm_probability", 0.15)) != 0.15:
+        raise ValueError("--mlm_masking / --mlm_probability belong to --task masked-lm")
+    if args.dataset not in ("synthetic", "pairs"):
+        raise ValueError(f"--task sentence-embedding trains on --dataset synthetic or pairs ((anchor, positive) text "
+                         f"pairs under --dataset_dir); --dataset {args.dataset} holds none")
+    if args.dataset == "pairs" and not args.dataset_dir:
+        raise ValueError("--dataset pairs needs --dataset_dir (train / test .tsv or .jsonl with anchor / positive or "
+                         "sentence1 / sentence2 columns)")
+    return scale
 
 
 def _label_smoothing(args, task: str, ptype) -> float:
@@ -260,6 +298,15 @@ def _provenance(args, model, rank: int, n_train: int, n_eval: int, batch_plan=No
         info["metric"] = ("loss and exact match of the best (start, end) token span over the windows with both "
                           "labels valid (not text-level EM / F1)")
         logger.info("question-answering corpus: %s; max_answer_length %d", info["corpus"], info["max_answer_length"])
+    if getattr(args, "task", "sequence-classification") == "sentence-embedding":
+        info["task"] = "sentence-embedding"
+        info["contrastive_scale"] = float(getattr(model, "contrastive_scale", 20.0))
+        info["corpus"] = ("pair files in " + str(args.dataset_dir) if args.dataset == "pairs" else
+                          "synthetic pair corpus (the positive repeats its anchor's tokens with 15 % resampled, ragged "
+                          "lengths drawn independently)")
+        info["metric"] = ("in-batch-negatives contrastive loss; accuracy = in-batch retrieval accuracy (anchors whose "
+                          "best-scoring positive of the local batch is their own), which depends on the batch size")
+        logger.info("sentence-embedding corpus: %s; --contrastive_scale %g", info["corpus"], info["contrastive_scale"])
     ptype = getattr(model.cfg, "problem_type", None)
     if ptype is not None and getattr(args, "task", "sequence-classification") == "sequence-classification":
         info["problem_type"] = ptype
@@ -331,6 +378,7 @@ def build(args, mode: str):
                          f"--dataset {args.dataset} holds one label per text")
     if task == "question-answering" and args.dataset not in ("synthetic", "squad"):
         raise ValueError(_QA_DATASETS.format(args.dataset))
+    scale = check_sentence_embedding(args) if task == "sentence-embedding" else None
     ptype = getattr(args, "problem_type", None)
     if ptype is not None and task != "sequence-classification":
         raise ValueError(f"--problem_type {ptype} is valid only with --task sequence-classification, not --task {task}")
@@ -360,6 +408,8 @@ def build(args, mode: str):
     model.to(dev)
     model.rng.base_seed = args.seed
     model.rng.rank = rank
+    if scale is not None:
+        model.contrastive_scale = scale  # a training argument on the model object (never in config.json)
     if task == "question-answering":
         if int(getattr(args, "max_answer_length", 30)) < 1:
             raise ValueError(f"--max_answer_length {args.max_answer_length} must be at least 1")

@@ -156,12 +156,17 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
     g.add_argument("--device", type=str, default=None, help="cuda | cpu (default: cuda if available)")
     g.add_argument("--num_labels", type=int, default=2)
     g.add_argument("--task", choices=["sequence-classification", "masked-lm", "token-classification",
-                                      "question-answering"],
+                                      "question-answering", "sentence-embedding"],
                    default="sequence-classification",
                    help="masked-lm: RoBERTa MLM pretraining (BASELINE.json config 5); token-classification: one label "
                         "per token (NER / POS tagging; --dataset synthetic or conll, --num_labels follows the tag list "
                         "of a CoNLL directory); question-answering: extractive start / end span prediction "
-                        "(--dataset synthetic or squad)")
+                        "(--dataset synthetic or squad); sentence-embedding: mean-pooled, L2-normalised embeddings "
+                        "trained on (anchor, positive) pairs with the in-batch-negatives contrastive loss "
+                        "(sentence-transformers' MultipleNegativesRankingLoss; --dataset synthetic or pairs with "
+                        "train / test .tsv or .jsonl under --dataset_dir; accuracy = in-batch retrieval accuracy)")
+    g.add_argument("--contrastive_scale", type=float, default=20.0,
+                   help="sentence-embedding: the factor on the cosine similarities before the softmax (finite, > 0)")
     g.add_argument("--problem_type", choices=["single_label_classification", "multi_label_classification",
                                               "regression"], default=None,
                    help="sequence-classification only (HF config.problem_type; default single-label cross-entropy on "
