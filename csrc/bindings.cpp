@@ -1746,6 +1746,88 @@ void span_ce(torch::Tensor logits, torch::Tensor cu, c10::optional<torch::Tensor
                       (int)B, cur_stream());
 }
 
+// ---- linear-chain CRF head (crf_head.hip). em [R][C] bf16 (2 <= C <= 16); cu int32 [B+1]; theta fp32 [C·C + 2C] =
+// {trans, start, end}; ws_alpha fp32 [R][16]; ws_bp u8 [R][16]
+static void crf_check(const torch::Tensor& em, const torch::Tensor& cu, const torch::Tensor& theta, int64_t* R,
+                      int64_t* B, int64_t* C) {
+  TORCH_CHECK(em.is_cuda() && em.dim() == 2 && em.is_contiguous() && em.scalar_type() == torch::kBFloat16,
+              "crf emissions [R][C] bf16");
+  *R = em.size(0);
+  *C = em.size(1);
+  *B = cu.numel() - 1;
+  TORCH_CHECK(*R >= 1 && *R < ((int64_t)1 << 30) && *B >= 1 && *B < ((int64_t)1 << 30) && *C >= 2 && *C <= 16,
+              "crf: 1 <= rows < 2^30, at least one sequence, 2 <= tags <= 16");
+  TORCH_CHECK(cu.is_cuda() && cu.is_contiguous() && cu.scalar_type() == torch::kInt32, "crf cu int32 [B+1]");
+  check_f32(theta, "crf theta");
+  TORCH_CHECK(theta.numel() == *C * *C + 2 * *C, "crf theta fp32 [C*C + 2C]");
+}
+static const int64_t* crf_rows_i64(const c10::optional<torch::Tensor>& t, int64_t R, const char* what) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == torch::kInt64 && t->numel() == R, what);
+  return t->data_ptr<int64_t>();
+}
+
+// labels given: the chain is the labelled rows; ws_alpha and rec are written. Without: keep int64 [R] (or none) is the
+// row predicate, pred alone is written.
+void crf_forward(torch::Tensor em, torch::Tensor cu, c10::optional<torch::Tensor> labels,
+                 c10::optional<torch::Tensor> keep, torch::Tensor theta, torch::Tensor ws_alpha, torch::Tensor ws_bp,
+                 torch::Tensor pred, torch::Tensor rec) {
+  int64_t R, B, C;
+  crf_check(em, cu, theta, &R, &B, &C);
+  const int64_t* lab = crf_rows_i64(labels, R, "crf labels int64 [R]");
+  const int64_t* kp = crf_rows_i64(keep, R, "crf keep int64 [R]");
+  TORCH_CHECK(ws_bp.is_cuda() && ws_bp.is_contiguous() && ws_bp.scalar_type() == torch::kUInt8 &&
+              ws_bp.numel() >= 16 * R && (uintptr_t)ws_bp.data_ptr() % 16 == 0, "crf ws_bp u8 [R][16], 16-byte aligned");
+  TORCH_CHECK(pred.is_cuda() && pred.is_contiguous() && pred.scalar_type() == torch::kInt32 && pred.numel() == R,
+              "crf pred int32 [R]");
+  float *wa = nullptr, *rp = nullptr;
+  if (lab != nullptr) {
+    check_f32(ws_alpha, "crf ws_alpha");
+    check_f32(rec, "crf rec");
+    TORCH_CHECK(ws_alpha.numel() >= 16 * R && (uintptr_t)ws_alpha.data_ptr() % 16 == 0 && rec.numel() >= 4 * B &&
+                (uintptr_t)rec.data_ptr() % 16 == 0, "crf ws_alpha fp32 [R][16] / rec fp32 [B][4], 16-byte aligned");
+    wa = ws_alpha.data_ptr<float>();
+    rp = rec.data_ptr<float>();
+  }
+  hsd::launch_crf_forward(CBF(em), cu.data_ptr<int>(), lab, kp, theta.data_ptr<float>(), wa, ws_bp.data_ptr<uint8_t>(),
+                          pred.data_ptr<int>(), rp, (int)R, (int)B, (int)C, cur_stream());
+}
+
+void crf_marginals(torch::Tensor em, torch::Tensor cu, torch::Tensor labels, torch::Tensor theta,
+                   torch::Tensor ws_alpha, torch::Tensor g0, torch::Tensor slab) {
+  int64_t R, B, C;
+  crf_check(em, cu, theta, &R, &B, &C);
+  const int64_t* lab = head_labels(labels, R);
+  check_f32(ws_alpha, "crf ws_alpha");
+  check_f32(g0, "crf g0");
+  check_f32(slab, "crf slab");
+  TORCH_CHECK(ws_alpha.numel() >= 16 * R && (uintptr_t)ws_alpha.data_ptr() % 16 == 0 && g0.numel() == R * C &&
+              slab.numel() >= B * (C * C + 2 * C), "crf ws_alpha / g0 / slab");
+  hsd::launch_crf_marginals(CBF(em), cu.data_ptr<int>(), lab, theta.data_ptr<float>(), ws_alpha.data_ptr<float>(),
+                            g0.data_ptr<float>(), slab.data_ptr<float>(), (int)R, (int)B, (int)C, cur_stream());
+}
+
+// rec fp32 [B][4]; slab fp32 [B][C·C + 2C] or none (dtheta untouched); stats fp32 [4]; cnt fp32 [16]; dtheta fp32 [C·C + 2C]
+void crf_reduce(torch::Tensor rec, c10::optional<torch::Tensor> slab, int64_t B, int64_t C, torch::Tensor stats,
+                torch::Tensor cnt, torch::Tensor dtheta) {
+  check_f32(rec, "crf rec");
+  check_f32(stats, "crf stats");
+  check_f32(cnt, "crf cnt");
+  TORCH_CHECK(B >= 1 && B < ((int64_t)1 << 30) && C >= 2 && C <= 16 && rec.numel() >= 4 * B &&
+              (uintptr_t)rec.data_ptr() % 16 == 0 && stats.numel() >= 4 && cnt.numel() >= 16, "crf rec / stats / cnt");
+  const float* sp = nullptr;
+  float* dp = nullptr;
+  if (slab.has_value()) {
+    check_f32(*slab, "crf slab");
+    check_f32(dtheta, "crf dtheta");
+    TORCH_CHECK(slab->numel() >= B * (C * C + 2 * C) && dtheta.numel() == C * C + 2 * C, "crf slab / dtheta");
+    sp = slab->data_ptr<float>();
+    dp = dtheta.data_ptr<float>();
+  }
+  hsd::launch_crf_reduce(rec.data_ptr<float>(), sp, (int)B, (int)C, stats.data_ptr<float>(), cnt.data_ptr<float>(), dp,
+                         cur_stream());
+}
+
 // ---- sentence-embedding head (sent_head.hip). h [R][H] bf16, cu int32 [n+1], mask int64 [R] or none; e fp32 [n][H],
 // aux fp32 [n][2]; ws fp32 / wsc int32 workspaces of n · chunks · H / n · chunks elements, chunks =
 // sent_pool_chunks(max_seqlen)
@@ -2109,6 +2191,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed"), py::arg("label_smoothing") = 0.0);
   m.def("token_head_bwd_given", &token_head_bwd_given);
   m.def("span_ce", &span_ce);
+  m.def("crf_forward", &crf_forward);
+  m.def("crf_marginals", &crf_marginals);
+  m.def("crf_reduce", &crf_reduce);
   m.def("sent_pool_fwd", &sent_pool_fwd);
   m.def("sent_pool_bwd", &sent_pool_bwd);
   m.def("sent_pool_chunks", [](int64_t max_seqlen) { return (int64_t)hsd::sent_pool_chunks((int)max_seqlen); });

@@ -190,6 +190,19 @@ void launch_token_head_wide_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* 
 // null (pred only: rec, g0 and stats untouched). rec fp32 [B][8], pred int32 [B][2], g0 fp32 [R][2], stats fp32 [8].
 void launch_span_ce(const bf16_t* logits, const int* cu, const int64_t* mask, const int64_t* pos, int max_answer_length,
                     float* rec, int* pred, float* g0, float* stats, int R, int B, hipStream_t st);
+// crf_head.hip: linear-chain CRF over the emissions em [R][C] bf16 (2 <= C <= 16) of the B sequences cu int32 [B+1]; one
+// wave per sequence, any length. theta fp32 = {trans [C][C], start [C], end [C]}. The chain of a sequence: its rows with
+// 0 <= label < C, or without labels (decode only: ws_alpha and rec untouched) the rows with keep != 0 (null: all).
+// Forward: ws_alpha fp32 [R][16], ws_bp u8 [R][16] (16-byte aligned), pred int32 [R] (-1 off the chain), rec fp32 [B][4]
+// = {nll, chain rows, hits, 0}. Marginals: g0 fp32 [R][C] (every element written), slab fp32 [B][C·C + 2C]. Reduce:
+// stats fp32 [4] = {mean loss, hits, N, loss sum}, cnt fp32 [16] = N, dtheta fp32 [C·C + 2C] unscaled (slab may be null:
+// dtheta untouched).
+void launch_crf_forward(const bf16_t* em, const int* cu, const int64_t* labels, const int64_t* keep, const float* theta,
+                        float* ws_alpha, uint8_t* ws_bp, int* pred, float* rec, int R, int B, int C, hipStream_t st);
+void launch_crf_marginals(const bf16_t* em, const int* cu, const int64_t* labels, const float* theta,
+                          const float* ws_alpha, float* g0, float* slab, int R, int B, int C, hipStream_t st);
+void launch_crf_reduce(const float* rec, const float* slab, int B, int C, float* stats, float* cnt, float* dtheta,
+                       hipStream_t st);
 // sent_head.hip: the head of --task sentence-embedding. h [R][H] bf16 holds n sequences (cu int32 [n+1], mask int64 [R]
 // optional); H % 8 == 0, H <= 1024, n < 65,535. maxch = sent_pool_chunks(longest sequence): rows of a sequence past
 // maxch · 128 are not read (forward) and get zeros (backward). e fp32 [n][H], aux fp32 [n][2] = {1/|mean|, live rows},

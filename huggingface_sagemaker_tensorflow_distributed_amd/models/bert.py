@@ -150,6 +150,8 @@ def _init_(module: nn.Module, cfg: ModelConfig, generator: Optional[torch.Genera
                     p.fill_(1.0)
                 else:
                     p.zero_()
+            elif leaf.startswith("crf_"):
+                p.uniform_(-0.1, 0.1, generator=generator)  # pytorch-crf's reset_parameters
             elif leaf.endswith("bias"):
                 p.zero_()
             else:
@@ -302,18 +304,64 @@ class TransformerForTokenClassification(_Base):
     Inputs: padded ``[B, S]`` ids with ``[B, S]`` labels (logits ``[B, S, L]``), or a packed ``[1, T]`` buffer with
     ``[T]`` labels (data/packing.py; logits ``[T, L]``). The head (``ops.token_head``) draws one dropout seed after
     the encoder's; its site is the flat ``[rows, H]`` buffer. Nothing reads a device value on the host, so the
-    whole step captures into a graph (``graph_safe``)."""
+    whole step captures into a graph (``graph_safe``).
+
+    ``cfg.use_crf`` (``--crf true``, BERT-CRF): three more parameters (start, end and transition scores) and, with
+    labels, the loss of ``ops.token_crf_head``: the negative log-likelihood of the gold tag sequence over each
+    sequence's labelled rows, divided by their number, with the Viterbi tags on ``loss._hsd_pred`` and their hits in
+    ``loss._hsd_stats`` (the reported accuracy is the decoded one). Without labels ``forward`` still returns the
+    emissions; :meth:`decode` returns tags. The Viterbi back-trace runs on the device: still ``graph_safe``."""
 
     graph_safe = True
     arch_suffix = "ForTokenClassification"
 
     def __init__(self, cfg: ModelConfig):
         super().__init__(cfg)
-        self.classifier_weight, self.classifier_bias = _param(cfg.num_labels, cfg.hidden_size), _param(cfg.num_labels)
+        L = cfg.num_labels
+        self.classifier_weight, self.classifier_bias = _param(L, cfg.hidden_size), _param(L)
+        if cfg.use_crf:
+            # --crf true: additive score biases of a linear-chain CRF over the emissions (ops.token_crf_head). Their
+            # leaf names end in "bias", so weight decay and LAMB's trust ratio leave them alone like every other bias.
+            self.crf_start_bias, self.crf_end_bias, self.crf_transition_bias = _param(L), _param(L), _param(L, L)
 
     def _head_hf_names(self):
         yield "classifier.weight", "classifier_weight", None, 1
         yield "classifier.bias", "classifier_bias", None, 1
+        if self.cfg.use_crf:  # pytorch-crf's names under a ``crf`` submodule
+            yield "crf.start_transitions", "crf_start_bias", None, 1
+            yield "crf.end_transitions", "crf_end_bias", None, 1
+            yield "crf.transitions", "crf_transition_bias", None, 1
+
+    def _offsets(self, input_ids) -> torch.Tensor:
+        B, S = input_ids.shape
+        return self.encoder.embeddings._cached(
+            "cu", input_ids, lambda: torch.arange(B + 1, device=input_ids.device, dtype=torch.int32) * S)
+
+    def _crf_forward(self, h, input_ids, labels, keep, cu_seqlens, max_seqlen, p, seed):
+        if cu_seqlens is not None:
+            cu, longest = cu_seqlens, int(max_seqlen)
+        else:
+            cu, longest = self._offsets(input_ids), int(input_ids.shape[1])
+        return ops.token_crf_head(h.reshape(-1, h.shape[-1]), self.classifier_weight, self.classifier_bias, labels, cu,
+                                  self.crf_start_bias, self.crf_end_bias, self.crf_transition_bias, p, seed, keep=keep,
+                                  max_seqlen=longest)
+
+    def decode(self, input_ids, attention_mask=None, token_type_ids=None, keep=None, *, cu_seqlens=None,
+               max_seqlen=None, position_ids=None) -> torch.Tensor:
+        """Tags without labels: int32, ``[B, S]`` padded / ``[T]`` packed, -1 on the rows left out. ``keep`` (the
+        shape of the result; default: the attention mask, or every row) says which rows form each sequence's chain,
+        e.g. the first subword of every word. With ``--crf`` the Viterbi path, otherwise the per-token argmax."""
+        if keep is None:
+            keep = attention_mask
+        if not self.cfg.use_crf:
+            logits = self.forward(input_ids, attention_mask, token_type_ids, cu_seqlens=cu_seqlens,
+                                  max_seqlen=max_seqlen, position_ids=position_ids)
+            tags = logits.argmax(dim=-1).to(torch.int32)
+            return tags if keep is None else torch.where(keep.reshape(tags.shape).ne(0), tags, torch.full_like(tags, -1))
+        h = self._encode(input_ids, attention_mask, token_type_ids, cu_seqlens, max_seqlen, position_ids)
+        p = self.head_dropout() if self.training else 0.0
+        _, pred = self._crf_forward(h, input_ids, None, keep, cu_seqlens, max_seqlen, p, self.rng.next() if p else 0)
+        return pred.view(tuple(h.shape[:-1]))
 
     def head_dropout(self) -> float:
         c = self.cfg
@@ -327,9 +375,16 @@ class TransformerForTokenClassification(_Base):
         H = h.shape[-1]
         p = self.head_dropout() if self.training else 0.0
         seed = self.rng.next() if p else 0
+        shape = tuple(h.shape[:-1]) + (self.cfg.num_labels,)  # [B, S, L] padded, [T, L] packed
+        if self.cfg.use_crf and labels is not None:
+            # the CRF's sequence likelihood over the labelled rows; without labels the emissions below, as ever
+            if self.label_smoothing:
+                raise ValueError("label_smoothing smooths a per-token cross-entropy; the CRF head trains a sequence "
+                                 "likelihood")
+            loss, logits = self._crf_forward(h, input_ids, labels, None, cu_seqlens, max_seqlen, p, seed)
+            return loss, logits.view(shape)
         out = ops.token_head(h.reshape(-1, H), self.classifier_weight, self.classifier_bias, labels, p, seed,
                              label_smoothing=self.label_smoothing)
-        shape = tuple(h.shape[:-1]) + (self.cfg.num_labels,)  # [B, S, L] padded, [T, L] packed
         if labels is None:
             return out.view(shape)
         loss, logits = out
@@ -587,9 +642,16 @@ class RobertaForMaskedLM(_Base):
 
 
 def build_model(cfg: ModelConfig, task: str = "sequence-classification", seed: Optional[int] = 0,
-                problem_type: Optional[str] = None) -> _Base:
+                problem_type: Optional[str] = None, use_crf: Optional[bool] = None) -> _Base:
     """``problem_type``: sets ``cfg.problem_type`` of a sequence-classification model (models/config.py); any other
-    task refuses it."""
+    task refuses it. ``use_crf``: sets ``cfg.use_crf`` of a token-classification model (None: the config's own);
+    any other task refuses a CRF."""
+    if use_crf is not None and task in ("token-classification", "token-cls"):
+        cfg = cfg.replace(use_crf=bool(use_crf))
+    if (use_crf or cfg.use_crf) and task not in ("token-classification", "token-cls"):
+        if use_crf:
+            raise ValueError(f"use_crf is for task token-classification, not {task!r}")
+        cfg = cfg.replace(use_crf=False)  # a CRF checkpoint's encoder under another head
     if problem_type is not None:
         if task not in ("sequence-classification", "seq-cls"):
             raise ValueError(f"problem_type={problem_type!r} is for task sequence-classification, not {task!r}")

@@ -49,6 +49,8 @@ class ModelConfig:
     # label: it is never inferred from the labels' dtype), "single_label_classification",
     # "multi_label_classification" (BCE-with-logits) or "regression" (MSE)
     problem_type: Optional[str] = None
+    # token-classification only: a linear-chain CRF over the per-token scores (--crf true; config.json "use_crf")
+    use_crf: bool = False
     tie_word_embeddings: bool = True
     # distilbert-only
     sinusoidal_pos_embds: bool = False
@@ -92,6 +94,8 @@ class ModelConfig:
             common["architectures"] = [architecture]
         if self.problem_type is not None:
             common["problem_type"] = self.problem_type
+        if self.use_crf:
+            common["use_crf"] = True
         if mt == "distilbert":
             common.update({
                 "dim": self.hidden_size, "n_layers": self.num_hidden_layers,
@@ -150,6 +154,7 @@ class ModelConfig:
                 sinusoidal_pos_embds=d.get("sinusoidal_pos_embds", False),
                 seq_classif_dropout=d.get("seq_classif_dropout", 0.2), qa_dropout=d.get("qa_dropout", 0.1),
                 id2label=labels, problem_type=check_problem_type(d.get("problem_type")),
+            use_crf=bool(d.get("use_crf", False)),
             )
         if mt == "mpnet":  # [dep: transformers/models/mpnet/configuration_mpnet.py] defaults
             return cls(
@@ -164,6 +169,7 @@ class ModelConfig:
                 eos_token_id=d.get("eos_token_id", 2),
                 relative_attention_num_buckets=d.get("relative_attention_num_buckets", 32),
                 num_labels=nl, id2label=labels, problem_type=check_problem_type(d.get("problem_type")),
+            use_crf=bool(d.get("use_crf", False)),
             )
         return cls(
             model_type=mt, vocab_size=d.get("vocab_size", 30522), hidden_size=d.get("hidden_size", 768),
@@ -178,6 +184,7 @@ class ModelConfig:
             layer_norm_eps=d.get("layer_norm_eps", 1e-12), pad_token_id=d.get("pad_token_id", 0),
             bos_token_id=d.get("bos_token_id"), eos_token_id=d.get("eos_token_id"),
             num_labels=nl, id2label=labels, problem_type=check_problem_type(d.get("problem_type")),
+            use_crf=bool(d.get("use_crf", False)),
         )
 
 

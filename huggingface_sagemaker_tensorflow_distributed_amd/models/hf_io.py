@@ -113,12 +113,14 @@ def read_checkpoint(path: str) -> Optional[Dict[str, torch.Tensor]]:
 
 
 def from_pretrained(name_or_path: str, task: str = "sequence-classification", num_labels: Optional[int] = None,
-                    seed: Optional[int] = 0, problem_type: Optional[str] = None) -> _Base:
-    """``problem_type``: overrides the ``problem_type`` of the config (sequence-classification only)."""
+                    seed: Optional[int] = 0, problem_type: Optional[str] = None,
+                    use_crf: Optional[bool] = None) -> _Base:
+    """``problem_type``: overrides the ``problem_type`` of the config (sequence-classification only). ``use_crf``:
+    overrides its ``use_crf`` (token-classification only; None keeps it, so a saved CRF directory loads as one)."""
     cfg = resolve_config(name_or_path, num_labels=num_labels)
     # the command line's --task question-answering is build_model's "span-extraction"
     model = build_model(cfg, task="span-extraction" if task == "question-answering" else task, seed=seed,
-                        problem_type=problem_type)
+                        problem_type=problem_type, use_crf=use_crf)
     model.weights_source = "random-init"  # what the run's provenance record reports
     if os.path.isdir(name_or_path):
         sd = read_checkpoint(name_or_path)
@@ -127,6 +129,9 @@ def from_pretrained(name_or_path: str, task: str = "sequence-classification", nu
             model.weights_source = os.path.abspath(name_or_path)
             if info["missing"]:
                 logger.info("Some weights were newly initialized: %s", info["missing"])
+            if any(k.startswith("crf.") for k in info["missing"]):
+                logger.warning("%s holds no CRF parameters (a plain token-classification checkpoint): the start, end "
+                               "and transition scores are freshly initialised", name_or_path)
         else:
             logger.warning("%s has no weights file; using random init", name_or_path)
     else:

@@ -408,6 +408,40 @@ def token_head(h2d, w, b, labels, p: float, seed: int, label_smoothing: float = 
     return _with_stats(loss, stats), logits
 
 
+def token_crf_head(h2d, w, b, labels, cu, start, end, trans, p: float, seed: int, keep=None, max_seqlen=None):
+    """Token-classification head with a linear-chain CRF (``--crf true``, BERT-CRF) on every row of ``h2d`` [R, H]: the
+    emissions are :func:`token_head`'s ``logits = dropout(h) Wᵀ + b`` [R, C]; over the sequences ``cu[b] .. cu[b+1]-1``
+    of the flat buffer (padded batches: ``cu = arange(B+1)·S``) the loss is the negative log-likelihood of the gold tag
+    sequence divided by the number of labelled rows, and the prediction the Viterbi path. The chain of a sequence is
+    its rows with ``0 <= label < C``; the definition is ``reference.crf_loss`` / ``crf_decode``. ``start`` / ``end``
+    [C] and ``trans`` [C, C] are the CRF's parameters.
+
+    With ``labels`` [R] returns ``(loss, logits)`` with the fp32 {mean loss, Viterbi hits, chain rows, loss sum} on
+    ``loss._hsd_stats``, the hits on ``loss._hsd_correct`` and the Viterbi tags (int32 [R], -1 off the chain) on
+    ``loss._hsd_pred``. Without labels returns ``(logits, pred)``: the tags over the rows with ``keep [R] != 0``
+    (``None``: every row). ``max_seqlen``: the longest sequence as a host int, if the caller knows it (the reference
+    path reads it from ``cu`` otherwise; the kernels never need it).
+
+    bf16 GPU tensors within ``hip.crf_head_ok`` (H % 8 == 0, H <= 1024, 2 <= C <= 16, any sequence length) run the
+    kernels of csrc/kernels/crf_head.hip after token_head.hip's classifier pass, unless ``HSD_TOKEN_HEAD=composed``.
+    Everything else (CPU tensors, fp32 GPU tensors, ``HSD_OPS=torch``, C > 16, differentiable emissions without labels)
+    runs ``reference.token_crf`` with the same seed and so the same mask. Nothing reads a device value on the host when
+    ``max_seqlen`` is given."""
+    lab = labels.reshape(-1) if labels is not None else None
+    needs_grad = torch.is_grad_enabled() and (h2d.requires_grad or w.requires_grad or b.requires_grad)
+    if _hip(h2d) and TOKEN_HEAD_FUSED and _hipmod().crf_head_ok(h2d, w, cu, start, end, trans) \
+            and not (lab is None and needs_grad):
+        if lab is None:
+            return _hipmod().token_crf_decode(h2d, w, b, keep, cu, start, end, trans, p, seed)
+        loss, logits, stats, pred = _hipmod().token_crf(h2d, w, b, lab, cu, start, end, trans, p, seed)
+    else:
+        if lab is None:
+            return _ref.token_crf_decode(h2d, w, b, keep, cu, start, end, trans, p, seed, True, max_seqlen)
+        loss, logits, stats, pred = _ref.token_crf(h2d, w, b, lab, cu, start, end, trans, p, seed, True, max_seqlen)
+    loss._hsd_stats, loss._hsd_correct, loss._hsd_pred = stats, stats[1], pred
+    return loss, logits
+
+
 def qa_head(h2d, w, b, positions, cu, row_mask, p: float, seed: int, max_answer_length: int = 30, max_seqlen=None):
     """Question-answering (span extraction) head on every row of ``h2d`` [R, H]: ``logits = dropout(h) Wᵀ + b``
     [R, 2] (start, end) and the span loss over the sequences ``cu[b] .. cu[b+1]-1`` of the flat buffer, with

@@ -1825,6 +1825,99 @@ def qa_head_logits(h2d, w, b, cu, row_mask, p, seed, max_answer_length):
     return logits, pred
 
 
+# ------------------------------------------------------------------------------------------ linear-chain CRF head
+def crf_head_ok(h2d, w, cu, start, end, trans) -> bool:
+    """What the fused CRF head takes: the token head's rows and classifier (``token_head_ok``: bf16 [R, H], H % 8 == 0,
+    H <= 1024, 2 <= C <= 16), offsets on the device and CRF parameters of C tags on the device, fp32 or bf16 (the
+    kernels compute in fp32: a bf16 run's compute copies are widened once per call)."""
+    C = w.shape[0]
+    return (token_head_ok(h2d, w) and h2d.shape[0] < (1 << 30) and cu.is_cuda and cu.numel() >= 2
+            and all(t.is_cuda and t.dtype in (torch.float32, torch.bfloat16) for t in (start, end, trans))
+            and tuple(start.shape) == (C,) and tuple(end.shape) == (C,) and tuple(trans.shape) == (C, C))
+
+
+def _crf_theta(start, end, trans):
+    """{trans, start, end} as the one packed fp32 vector the kernels read."""
+    return torch.cat([trans.detach().reshape(-1), start.detach(), end.detach()]).float()
+
+
+def _crf_workspace(R, extra, device):
+    """(alpha fp32 [R·16], back-pointers u8 [R·16], ``extra`` more floats) carved from the shared workspace."""
+    ws = _workspace(20 * R + extra, device)
+    return ws[:16 * R], ws[16 * R:20 * R].view(torch.uint8), ws[20 * R:20 * R + extra]
+
+
+class _TokenCRF(torch.autograd.Function):
+    """Every row of h -> emissions (token_head.hip, logits-only) -> crf_fwd_kernel (alpha, Viterbi, back-trace, gold
+    score) [-> crf_marg_kernel (beta, g0, parameter-gradient slabs) when a gradient is needed] -> crf_reduce_kernel
+    (crf_head.hip). Backward: the token head's backward from the saved gradient table g0 (tok_bwd_kernel<true>) and the
+    three parameter gradients times dloss / max(N, 1) added into main_grad."""
+
+    @staticmethod
+    def forward(ctx, h2d, w, b, labels, cu, start, end, trans, p, seed):
+        x = h2d.contiguous()
+        R, C = x.shape[0], w.shape[0]
+        B = cu.numel() - 1
+        P = C * C + 2 * C
+        cu32 = (cu if cu.dtype == torch.int32 else cu.to(torch.int32)).contiguous()
+        lab = labels.contiguous().long()
+        logits = _token_logits(x, w.contiguous(), b.contiguous(), p, seed)
+        theta = _crf_theta(start, end, trans)
+        needs_grad = any(ctx.needs_input_grad[i] for i in (0, 1, 2, 5, 6, 7))
+        alpha, bp, slab = _crf_workspace(R, B * P if needs_grad else 0, x.device)
+        pred = torch.empty(R, dtype=torch.int32, device=x.device)
+        rec = torch.empty(4 * B, dtype=torch.float32, device=x.device)
+        out = torch.empty(4 + 16 + P, dtype=torch.float32, device=x.device)  # stats, cnt, dtheta
+        stats, cnt, dtheta = out[:4], out[4:20], out[20:]
+        _C.crf_forward(logits, cu32, lab, None, theta, alpha, bp, pred, rec)
+        g0 = None
+        if needs_grad:
+            g0 = torch.empty((R, C), dtype=torch.float32, device=x.device)
+            _C.crf_marginals(logits, cu32, lab, theta, alpha, g0, slab)
+        _C.crf_reduce(rec, slab if needs_grad else None, B, C, stats, cnt, dtheta)
+        ctx.save_for_backward(x, w, b, start, end, trans, g0, cnt, dtheta)
+        ctx.cfg = (float(p), seed)
+        ctx.mark_non_differentiable(logits, stats, pred)
+        ctx.set_materialize_grads(False)
+        return stats[0], logits, stats, pred
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits, _dstats, _dpred):
+        x, w, b, start, end, trans, g0, cnt, dtheta = ctx.saved_tensors
+        p, seed = ctx.cfg
+        C = w.shape[0]
+        g_w, g_b, dl, dh, part = _token_bwd_args(ctx, x, w, b, dloss)
+        # g = g0 · dloss / max(N, 1), N = cnt[c] for every tag c
+        _C.token_head_bwd_given(x, w.contiguous(), g0, cnt, 1.0, dl, dh, part, g_w.buf.view(-1), g_b.buf.view(-1),
+                                p, _s64(seed))
+        scale = dl / cnt[:1].clamp(min=1.0)
+        grads = []
+        for prm, lo, hi in ((start, C * C, C * C + C), (end, C * C + C, C * C + 2 * C), (trans, 0, C * C)):
+            g = _Grad(prm)
+            g.buf.view(-1).addcmul_(dtheta[lo:hi], scale)
+            grads.append(g.done())
+        return (dh, g_w.done(), g_b.done(), None, None, *grads, None, None)
+
+
+def token_crf(h2d, w, b, labels, cu, start, end, trans, p, seed):
+    """(loss, logits, stats, pred) of the fused CRF head (labels [R] required); stats = fp32 {mean loss, Viterbi hits,
+    chain rows, loss sum}, pred int32 [R] (-1 off the chain)."""
+    return _TokenCRF.apply(h2d, w, b, labels, cu, start, end, trans, p, seed)
+
+
+def token_crf_decode(h2d, w, b, keep, cu, start, end, trans, p, seed):
+    """(logits, pred) of the fused CRF head without labels (inference: no autograd): the Viterbi tags over the rows with
+    ``keep != 0`` (None: every row of a sequence)."""
+    x = h2d.detach().contiguous()
+    cu32, kp = _span_args(x, cu, keep)
+    logits = _token_logits(x, w.detach().contiguous(), b.detach().contiguous(), p, seed)
+    _, bp, _ = _crf_workspace(x.shape[0], 0, x.device)
+    pred = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
+    none = torch.empty(0, dtype=torch.float32, device=x.device)
+    _C.crf_forward(logits, cu32, None, kp, _crf_theta(start, end, trans), none, bp, pred, none)
+    return logits, pred
+
+
 # ------------------------------------------------------------------------------------------ sentence-embedding head
 def sent_head_ok(h2d, cu) -> bool:
     """What csrc/kernels/sent_head.hip takes: bf16 rows ``[R, H]`` with H % 8 == 0 and H <= 1024, offsets on the

@@ -396,6 +396,118 @@ def qa_head(h2d, w, b, positions, cu, row_mask, p: float, seed: int, max_answer_
     return loss, logits, stats, pred
 
 
+def _crf_frames(emissions, chain, cu, max_seqlen):
+    """The flat rows as ``[B, L]`` frames: (row index ``[B, L]``, ``on [B, L]`` = the frame is a chain row of its
+    sequence, emissions ``[B, L, C]`` in fp32, or fp64 for fp64 input). ``chain [R]`` bool; rows outside every sequence
+    belong to no frame. ``max_seqlen``: the longest sequence as a host int (read from ``cu`` when it is not given)."""
+    R = emissions.shape[0]
+    cul = cu.long()
+    if max_seqlen is None:
+        max_seqlen = int((cul[1:] - cul[:-1]).max())
+    L = max(1, int(max_seqlen))
+    start = cul[:-1].clamp(0, R)
+    stop = torch.maximum(cul[1:].clamp(0, R), start)
+    row = start[:, None] + torch.arange(L, device=cu.device)[None, :]
+    inside = row < stop[:, None]
+    row = row.clamp(max=R - 1)
+    x = emissions if emissions.dtype == torch.float64 else emissions.float()
+    return row, inside & chain[row], x[row]
+
+
+def crf_decode(emissions, chain, cu, start, end, trans, max_seqlen: Optional[int] = None):
+    """Viterbi path of a linear-chain CRF over the chain rows (``chain [R]`` bool) of every sequence
+    ``cu[b] .. cu[b+1]-1`` of ``emissions [R, C]``: ``pred [R]`` int32, the tag on a chain row and -1 elsewhere. The
+    path maximises ``start[y_1] + Σ_k emissions[t_k][y_k] + Σ_{k>1} trans[y_{k-1}][y_k] + end[y_n]``; ties go to the
+    smaller tag (first maximum). No host read beyond ``max_seqlen`` when it is not given."""
+    R, C = emissions.shape
+    row, on, x = _crf_frames(emissions.detach(), chain, cu, max_seqlen)
+    B, L = on.shape
+    st, en, tr = (t.detach().to(x.dtype) for t in (start, end, trans))
+    delta = st.expand(B, C).clone()
+    begun = torch.zeros(B, dtype=torch.bool, device=x.device)
+    back = []
+    for t in range(L):
+        cand, arg = (delta[:, :, None] + tr[None]).max(dim=1)  # over the previous tag: the first maximum
+        new = torch.where(begun[:, None], cand, st[None]) + x[:, t]
+        delta = torch.where(on[:, t, None], new, delta)
+        back.append(arg)
+        begun = begun | on[:, t]
+    cur = (delta + en[None]).argmax(dim=1)
+    pred = torch.full((R + 1,), -1, dtype=torch.int64, device=x.device)
+    for t in range(L - 1, -1, -1):
+        slot = torch.where(on[:, t], row[:, t], torch.full_like(row[:, t], R))  # the spare slot takes the other frames
+        pred = pred.scatter(0, slot, cur)
+        cur = torch.where(on[:, t], back[t].gather(1, cur[:, None])[:, 0], cur)
+    pred[R] = -1
+    return pred[:R].to(torch.int32)
+
+
+def crf_loss(emissions, labels, cu, start, end, trans, max_seqlen: Optional[int] = None):
+    """Linear-chain CRF negative log-likelihood (BERT-CRF; pytorch-crf's ``reduction="token_mean"`` on a batch whose
+    every row is labelled). The CHAIN of sequence ``b`` is its rows ``cu[b] <= r < cu[b+1]`` with ``0 <= labels[r] < C``,
+    in order ``t_1 .. t_n`` with gold tags ``y_k``; every other row ([CLS], [SEP], padding, subword continuations, a
+    packed buffer's dead rows) is stepped over and gets an exactly zero gradient; an empty chain contributes nothing.
+
+    ``score(y) = start[y_1] + Σ_k emissions[t_k][y_k] + Σ_{k>1} trans[y_{k-1}][y_k] + end[y_n]`` (``trans[i][j]``: tag
+    ``i`` followed by tag ``j``), ``logZ`` = log-sum-exp of ``score`` over all ``C^n`` taggings (forward algorithm),
+    ``loss = Σ_b (logZ_b - score_b(gold)) / max(N, 1)`` with ``N`` the chain rows of the batch.
+
+    Returns ``(loss, stats, pred)``: ``stats`` fp32 {mean loss, hits, N, loss sum} with hits = Viterbi tags equal to the
+    label, ``pred`` from :func:`crf_decode`. fp32 arithmetic (fp64 for fp64 emissions)."""
+    R, C = emissions.shape
+    lab = labels.reshape(-1).long()
+    chain = (lab >= 0) & (lab < C)
+    row, on, x = _crf_frames(emissions, chain, cu, max_seqlen)
+    B, L = on.shape
+    y = lab[row].clamp(0, C - 1)
+    st, en, tr = (t.to(x.dtype) for t in (start, end, trans))
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
+    alpha = st.expand(B, C)
+    gold = torch.zeros(B, dtype=x.dtype, device=x.device)
+    begun = torch.zeros(B, dtype=torch.bool, device=x.device)
+    prev = torch.zeros(B, dtype=torch.long, device=x.device)
+    for t in range(L):
+        o, yt = on[:, t], y[:, t]
+        new = torch.where(begun[:, None], torch.logsumexp(alpha[:, :, None] + tr[None], dim=1), st[None]) + x[:, t]
+        alpha = torch.where(o[:, None], new, alpha)
+        step = torch.where(begun, tr[prev, yt], st[yt]) + x[:, t].gather(1, yt[:, None])[:, 0]
+        gold = gold + torch.where(o, step, zero)
+        prev = torch.where(o, yt, prev)
+        begun = begun | o
+    nll = torch.where(begun, torch.logsumexp(alpha + en[None], dim=1) - gold - en[prev], zero)
+    lsum = nll.sum()
+    n = on.sum().to(torch.float32)
+    loss = lsum / n.clamp(min=1.0).to(x.dtype)
+    with torch.no_grad():
+        pred = crf_decode(emissions, chain, cu, start, end, trans, L)
+        hits = (pred.long() == lab).sum().to(torch.float32)  # pred is -1 off the chain, a chain label is >= 0
+        stats = torch.stack([loss.detach().float(), hits, n, lsum.detach().float()])
+    return loss, stats, pred
+
+
+def token_crf(h2d, w, b, labels, cu, start, end, trans, p: float, seed: int, training: bool = True,
+              max_seqlen: Optional[int] = None):
+    """Token-classification head with a linear-chain CRF on top (``--crf true``): the emissions are the token head's
+    ``logits = dropout(h) Wᵀ + b`` [R, C] (the same dropout site as :func:`token_head`, in the input dtype), the loss is
+    :func:`crf_loss` of them. With ``labels`` [R] returns ``(loss, logits, stats, pred)``, without them the logits."""
+    logits = F.linear(dropout(h2d, p, seed, training), w, b)
+    if labels is None:
+        return logits
+    loss, stats, pred = crf_loss(logits, labels, cu, start, end, trans, max_seqlen)
+    return loss, logits, stats, pred
+
+
+def token_crf_decode(h2d, w, b, keep, cu, start, end, trans, p: float, seed: int, training: bool = True,
+                     max_seqlen: Optional[int] = None):
+    """``(logits, pred)`` without labels: the Viterbi tags over the rows with ``keep [R] != 0`` (``None``: every row of a
+    sequence)."""
+    logits = F.linear(dropout(h2d, p, seed, training), w, b)
+    chain = torch.ones(logits.shape[0], dtype=torch.bool, device=logits.device)
+    if keep is not None:
+        chain = keep.reshape(-1).ne(0)
+    return logits, crf_decode(logits, chain, cu, start, end, trans, max_seqlen)
+
+
 def pool_normalize(h2d, cu, row_mask):
     """Masked mean pooling + L2 normalisation of the ``n = cu.numel() - 1`` sequences of the flat ``h2d [R, H]``
     (sentence-transformers ``Pooling(mean)`` + ``Normalize``): ``m_s = Σ_r w_r h_r / max(Σ_r w_r, 1)`` over the rows

@@ -220,6 +220,19 @@ def _label_smoothing(args, task: str, ptype) -> float:
     return eps
 
 
+def check_crf(args) -> bool:
+    """``--crf`` of the run, refused where there is no per-token tag sequence to model or the loss is smoothed."""
+    crf = bool(getattr(args, "crf", False))
+    task = getattr(args, "task", "sequence-classification")
+    smoothing = float(getattr(args, "label_smoothing_factor", 0.0) or 0.0)
+    if crf and task != "token-classification":
+        raise ValueError(f"--crf true puts a linear-chain CRF on the token-classification head; --task {task} has none")
+    if crf and smoothing > 0.0:
+        raise ValueError("--label_smoothing_factor smooths a per-token cross-entropy; --crf true trains the likelihood "
+                         "of the whole tag sequence, which it does not apply to")
+    return crf
+
+
 def _lr_group_flags(args):
     """``(--layerwise_lr_decay, --head_lr_multiplier)`` of the run, refused outside (0, 1] and finite > 0."""
     return lr_groups.validate(getattr(args, "layerwise_lr_decay", 1.0), getattr(args, "head_lr_multiplier", 1.0))
@@ -287,6 +300,10 @@ def _provenance(args, model, rank: int, n_train: int, n_eval: int, batch_plan=No
                           "synthetic tagging corpus (tag = f(token, left neighbour), ragged lengths, ~25 % of the "
                           "real tokens ignored)")
         info["metric"] = "loss and accuracy over the labelled tokens (not entity-level F1)"
+        if getattr(model.cfg, "use_crf", False):
+            info["crf"] = True
+            info["metric"] = ("linear-chain CRF: sequence negative log-likelihood per labelled token, accuracy of the "
+                              "Viterbi path over the labelled tokens (not entity-level F1)")
         logger.info("token-classification corpus: %s; %d labels", info["corpus"], info["num_labels"])
     if getattr(args, "task", "sequence-classification") == "question-answering":
         info["task"] = "question-answering"
@@ -385,6 +402,7 @@ def build(args, mode: str):
     if ptype in ("regression", "multi_label_classification") and args.dataset in ("imdb", "sst2"):
         raise ValueError(_PTYPE_DATASETS.format(ptype, args.dataset))
     smoothing = _label_smoothing(args, task, ptype)
+    crf = check_crf(args)
     _lr_group_flags(args)
     ema_d, ema_warm = _ema_flags(args)
     tags = _conll_tags(args)
@@ -393,7 +411,12 @@ def build(args, mode: str):
             logger.info("--dataset conll: %d tags %s; --num_labels %d -> %d", len(tags), tags, args.num_labels, len(tags))
         args.num_labels = len(tags)
     model = from_pretrained(args.model_name_or_path or "bert-base-uncased", task=task, num_labels=args.num_labels,
-                            seed=args.seed, problem_type=ptype)
+                            seed=args.seed, problem_type=ptype, use_crf=True if crf else None)
+    if task == "token-classification" and model.cfg.use_crf:
+        if smoothing > 0.0:  # a saved CRF directory without the flag
+            raise ValueError("--label_smoothing_factor does not apply to a CRF model (config.json use_crf)")
+        logger.info("linear-chain CRF head over %d tags: the loss is the sequence likelihood over the labelled tokens, "
+                    "accuracy that of the Viterbi path", model.cfg.num_labels)
     if model.cfg.model_type == "mpnet" and dtype_name == "fp8":
         raise ValueError("--dtype fp8 is not supported for mpnet models (the relative-position-bias attention kernels "
                          "are bf16; --dtype bf16 or fp32)")

@@ -182,6 +182,11 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
                         "label_smoothing=): the target becomes (1-eps)*onehot + eps/num_classes, in fit and in evaluate. "
                         "0 <= eps < 1. For single-label sequence-classification, token-classification and masked-lm; "
                         "question-answering and --problem_type regression / multi_label_classification refuse it")
+    g.add_argument("--crf", type=str2bool, default=False,
+                   help="token-classification only: a linear-chain CRF over the per-token scores (BERT-CRF). Training "
+                        "maximises the likelihood of the whole tag sequence over each sequence's labelled tokens, "
+                        "evaluation and accuracy use the Viterbi path. Refused for the other tasks and together with "
+                        "--label_smoothing_factor > 0; at most 16 labels run the fused kernels")
     g.add_argument("--max_answer_length", type=int, default=30,
                    help="question-answering: the longest span (in tokens) the best-span search returns")
     g.add_argument("--doc_stride", type=int, default=128,
