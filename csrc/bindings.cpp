@@ -1706,6 +1706,38 @@ void token_head_wide_bwd(torch::Tensor h, torch::Tensor W, torch::Tensor logits,
                                   (int)H, (int)C, p, (uint64_t)seed, cur_stream(), eps);
 }
 
+// the wide head's backward from a given gradient table (the CRF head of crf_head_wide.hip): the arguments of
+// token_head_bwd_given
+void token_head_wide_bwd_given(torch::Tensor h, torch::Tensor W, torch::Tensor g0, torch::Tensor cnt, double gmul,
+                               torch::Tensor dloss, c10::optional<torch::Tensor> dh, torch::Tensor part,
+                               torch::Tensor dW, torch::Tensor db, double p, int64_t seed) {
+  TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() && h.scalar_type() == torch::kBFloat16,
+              "token_head_wide h");
+  const int64_t R = h.size(0), H = h.size(1), C = W.size(0);
+  TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 16 && H % 8 == 0 && H >= 8 && H <= 1024 && C >= 17 && C <= 64,
+              "token_head_wide: 1 <= rows < 2^31, H % 8 == 0, H <= 1024, 17 <= classes <= 64");
+  check_bf16_2d(W, C, H, "token_head_wide W");
+  check_f32(g0, "g0");
+  check_f32(cnt, "cnt");
+  check_f32(dloss, "dloss");
+  check_f32(part, "part");
+  check_f32(dW, "dW");
+  check_f32(db, "db");
+  TORCH_CHECK(g0.numel() == R * C && (uintptr_t)g0.data_ptr() % 16 == 0 && cnt.numel() >= C && dloss.numel() >= 1,
+              "token_head_wide g0 (16-byte aligned) / cnt / dloss");
+  TORCH_CHECK(part.numel() >= (int64_t)hsd::token_head_wide_bwd_blocks((int)R, (int)H) * (C * H + C),
+              "token_head_wide workspace");
+  TORCH_CHECK(dW.numel() == C * H && db.numel() == C, "token_head_wide grads");
+  hsd::bf16_t* dhp = nullptr;
+  if (dh.has_value()) {
+    check_bf16_2d(*dh, R, H, "dh");
+    dhp = BF(*dh);
+  }
+  hsd::launch_token_head_wide_bwd_given(CBF(h), CBF(W), g0.data_ptr<float>(), cnt.data_ptr<float>(), (float)gmul,
+                                        dloss.data_ptr<float>(), dhp, part.data_ptr<float>(), dW.data_ptr<float>(),
+                                        db.data_ptr<float>(), (int)R, (int)H, (int)C, p, (uint64_t)seed, cur_stream());
+}
+
 int64_t token_head_wide_fwd_blocks(int64_t R) { return hsd::token_head_wide_fwd_blocks((int)R); }
 int64_t token_head_wide_bwd_blocks(int64_t R, int64_t H) { return hsd::token_head_wide_bwd_blocks((int)R, (int)H); }
 
@@ -1746,17 +1778,22 @@ void span_ce(torch::Tensor logits, torch::Tensor cu, c10::optional<torch::Tensor
                       (int)B, cur_stream());
 }
 
-// ---- linear-chain CRF head (crf_head.hip). em [R][C] bf16 (2 <= C <= 16); cu int32 [B+1]; theta fp32 [C·C + 2C] =
-// {trans, start, end}; ws_alpha fp32 [R][16]; ws_bp u8 [R][16]
+// ---- linear-chain CRF head (crf_head.hip). em [R][C] bf16 (2 <= C <= 16; 17 .. 64: the crf_wide_* entries below); cu
+// int32 [B+1]; theta fp32 [C·C + 2C] = {trans, start, end}; ws_alpha fp32 [R][16]; ws_bp u8 [R][16]
 static void crf_check(const torch::Tensor& em, const torch::Tensor& cu, const torch::Tensor& theta, int64_t* R,
-                      int64_t* B, int64_t* C) {
+                      int64_t* B, int64_t* C, bool wide = false) {
   TORCH_CHECK(em.is_cuda() && em.dim() == 2 && em.is_contiguous() && em.scalar_type() == torch::kBFloat16,
               "crf emissions [R][C] bf16");
   *R = em.size(0);
   *C = em.size(1);
   *B = cu.numel() - 1;
-  TORCH_CHECK(*R >= 1 && *R < ((int64_t)1 << 30) && *B >= 1 && *B < ((int64_t)1 << 30) && *C >= 2 && *C <= 16,
-              "crf: 1 <= rows < 2^30, at least one sequence, 2 <= tags <= 16");
+  TORCH_CHECK(*R >= 1 && *R < ((int64_t)1 << 30) && *B >= 1 && *B < ((int64_t)1 << 30), "crf: 1 <= rows < 2^30, at "
+              "least one sequence");
+  if (wide) {
+    TORCH_CHECK(*C >= 17 && *C <= 64, "crf_wide: 17 <= tags <= 64");
+  } else {
+    TORCH_CHECK(*C >= 2 && *C <= 16, "crf: 2 <= tags <= 16");
+  }
   TORCH_CHECK(cu.is_cuda() && cu.is_contiguous() && cu.scalar_type() == torch::kInt32, "crf cu int32 [B+1]");
   check_f32(theta, "crf theta");
   TORCH_CHECK(theta.numel() == *C * *C + 2 * *C, "crf theta fp32 [C*C + 2C]");
@@ -1826,6 +1863,73 @@ void crf_reduce(torch::Tensor rec, c10::optional<torch::Tensor> slab, int64_t B,
   }
   hsd::launch_crf_reduce(rec.data_ptr<float>(), sp, (int)B, (int)C, stats.data_ptr<float>(), cnt.data_ptr<float>(), dp,
                          cur_stream());
+}
+
+// ---- the same head for 17 <= C <= 64 (crf_head_wide.hip): the arguments of the three entries above with the row
+// stride CP = 16·ceil(C / 16) in place of 16 (ws_alpha fp32 [R][CP], ws_bp u8 [R][CP]) and cnt fp32 [64]
+void crf_wide_forward(torch::Tensor em, torch::Tensor cu, c10::optional<torch::Tensor> labels,
+                      c10::optional<torch::Tensor> keep, torch::Tensor theta, torch::Tensor ws_alpha,
+                      torch::Tensor ws_bp, torch::Tensor pred, torch::Tensor rec) {
+  int64_t R, B, C;
+  crf_check(em, cu, theta, &R, &B, &C, true);
+  const int64_t CP = 16 * ((C + 15) / 16);
+  const int64_t* lab = crf_rows_i64(labels, R, "crf labels int64 [R]");
+  const int64_t* kp = crf_rows_i64(keep, R, "crf keep int64 [R]");
+  TORCH_CHECK(ws_bp.is_cuda() && ws_bp.is_contiguous() && ws_bp.scalar_type() == torch::kUInt8 &&
+              ws_bp.numel() >= CP * R && (uintptr_t)ws_bp.data_ptr() % 16 == 0,
+              "crf_wide ws_bp u8 [R][16*ceil(C/16)], 16-byte aligned");
+  TORCH_CHECK(pred.is_cuda() && pred.is_contiguous() && pred.scalar_type() == torch::kInt32 && pred.numel() == R,
+              "crf pred int32 [R]");
+  float *wa = nullptr, *rp = nullptr;
+  if (lab != nullptr) {
+    check_f32(ws_alpha, "crf ws_alpha");
+    check_f32(rec, "crf rec");
+    TORCH_CHECK(ws_alpha.numel() >= CP * R && (uintptr_t)ws_alpha.data_ptr() % 16 == 0 && rec.numel() >= 4 * B &&
+                (uintptr_t)rec.data_ptr() % 16 == 0,
+                "crf_wide ws_alpha fp32 [R][16*ceil(C/16)] / rec fp32 [B][4], 16-byte aligned");
+    wa = ws_alpha.data_ptr<float>();
+    rp = rec.data_ptr<float>();
+  }
+  hsd::launch_crf_wide_forward(CBF(em), cu.data_ptr<int>(), lab, kp, theta.data_ptr<float>(), wa,
+                               ws_bp.data_ptr<uint8_t>(), pred.data_ptr<int>(), rp, (int)R, (int)B, (int)C,
+                               cur_stream());
+}
+
+void crf_wide_marginals(torch::Tensor em, torch::Tensor cu, torch::Tensor labels, torch::Tensor theta,
+                        torch::Tensor ws_alpha, torch::Tensor g0, torch::Tensor slab) {
+  int64_t R, B, C;
+  crf_check(em, cu, theta, &R, &B, &C, true);
+  const int64_t CP = 16 * ((C + 15) / 16);
+  const int64_t* lab = head_labels(labels, R);
+  check_f32(ws_alpha, "crf ws_alpha");
+  check_f32(g0, "crf g0");
+  check_f32(slab, "crf slab");
+  TORCH_CHECK(ws_alpha.numel() >= CP * R && (uintptr_t)ws_alpha.data_ptr() % 16 == 0 && g0.numel() == R * C &&
+              slab.numel() >= B * (C * C + 2 * C), "crf_wide ws_alpha / g0 / slab");
+  hsd::launch_crf_wide_marginals(CBF(em), cu.data_ptr<int>(), lab, theta.data_ptr<float>(),
+                                 ws_alpha.data_ptr<float>(), g0.data_ptr<float>(), slab.data_ptr<float>(), (int)R,
+                                 (int)B, (int)C, cur_stream());
+}
+
+void crf_wide_reduce(torch::Tensor rec, c10::optional<torch::Tensor> slab, int64_t B, int64_t C, torch::Tensor stats,
+                     torch::Tensor cnt, torch::Tensor dtheta) {
+  check_f32(rec, "crf rec");
+  check_f32(stats, "crf stats");
+  check_f32(cnt, "crf cnt");
+  TORCH_CHECK(B >= 1 && B < ((int64_t)1 << 30) && C >= 17 && C <= 64 && rec.numel() >= 4 * B &&
+              (uintptr_t)rec.data_ptr() % 16 == 0 && stats.numel() >= 4 && cnt.numel() >= 64,
+              "crf_wide rec / stats / cnt");
+  const float* sp = nullptr;
+  float* dp = nullptr;
+  if (slab.has_value()) {
+    check_f32(*slab, "crf slab");
+    check_f32(dtheta, "crf dtheta");
+    TORCH_CHECK(slab->numel() >= B * (C * C + 2 * C) && dtheta.numel() == C * C + 2 * C, "crf_wide slab / dtheta");
+    sp = slab->data_ptr<float>();
+    dp = dtheta.data_ptr<float>();
+  }
+  hsd::launch_crf_wide_reduce(rec.data_ptr<float>(), sp, (int)B, (int)C, stats.data_ptr<float>(),
+                              cnt.data_ptr<float>(), dp, cur_stream());
 }
 
 // ---- sentence-embedding head (sent_head.hip). h [R][H] bf16, cu int32 [n+1], mask int64 [R] or none; e fp32 [n][H],
@@ -2194,6 +2298,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("crf_forward", &crf_forward);
   m.def("crf_marginals", &crf_marginals);
   m.def("crf_reduce", &crf_reduce);
+  m.def("crf_wide_forward", &crf_wide_forward);
+  m.def("crf_wide_marginals", &crf_wide_marginals);
+  m.def("crf_wide_reduce", &crf_wide_reduce);
+  m.def("token_head_wide_bwd_given", &token_head_wide_bwd_given);
   m.def("sent_pool_fwd", &sent_pool_fwd);
   m.def("sent_pool_bwd", &sent_pool_bwd);
   m.def("sent_pool_chunks", [](int64_t max_seqlen) { return (int64_t)hsd::sent_pool_chunks((int)max_seqlen); });

@@ -172,8 +172,8 @@ void launch_token_head_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* logit
 void launch_token_head_bwd_given(const bf16_t* h, const bf16_t* W, const float* g0, const float* cnt, float gmul,
                                  const float* dloss, bf16_t* dh, float* part, float* dW, float* db, int R, int H,
                                  int C, double p, uint64_t seed, hipStream_t st);
-// token_head_wide.hip: the same head for 17 <= C <= 64 (same arguments and semantics; no given-gradient entry). The
-// forward takes token_head_wide_fwd_lds(H, C) bytes of dynamic LDS (up to 132 KB: the device must allow it per
+// token_head_wide.hip: the same head for 17 <= C <= 64 (same arguments and semantics, the given-gradient entry
+// included: cnt fp32 [C], which the wide CRF reducer fills). The forward takes token_head_wide_fwd_lds(H, C) bytes of dynamic LDS (up to 132 KB: the device must allow it per
 // workgroup); the backward writes token_head_wide_bwd_blocks(R, H) slabs of C·H + C.
 int token_head_wide_fwd_blocks(int R);
 int token_head_wide_bwd_blocks(int R, int H);
@@ -185,6 +185,9 @@ void launch_token_head_wide_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* 
                                 const float* stats, const float* dloss, bf16_t* dh, float* part, float* dW, float* db,
                                 int R, int H, int C, double p, uint64_t seed, hipStream_t st,
                                 float label_smoothing = 0.0f);
+void launch_token_head_wide_bwd_given(const bf16_t* h, const bf16_t* W, const float* g0, const float* cnt, float gmul,
+                                      const float* dloss, bf16_t* dh, float* part, float* dW, float* db, int R, int H,
+                                      int C, double p, uint64_t seed, hipStream_t st);
 // qa_head.hip: span-extraction loss of --task question-answering on logits [R][2] bf16. One workgroup per sequence
 // (rows cu[b] .. cu[b+1]-1, at most 1,024; mask int64 [R] optional), then the stats reducer. pos int64 [B][2] may be
 // null (pred only: rec, g0 and stats untouched). rec fp32 [B][8], pred int32 [B][2], g0 fp32 [R][2], stats fp32 [8].
@@ -203,6 +206,16 @@ void launch_crf_marginals(const bf16_t* em, const int* cu, const int64_t* labels
                           const float* ws_alpha, float* g0, float* slab, int R, int B, int C, hipStream_t st);
 void launch_crf_reduce(const float* rec, const float* slab, int B, int C, float* stats, float* cnt, float* dtheta,
                        hipStream_t st);
+// crf_head_wide.hip: the same head for 17 <= C <= 64, one workgroup of ng = ceil(C / 16) waves per sequence. The
+// arguments of the three launches above with the row stride 16·ng in place of 16 (ws_alpha fp32 [R][16·ng], ws_bp u8
+// [R][16·ng]) and cnt fp32 [64].
+void launch_crf_wide_forward(const bf16_t* em, const int* cu, const int64_t* labels, const int64_t* keep,
+                             const float* theta, float* ws_alpha, uint8_t* ws_bp, int* pred, float* rec, int R, int B,
+                             int C, hipStream_t st);
+void launch_crf_wide_marginals(const bf16_t* em, const int* cu, const int64_t* labels, const float* theta,
+                               const float* ws_alpha, float* g0, float* slab, int R, int B, int C, hipStream_t st);
+void launch_crf_wide_reduce(const float* rec, const float* slab, int B, int C, float* stats, float* cnt, float* dtheta,
+                            hipStream_t st);
 // sent_head.hip: the head of --task sentence-embedding. h [R][H] bf16 holds n sequences (cu int32 [n+1], mask int64 [R]
 // optional); H % 8 == 0, H <= 1024, n < 65,535. maxch = sent_pool_chunks(longest sequence): rows of a sequence past
 // maxch · 128 are not read (forward) and get zeros (backward). e fp32 [n][H], aux fp32 [n][2] = {1/|mean|, live rows},

@@ -50,6 +50,8 @@
 //   tokw_fwd_kernel<true>    161 VGPRs, scratch 0, occupancy 3,              LDS 144 B static + the W image  (kSmooth)
 //   tokw_bwd_kernel<false>   247 VGPRs, scratch 0, occupancy 2 waves / SIMD, LDS 48,640 B
 //   tokw_bwd_kernel<true>    249 VGPRs, scratch 0, occupancy 2,              LDS 48,640 B                    (kSmooth)
+//   tokw_bwd_kernel<false, true> (the given-gradient entry of crf_head_wide.hip): 256 VGPRs, scratch 0, occupancy 2,
+//                            LDS 48,640 B (profiles/crf_wide/resource_usage.txt; the two above are unchanged by it)
 //   tokw_reduce_kernel        12 VGPRs, scratch 0
 // (no AGPRs in any of them)
 #include "head_common.h"
@@ -249,14 +251,21 @@ __device__ __forceinline__ void load_tile(const bf16_t* __restrict__ h, int tile
   }
 }
 
-template <bool kSmooth>
+// GIVEN = false: g from the logits and the labels. GIVEN = true (launch_token_head_wide_bwd_given: the CRF head of
+// crf_head_wide.hip): the caller's per-row gradient table g0 [R][C] fp32, g[row][c] = g0[row][c] · dloss · gmul /
+// max(cnt[c], 1); logits, labels and stats are not read, a row of zeros in g0 is an ignored row. Everything from g on
+// is the same code.
+template <bool kSmooth, bool GIVEN = false>
 __global__ __launch_bounds__(256, 2) void tokw_bwd_kernel(const bf16_t* __restrict__ h, const bf16_t* __restrict__ W,
                                                           const bf16_t* __restrict__ logits,
                                                           const int64_t* __restrict__ labels,
                                                           const float* __restrict__ stats,
                                                           const float* __restrict__ dloss, bf16_t* __restrict__ dh,
                                                           float* __restrict__ part, int R, int H, int C, int write_dh,
-                                                          DropoutParams dp, float eps) {
+                                                          DropoutParams dp, float eps,
+                                                          const float* __restrict__ g0 = nullptr,
+                                                          const float* __restrict__ cnt = nullptr, float gmul = 0.f) {
+  static_assert(!(GIVEN && kSmooth), "a given gradient table is not smoothed");
   dp = resolve_seed(dp);
   __shared__ __attribute__((aligned(16))) bf16_t Wt[CR * WT_STRIDE];
   __shared__ __attribute__((aligned(16))) bf16_t Dst[4][TR * D_STRIDE];
@@ -284,7 +293,18 @@ __global__ __launch_bounds__(256, 2) void tokw_bwd_kernel(const bf16_t* __restri
   }
   __syncthreads();
 
-  const float scale = dloss[0] / fmaxf(stats[2], 1.0f);
+  float scale = 0.f, cscale[GIVEN ? GMAX : 1][4];  // GIVEN: one factor per class 16g + 4q + j of this lane
+  if constexpr (GIVEN) {
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = 16 * g + 4 * q + j;
+        cscale[g][j] = c < C ? dloss[0] * gmul / fmaxf(cnt[c], 1.0f) : 0.f;
+      }
+  } else {
+    scale = dloss[0] / fmaxf(stats[2], 1.0f);
+  }
   const bool vec4 = (C & 3) == 0;
   // transposed-read addresses (ds_read_b64_tr_b16): lane 4a + p of a 16-lane group supplies row a, columns 4p .. 4p+3
   // of the group's 4-row block (rows 4q .. 4q+3 of the tile); lane i of the group receives column i of those rows
@@ -317,8 +337,36 @@ __global__ __launch_bounds__(256, 2) void tokw_bwd_kernel(const bf16_t* __restri
     load_tile(h, tile + gridDim.x, ntiles, R, H, c0, wave, r, q, nxt);
     const int row = tile * TR + r;
     const bool rvalid = row < R;
-    const int64_t lab = rvalid ? labels[row] : -100;
-    const bool valid = lab >= 0 && lab < C;
+    int64_t lab = -100;
+    bool valid;
+    float gr[GIVEN ? GMAX : 1][4];  // GIVEN: g0 of this lane's 4 classes per group of its row
+    if constexpr (GIVEN) {
+      valid = false;
+#pragma unroll
+      for (int g = 0; g < GMAX; ++g) {
+        const int cg = 16 * g + 4 * q;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gr[g][j] = 0.f;
+        if (g < ng && rvalid) {
+          const float* const in = g0 + (int64_t)row * C + cg;
+          if (vec4) {
+            if (cg < C) {
+              const f32x4 v = *reinterpret_cast<const f32x4*>(in);
+              gr[g][0] = v.x; gr[g][1] = v.y; gr[g][2] = v.z; gr[g][3] = v.w;
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (cg + j < C) gr[g][j] = in[j];
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) valid = valid || gr[g][j] != 0.f;
+      }
+    } else {
+      lab = rvalid ? labels[row] : -100;
+      valid = lab >= 0 && lab < C;
+    }
     if (__ballot(valid) == 0ull) {
       // every row of the tile is ignored: zeros, nothing else (the branch is wave-uniform)
       if (write_dh) {
@@ -330,42 +378,44 @@ __global__ __launch_bounds__(256, 2) void tokw_bwd_kernel(const bf16_t* __restri
       }
     } else {
       // g of this lane's 4 classes per group of its row
-      float e[GMAX][4], m = -INFINITY;
+      float e[GMAX][4], m = -INFINITY, inv = 0.f;
+      if constexpr (!GIVEN) {
 #pragma unroll
-      for (int g = 0; g < GMAX; ++g) {
-        const int cg = 16 * g + 4 * q;
+        for (int g = 0; g < GMAX; ++g) {
+          const int cg = 16 * g + 4 * q;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) e[g][j] = -INFINITY;
-        if (g < ng && rvalid) {
-          const bf16_t* const in = logits + (int64_t)row * C + cg;
-          if (vec4) {
-            if (cg < C) {
-              const u32x2 v = *reinterpret_cast<const u32x2*>(in);
-              e[g][0] = lo_bf(v.x); e[g][1] = hi_bf(v.x); e[g][2] = lo_bf(v.y); e[g][3] = hi_bf(v.y);
+          for (int j = 0; j < 4; ++j) e[g][j] = -INFINITY;
+          if (g < ng && rvalid) {
+            const bf16_t* const in = logits + (int64_t)row * C + cg;
+            if (vec4) {
+              if (cg < C) {
+                const u32x2 v = *reinterpret_cast<const u32x2*>(in);
+                e[g][0] = lo_bf(v.x); e[g][1] = hi_bf(v.x); e[g][2] = lo_bf(v.y); e[g][3] = hi_bf(v.y);
+              }
+            } else {
+#pragma unroll
+              for (int j = 0; j < 4; ++j)
+                if (cg + j < C) e[g][j] = bf2f(in[j]);
             }
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              if (cg + j < C) e[g][j] = bf2f(in[j]);
           }
-        }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) m = fmaxf(m, e[g][j]);
+          for (int j = 0; j < 4; ++j) m = fmaxf(m, e[g][j]);
+        }
+        m = fmaxf(m, __shfl_xor(m, 16, 64));
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        if (!rvalid) m = 0.f;
+        float se = 0.f;
+#pragma unroll
+        for (int g = 0; g < GMAX; ++g)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            e[g][j] = __expf(e[g][j] - m);  // exp(-inf) = 0 in the padding classes
+            se += e[g][j];
+          }
+        se += __shfl_xor(se, 16, 64);
+        se += __shfl_xor(se, 32, 64);
+        inv = 1.0f / se;
       }
-      m = fmaxf(m, __shfl_xor(m, 16, 64));
-      m = fmaxf(m, __shfl_xor(m, 32, 64));
-      if (!rvalid) m = 0.f;
-      float se = 0.f;
-#pragma unroll
-      for (int g = 0; g < GMAX; ++g)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          e[g][j] = __expf(e[g][j] - m);  // exp(-inf) = 0 in the padding classes
-          se += e[g][j];
-        }
-      se += __shfl_xor(se, 16, 64);
-      se += __shfl_xor(se, 32, 64);
-      const float inv = 1.0f / se;
       bf16x4 gb[GMAX];  // B operand of dh: [k = class 16g + 4q + j][n = row r]
 #pragma unroll
       for (int g = 0; g < GMAX; ++g) {
@@ -373,7 +423,8 @@ __global__ __launch_bounds__(256, 2) void tokw_bwd_kernel(const bf16_t* __restri
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int c = 16 * g + 4 * q + j;
-          if constexpr (kSmooth)
+          if constexpr (GIVEN) gv[j] = gr[g][j] * cscale[g][j];
+          else if constexpr (kSmooth)
             gv[j] = valid && c < C ? (e[g][j] * inv - (c == (int)lab ? 1.0f - eps : 0.f) - eps / (float)C) * scale : 0.f;
           else gv[j] = valid && c < C ? (e[g][j] * inv - (c == (int)lab ? 1.f : 0.f)) * scale : 0.f;
           accb[g][j] += gv[j];
@@ -500,6 +551,13 @@ __global__ __launch_bounds__(256) void tokw_reduce_kernel(const float* __restric
   }
 }
 
+static void launch_reduce(const float* part, int nblk, int H, int C, float* dW, float* db, hipStream_t st) {
+  const int n = C * H + C;
+  hipLaunchKernelGGL(tokw_reduce_kernel, dim3((n + RED_X - 1) / RED_X), dim3(RED_X * RED_G), 0, st, part, nblk, n,
+                     C * H, dW, db);
+  HSD_CHECK_LAUNCH();
+}
+
 // waves per forward block: the fewest of 4 / 8 / 12 with which the tiles fit FWD_MAX_BLOCKS blocks (12 beyond that)
 static int fwd_waves(int ntiles) {
   for (int w = 4; w < FWD_MAX_WAVES; w += 4)
@@ -559,10 +617,19 @@ void launch_token_head_wide_bwd(const bf16_t* h, const bf16_t* W, const bf16_t* 
     hipLaunchKernelGGL(tokw::tokw_bwd_kernel<false>, grid, dim3(256), 0, st, h, W, logits, labels, stats, dloss, dh,
                        part, R, H, C, dh != nullptr ? 1 : 0, dp, 0.f);
   HSD_CHECK_LAUNCH();
-  const int n = C * H + C;
-  hipLaunchKernelGGL(tokw::tokw_reduce_kernel, dim3((n + tokw::RED_X - 1) / tokw::RED_X),
-                     dim3(tokw::RED_X * tokw::RED_G), 0, st, (const float*)part, nblk, n, C * H, dW, db);
+  tokw::launch_reduce(part, nblk, H, C, dW, db, st);
+}
+
+void launch_token_head_wide_bwd_given(const bf16_t* h, const bf16_t* W, const float* g0, const float* cnt, float gmul,
+                                      const float* dloss, bf16_t* dh, float* part, float* dW, float* db, int R, int H,
+                                      int C, double p, uint64_t seed, hipStream_t st) {
+  const int nblk = token_head_wide_bwd_blocks(R, H);
+  const dim3 grid(nblk, (H + tokw::CR - 1) / tokw::CR);
+  hipLaunchKernelGGL((tokw::tokw_bwd_kernel<false, true>), grid, dim3(256), 0, st, h, W, (const bf16_t*)nullptr,
+                     (const int64_t*)nullptr, (const float*)nullptr, dloss, dh, part, R, H, C, dh != nullptr ? 1 : 0,
+                     make_dropout(p, seed), 0.f, g0, cnt, gmul);
   HSD_CHECK_LAUNCH();
+  tokw::launch_reduce(part, nblk, H, C, dW, db, st);
 }
 
 }  // namespace hsd

@@ -43,7 +43,7 @@ COMMON_FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wno-un
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"attention_d32.hip": NO_PACKED_FP32, "token_head_wide.hip": NO_PACKED_FP32,
               "attention32m_varlen.hip": NO_PACKED_FP32, "attention_relbias.hip": NO_PACKED_FP32,
-              "sent_head.hip": NO_PACKED_FP32, "crf_head.hip": NO_PACKED_FP32}
+              "sent_head.hip": NO_PACKED_FP32, "crf_head.hip": NO_PACKED_FP32, "crf_head_wide.hip": NO_PACKED_FP32}
 
 
 def _torch_flags():

@@ -422,9 +422,10 @@ def token_crf_head(h2d, w, b, labels, cu, start, end, trans, p: float, seed: int
     (``None``: every row). ``max_seqlen``: the longest sequence as a host int, if the caller knows it (the reference
     path reads it from ``cu`` otherwise; the kernels never need it).
 
-    bf16 GPU tensors within ``hip.crf_head_ok`` (H % 8 == 0, H <= 1024, 2 <= C <= 16, any sequence length) run the
-    kernels of csrc/kernels/crf_head.hip after token_head.hip's classifier pass, unless ``HSD_TOKEN_HEAD=composed``.
-    Everything else (CPU tensors, fp32 GPU tensors, ``HSD_OPS=torch``, C > 16, differentiable emissions without labels)
+    bf16 GPU tensors within ``hip.crf_head_ok`` (H % 8 == 0, H <= 1024, 2 <= C <= 64, any sequence length) run the
+    kernels of csrc/kernels/crf_head.hip after token_head.hip's classifier pass (C <= 16) or those of crf_head_wide.hip
+    after token_head_wide.hip's (17 <= C <= 64), unless ``HSD_TOKEN_HEAD=composed``.
+    Everything else (CPU tensors, fp32 GPU tensors, ``HSD_OPS=torch``, C > 64, differentiable emissions without labels)
     runs ``reference.token_crf`` with the same seed and so the same mask. Nothing reads a device value on the host when
     ``max_seqlen`` is given."""
     lab = labels.reshape(-1) if labels is not None else None

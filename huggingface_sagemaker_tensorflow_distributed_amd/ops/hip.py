@@ -1827,11 +1827,12 @@ def qa_head_logits(h2d, w, b, cu, row_mask, p, seed, max_answer_length):
 
 # ------------------------------------------------------------------------------------------ linear-chain CRF head
 def crf_head_ok(h2d, w, cu, start, end, trans) -> bool:
-    """What the fused CRF head takes: the token head's rows and classifier (``token_head_ok``: bf16 [R, H], H % 8 == 0,
-    H <= 1024, 2 <= C <= 16), offsets on the device and CRF parameters of C tags on the device, fp32 or bf16 (the
-    kernels compute in fp32: a bf16 run's compute copies are widened once per call)."""
+    """What the fused CRF head takes: the token head's rows and classifier (``token_head_ok`` or ``token_head_wide_ok``:
+    bf16 [R, H], H % 8 == 0, H <= 1024, 2 <= C <= 64), offsets on the device and CRF parameters of C tags on the device,
+    fp32 or bf16 (the kernels compute in fp32: a bf16 run's compute copies are widened once per call)."""
     C = w.shape[0]
-    return (token_head_ok(h2d, w) and h2d.shape[0] < (1 << 30) and cu.is_cuda and cu.numel() >= 2
+    return ((token_head_ok(h2d, w) or token_head_wide_ok(h2d, w)) and h2d.shape[0] < (1 << 30) and cu.is_cuda
+            and cu.numel() >= 2
             and all(t.is_cuda and t.dtype in (torch.float32, torch.bfloat16) for t in (start, end, trans))
             and tuple(start.shape) == (C,) and tuple(end.shape) == (C,) and tuple(trans.shape) == (C, C))
 
@@ -1841,17 +1842,29 @@ def _crf_theta(start, end, trans):
     return torch.cat([trans.detach().reshape(-1), start.detach(), end.detach()]).float()
 
 
-def _crf_workspace(R, extra, device):
-    """(alpha fp32 [R·16], back-pointers u8 [R·16], ``extra`` more floats) carved from the shared workspace."""
-    ws = _workspace(20 * R + extra, device)
-    return ws[:16 * R], ws[16 * R:20 * R].view(torch.uint8), ws[20 * R:20 * R + extra]
+def _crf_workspace(R, extra, device, cp=16):
+    """(alpha fp32 [R·cp], back-pointers u8 [R·cp], ``extra`` more floats) carved from the shared workspace; ``cp`` is
+    the padded tag count (16, or 16·ceil(C / 16) for the wide kernels)."""
+    na, nb = cp * R, cp * R // 4
+    ws = _workspace(na + nb + extra, device)
+    return ws[:na], ws[na:na + nb].view(torch.uint8), ws[na + nb:na + nb + extra]
+
+
+def _crf_kernels(C):
+    """(padded tag count, length of cnt, forward, marginals, reduce, emissions) for C tags: crf_head.hip after
+    token_head.hip up to 16 tags, crf_head_wide.hip after token_head_wide.hip for 17 .. 64."""
+    if C <= 16:
+        return 16, 16, _C.crf_forward, _C.crf_marginals, _C.crf_reduce, _token_logits
+    return (16 * ((C + 15) // 16), 64, _C.crf_wide_forward, _C.crf_wide_marginals, _C.crf_wide_reduce,
+            lambda x, wc, bc, p, seed: _token_wide_fwd(x, wc, bc, None, p, seed)[0])
 
 
 class _TokenCRF(torch.autograd.Function):
     """Every row of h -> emissions (token_head.hip, logits-only) -> crf_fwd_kernel (alpha, Viterbi, back-trace, gold
     score) [-> crf_marg_kernel (beta, g0, parameter-gradient slabs) when a gradient is needed] -> crf_reduce_kernel
     (crf_head.hip). Backward: the token head's backward from the saved gradient table g0 (tok_bwd_kernel<true>) and the
-    three parameter gradients times dloss / max(N, 1) added into main_grad."""
+    three parameter gradients times dloss / max(N, 1) added into main_grad. With 17 .. 64 tags the same chain on the
+    kernels of token_head_wide.hip and crf_head_wide.hip (``_crf_kernels``)."""
 
     @staticmethod
     def forward(ctx, h2d, w, b, labels, cu, start, end, trans, p, seed):
@@ -1861,20 +1874,21 @@ class _TokenCRF(torch.autograd.Function):
         P = C * C + 2 * C
         cu32 = (cu if cu.dtype == torch.int32 else cu.to(torch.int32)).contiguous()
         lab = labels.contiguous().long()
-        logits = _token_logits(x, w.contiguous(), b.contiguous(), p, seed)
+        cp, ncnt, k_fwd, k_marg, k_reduce, emissions = _crf_kernels(C)
+        logits = emissions(x, w.contiguous(), b.contiguous(), p, seed)
         theta = _crf_theta(start, end, trans)
         needs_grad = any(ctx.needs_input_grad[i] for i in (0, 1, 2, 5, 6, 7))
-        alpha, bp, slab = _crf_workspace(R, B * P if needs_grad else 0, x.device)
+        alpha, bp, slab = _crf_workspace(R, B * P if needs_grad else 0, x.device, cp)
         pred = torch.empty(R, dtype=torch.int32, device=x.device)
         rec = torch.empty(4 * B, dtype=torch.float32, device=x.device)
-        out = torch.empty(4 + 16 + P, dtype=torch.float32, device=x.device)  # stats, cnt, dtheta
-        stats, cnt, dtheta = out[:4], out[4:20], out[20:]
-        _C.crf_forward(logits, cu32, lab, None, theta, alpha, bp, pred, rec)
+        out = torch.empty(4 + ncnt + P, dtype=torch.float32, device=x.device)  # stats, cnt, dtheta
+        stats, cnt, dtheta = out[:4], out[4:4 + ncnt], out[4 + ncnt:]
+        k_fwd(logits, cu32, lab, None, theta, alpha, bp, pred, rec)
         g0 = None
         if needs_grad:
             g0 = torch.empty((R, C), dtype=torch.float32, device=x.device)
-            _C.crf_marginals(logits, cu32, lab, theta, alpha, g0, slab)
-        _C.crf_reduce(rec, slab if needs_grad else None, B, C, stats, cnt, dtheta)
+            k_marg(logits, cu32, lab, theta, alpha, g0, slab)
+        k_reduce(rec, slab if needs_grad else None, B, C, stats, cnt, dtheta)
         ctx.save_for_backward(x, w, b, start, end, trans, g0, cnt, dtheta)
         ctx.cfg = (float(p), seed)
         ctx.mark_non_differentiable(logits, stats, pred)
@@ -1886,10 +1900,18 @@ class _TokenCRF(torch.autograd.Function):
         x, w, b, start, end, trans, g0, cnt, dtheta = ctx.saved_tensors
         p, seed = ctx.cfg
         C = w.shape[0]
-        g_w, g_b, dl, dh, part = _token_bwd_args(ctx, x, w, b, dloss)
         # g = g0 · dloss / max(N, 1), N = cnt[c] for every tag c
-        _C.token_head_bwd_given(x, w.contiguous(), g0, cnt, 1.0, dl, dh, part, g_w.buf.view(-1), g_b.buf.view(-1),
-                                p, _s64(seed))
+        if C <= 16:
+            g_w, g_b, dl, dh, part = _token_bwd_args(ctx, x, w, b, dloss)
+            _C.token_head_bwd_given(x, w.contiguous(), g0, cnt, 1.0, dl, dh, part, g_w.buf.view(-1),
+                                    g_b.buf.view(-1), p, _s64(seed))
+        else:
+            R, H = x.shape
+            g_w, g_b, dl = _Grad(w), _Grad(b), _dloss1(dloss, x.device)
+            dh = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            part = _workspace(_C.token_head_wide_bwd_blocks(R, H) * (C * H + C), x.device)
+            _C.token_head_wide_bwd_given(x, w.contiguous(), g0, cnt, 1.0, dl, dh, part, g_w.buf.view(-1),
+                                         g_b.buf.view(-1), p, _s64(seed))
         scale = dl / cnt[:1].clamp(min=1.0)
         grads = []
         for prm, lo, hi in ((start, C * C, C * C + C), (end, C * C + C, C * C + 2 * C), (trans, 0, C * C)):
@@ -1910,11 +1932,12 @@ def token_crf_decode(h2d, w, b, keep, cu, start, end, trans, p, seed):
     ``keep != 0`` (None: every row of a sequence)."""
     x = h2d.detach().contiguous()
     cu32, kp = _span_args(x, cu, keep)
-    logits = _token_logits(x, w.detach().contiguous(), b.detach().contiguous(), p, seed)
-    _, bp, _ = _crf_workspace(x.shape[0], 0, x.device)
+    cp, _, k_fwd, _, _, emissions = _crf_kernels(w.shape[0])
+    logits = emissions(x, w.detach().contiguous(), b.detach().contiguous(), p, seed)
+    _, bp, _ = _crf_workspace(x.shape[0], 0, x.device, cp)
     pred = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
     none = torch.empty(0, dtype=torch.float32, device=x.device)
-    _C.crf_forward(logits, cu32, None, kp, _crf_theta(start, end, trans), none, bp, pred, none)
+    k_fwd(logits, cu32, None, kp, _crf_theta(start, end, trans), none, bp, pred, none)
     return logits, pred
 
 

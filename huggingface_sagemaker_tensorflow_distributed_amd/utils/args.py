@@ -186,7 +186,7 @@ def _add_framework_flags(p: argparse.ArgumentParser) -> None:
                    help="token-classification only: a linear-chain CRF over the per-token scores (BERT-CRF). Training "
                         "maximises the likelihood of the whole tag sequence over each sequence's labelled tokens, "
                         "evaluation and accuracy use the Viterbi path. Refused for the other tasks and together with "
-                        "--label_smoothing_factor > 0; at most 16 labels run the fused kernels")
+                        "--label_smoothing_factor > 0; at most 64 labels run the fused kernels")
     g.add_argument("--max_answer_length", type=int, default=30,
                    help="question-answering: the longest span (in tokens) the best-span search returns")
     g.add_argument("--doc_stride", type=int, default=128,
